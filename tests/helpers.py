@@ -1,4 +1,5 @@
 """Shared test helpers: the state recipe used by tools/oracle/make_golden.py, repeated with the oracle."""
+import contextlib
 import os
 
 import numpy as np
@@ -9,6 +10,21 @@ from mm_distillnet_amd.synth import synth_state, synth_inputs, calibrate_bn_
 from oracle import effdet_ref as O
 
 _CACHE = {}
+
+# The golden fixtures were captured with 8 torch intra-op threads.  CPU reductions (batch-norm statistics, sums) split their work by the
+# thread count, so their last bits - and, through the int() truncation of box edges, whole pseudo-label pixels - depend on it: the oracle
+# runs at that count wherever it is compared with a fixture, whatever the host's CPU share.
+GOLDEN_THREADS = 8
+
+
+@contextlib.contextmanager
+def golden_threads():
+    n = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    try:
+        yield
+    finally:
+        torch.set_num_threads(n)
 
 
 def make_state(coef, cin, seed, calib_mod, cls_bias=-4.0):
@@ -25,7 +41,8 @@ def make_state(coef, cin, seed, calib_mod, cls_bias=-4.0):
                 O.forward(state, x, coef, True, masks)
             del state["_bn_momentum"]
 
-        calibrate_bn_(st, tf, synth_inputs(4, 256, seed=1000 + seed)[calib_mod], seed=seed)
+        with golden_threads():
+            calibrate_bn_(st, tf, synth_inputs(4, 256, seed=1000 + seed)[calib_mod], seed=seed)
         _CACHE[key] = (spec, st)
     spec, st = _CACHE[key]
     return spec, {k: v.clone() for k, v in st.items()}

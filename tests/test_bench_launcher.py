@@ -115,17 +115,18 @@ def test_work_skipping_switches_are_refused():
 
 def test_alt_leg_only_for_the_plain_full_record_command():
     """bench.py's second leg (the same command with MMD_MFMA_F32=1 in a child process, `alt_mfma_f32` in the record) must start only where
-    starting a process is safe and the record is the full one: fp32, one process, CPU-baseline leg on, no profiler preloaded (rocprofv3's
+    starting a process is safe and the record is the full one: --full, fp32, one process, CPU-baseline leg on, no profiler preloaded (rocprofv3's
     library initialises the GPU before the program starts - a process in that state must not start another program), not already on v_mfma_f32."""
     import argparse
     import bench
     def args(**kw):
-        d = dict(precision="fp32", no_alt=False, no_cpu_baseline=False, gpus=1)
+        d = dict(full=True, precision="fp32", no_alt=False, no_cpu_baseline=False, gpus=1)
         d.update(kw)
         return argparse.Namespace(**d)
     guard = "/usr/local/graft/lib/libasan.so.libclang_rt.asan.graft-execguard.so"
     assert bench.alt_leg_wanted(args(), {"LD_PRELOAD": guard})
     assert bench.alt_leg_wanted(args(), {})
+    assert not bench.alt_leg_wanted(args(full=False), {})       # a plain run times the headline only
     assert not bench.alt_leg_wanted(args(no_alt=True), {})
     assert not bench.alt_leg_wanted(args(no_cpu_baseline=True), {})
     assert not bench.alt_leg_wanted(args(precision="bf16"), {})
@@ -135,3 +136,36 @@ def test_alt_leg_only_for_the_plain_full_record_command():
     assert not bench.alt_leg_wanted(args(), {"LD_PRELOAD": "/opt/rocm/lib/rocprofiler-sdk/librocprofiler-sdk-tool.so"})
     assert not bench.alt_leg_wanted(args(), {"ROCPROF_OUTPUT_PATH": "/tmp/x"})
     assert not bench.alt_leg_wanted(args(), {}, skipping=["MMD_DEV_SKIP_WG"])
+
+
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per output, float32 (float64 kept), small arrays whole, large ones as a sample whose positions
+    depend only on the array's size, the whole dump within DUMP_BUDGET."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn(12_000_000, generator=g)
+    outs = {"loss": torch.tensor([0.5]), "count": torch.tensor([3, 4], dtype=torch.int32), "acc": torch.tensor([1.0, 2.0], dtype=torch.float64),
+            "rows": torch.randn(40, 6, generator=g), "big": big, "big2": big.view(3000, 4000) * 2.0}
+    total = bench.dump_outputs(outs, str(tmp_path / "a"))
+    assert total <= bench.DUMP_BUDGET
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in outs)
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in outs}
+    assert a["loss"].dtype == np.float32 and a["count"].dtype == np.float32 and a["acc"].dtype == np.float64
+    np.testing.assert_array_equal(a["count"], [3.0, 4.0])
+    np.testing.assert_array_equal(a["rows"], outs["rows"].reshape(-1).numpy())
+    assert 0 < a["big"].size < big.numel()
+    np.testing.assert_array_equal(a["big2"], 2.0 * a["big"])          # same size -> same sampled positions
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    for k in outs:
+        np.testing.assert_array_equal(np.load(tmp_path / "b" / (k + ".npy")), a[k])
+
+
+def test_plain_and_full_arguments():
+    """--full is off by default; --steps must be at least 1 (the record's ms_per_step is the timed region over --steps)."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("MMD_")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps" in p.stderr and p.stdout.strip() == ""

@@ -13,7 +13,14 @@ from oracle import effdet_ref as O
 from oracle import losses_ref as L
 from oracle import postproc_ref as P
 from oracle import step_ref as ST
-from helpers import make_state, check_summary, grad_state
+from helpers import make_state, check_summary, grad_state, golden_threads
+
+
+@pytest.fixture(autouse=True)
+def _at_golden_threads():
+    """the oracle at the fixtures' thread count (helpers.GOLDEN_THREADS), not at the host's CPU share"""
+    with golden_threads():
+        yield
 
 
 @pytest.mark.parametrize("coef", [2, 4])

@@ -7,7 +7,7 @@ set2="SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES S
 i=0
 for s in "$set1" "$set2"; do
   i=$((i+1))
-  timeout -k 10 400 rocprofv3 --pmc $s --kernel-trace --output-format csv -d $out/pmc$i -o p -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 > $out/pmc$i.log 2>&1 || { tail -3 $out/pmc$i.log; exit 1; }
+  timeout -k 10 400 rocprofv3 --pmc $s --kernel-trace --output-format csv -d $out/pmc$i -o p -- python3 bench.py --full --no-cpu-baseline --steps 2 --warmup 1 > $out/pmc$i.log 2>&1 || { tail -3 $out/pmc$i.log; exit 1; }
 done
 python3 - $out <<'PY' > $out/summary.txt
 import csv, sys, collections, glob
