@@ -249,6 +249,13 @@ int mmd_mta_kl_multi(const float* const* a_s, const float* const* a_t, float* co
 
 int mmd_mta_attention_bwd(const float* f, const float* da, float* df, int rows, int C, float p, int accumulate, hipStream_t stream);
 
+// AttentionLoss (src/loss/AttentionLoss.py:17-41, p = 2), every (pyramid level, teacher) pair of one step: the pairwise calls of
+// ModelWithNMSLoss(.Augmented).forward (src/optimization/train_methods.py:351-358) on the raw maps of mmd_mta_attention(p = 2).
+// Host arrays of device pointers as for mmd_mta_kl_multi: a_s[nlev], a_t[nteachers*nlev] teacher-major, da_s[nlev] nullable, HW[nlev].
+// loss[t*nlev + l] = mean_{b,j} (ahat_s - ahat_t)^2 (stored: no zeroing needed); da_s[l] = gscale * d(sum of the losses)/d a_s, stored
+// for every element of the B x HW[l] map.  ws: nteachers*nlev*B floats.  Bitwise reproducible (no float atomics; two launches).
+int mmd_at_loss_multi(const float* const* a_s, const float* const* a_t, float* const* da_s, const int* HW, int nlev, int nteachers, int B, float* loss, float gscale, float* ws, hipStream_t stream);
+
 // YetAnotherFocalLoss forward + gradients (src/loss/YetAnotherFocalLoss.py:27-190).
 int mmd_focal_loss(const float* cls, const float* reg, const float* anchors, const float* boxes, const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws, double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale, int to_logit, int* any_boxes, hipStream_t stream);
 

@@ -1,5 +1,6 @@
 // Distillation and detection losses, forward + gradient in the same pass — CDNA4 / gfx950.
 //   MTA attention transfer ...... src/loss/MTALoss.py:15-77   (quirk kept: kl_div is fed probabilities)
+//   AttentionLoss (p = 2) ....... src/loss/AttentionLoss.py:17-41
 //   focal + smooth-L1 ........... src/loss/YetAnotherFocalLoss.py:6-190
 // Both are HBM-streaming reductions: the MTA channel reduction uses one wave per pixel row with a
 // shuffle tree; the per-image softmax/KL rows and the anchor assignment use block reductions.
@@ -262,6 +263,139 @@ extern "C" int mmd_mta_attention_bwd(const float* f, const float* da, float* df,
   if (!f || !da || !df || rows <= 0 || C <= 0 || (C & 3)) return MMD_EINVAL;
   hipLaunchKernelGGL(mta_attention_bwd_kernel, dim3(cdiv((long long)rows * (C >> 2), 256)), dim3(256), 0, stream, f, da, df,
                      rows, C, p, accumulate);
+  return mmd_check_launch();
+}
+
+// ------------------------------------------------------------------ AttentionLoss (attention transfer, Zagoruyko & Komodakis)
+//   src/loss/AttentionLoss.py:17-41 with its default p = 2 (the cfg's `p` / `T` do not reach it), called once per teacher by
+//   ModelWithNMSLoss(.Augmented).forward (src/optimization/train_methods.py:351-358), summed with w_kd (src/optimization/traditional.py:176-181).
+// On the raw maps a[b,j] = mean_c f^2 of mmd_mta_attention:  ahat = a / max(||a[b,:]||_2, 1e-12) (F.normalize),
+//   loss[t*nlev + l] = sum_b sum_j (ahat_s - ahat_t)^2 / (B*HW)
+//   da_s = (g - ahat_s <ahat_s, g>) / ||a_s||  (g / 1e-12 where ||a_s|| <= 1e-12),  g = gscale * sum_t 2 (ahat_s - ahat_t) / (B*HW)
+// Bitwise reproducible, no float atomics: one block per (image, level) owns that image's da_s row and STORES it (the teachers are summed in
+// a fixed order inside the block); each block stores its per-teacher loss partial, a one-block launch sums the partials in image order.
+__device__ __forceinline__ void block_sum5(float (&v)[MTA_MAX_T + 1], float* sm, int tid) {      // five block_sums for one pair of barriers
+#pragma unroll
+  for (int i = 0; i <= MTA_MAX_T; ++i) v[i] = wave_sum(v[i]);
+  __syncthreads();
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i <= MTA_MAX_T; ++i) sm[(tid >> 6) * (MTA_MAX_T + 1) + i] = v[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i <= MTA_MAX_T; ++i) {
+    float r = 0.f;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) r += sm[w * (MTA_MAX_T + 1) + i];
+    v[i] = r;
+  }
+}
+struct AtMulti {
+  const float* a_s[MTA_MAX_LEV]; const float* a_t[MTA_MAX_T][MTA_MAX_LEV]; float* da[MTA_MAX_LEV]; int HW[MTA_MAX_LEV];
+  int nt, B; float gscale; float* part;     // part[(t*nlev + l)*B + b]: sum_j (ahat_s - ahat_t)^2 of image b
+};
+// grid (B, nlev).  Two dependent block reductions (the nt+1 squared norms; the nt loss sums + <ahat_s, G>), then the stored gradient.
+// The maps are held in REGISTERS in chunks of 256 x AT_RC elements (j = chunk * 256 * AT_RC + tid + 256 i): a level of one chunk (HW <= 4096,
+// every level at 512^2) is read from global memory once for the three passes, a larger one reloads its chunks in each pass.  (Re-reading
+// global memory in every pass cost 42 us per launch against mta_kl_multi_kernel's 21 us on the same maps.)
+#define AT_RC 16
+__global__ __launch_bounds__(256) void at_loss_multi_kernel(AtMulti m) {
+  __shared__ float sm[4 * (MTA_MAX_T + 1)];
+  const int b = blockIdx.x, l = blockIdx.y, nlev = gridDim.y, tid = threadIdx.x;
+  const int HW = m.HW[l], nt = m.nt, nch = (HW + 256 * AT_RC - 1) / (256 * AT_RC);
+  const float* as = m.a_s[l] + (size_t)b * HW;
+  const float* tp[MTA_MAX_T];
+#pragma unroll
+  for (int k = 0; k < MTA_MAX_T; ++k) tp[k] = k < nt ? m.a_t[k][l] + (size_t)b * HW : nullptr;
+  float ra[AT_RC], rt[MTA_MAX_T][AT_RC];      // outside the map: 0 (contributes exact zeros below)
+  auto load = [&](int c) {
+#pragma unroll
+    for (int i = 0; i < AT_RC; ++i) {
+      const int j = c * 256 * AT_RC + tid + 256 * i;
+      ra[i] = j < HW ? as[j] : 0.f;
+#pragma unroll
+      for (int k = 0; k < MTA_MAX_T; ++k) rt[k][i] = (k < nt && j < HW) ? tp[k][j] : 0.f;
+    }
+  };
+  float v[MTA_MAX_T + 1];
+#pragma unroll
+  for (int i = 0; i <= MTA_MAX_T; ++i) v[i] = 0.f;
+  for (int c = 0; c < nch; ++c) {
+    load(c);
+#pragma unroll
+    for (int i = 0; i < AT_RC; ++i) {
+      v[MTA_MAX_T] += ra[i] * ra[i];
+#pragma unroll
+      for (int k = 0; k < MTA_MAX_T; ++k) if (k < nt) v[k] += rt[k][i] * rt[k][i];
+    }
+  }
+  block_sum5(v, sm, tid);
+  const float ns_raw = sqrtf(v[MTA_MAX_T]), ns = fmaxf(ns_raw, 1e-12f);
+  float nk[MTA_MAX_T];
+#pragma unroll
+  for (int k = 0; k < MTA_MAX_T; ++k) nk[k] = fmaxf(sqrtf(v[k]), 1e-12f);
+  // G_j = sum_t (ahat_s - ahat_t): v[k] = sum_j (ahat_s - ahat_t)^2, v[MTA_MAX_T] = <ahat_s, G>
+#pragma unroll
+  for (int i = 0; i <= MTA_MAX_T; ++i) v[i] = 0.f;
+  for (int c = 0; c < nch; ++c) {
+    if (nch > 1) load(c);
+#pragma unroll
+    for (int i = 0; i < AT_RC; ++i) {
+      const float ah = ra[i] / ns;
+      float G = 0.f;
+#pragma unroll
+      for (int k = 0; k < MTA_MAX_T; ++k) if (k < nt) { const float d = ah - rt[k][i] / nk[k]; v[k] += d * d; G += d; }
+      v[MTA_MAX_T] += ah * G;
+    }
+  }
+  block_sum5(v, sm, tid);
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < MTA_MAX_T; ++k) if (k < nt) m.part[((size_t)k * nlev + l) * m.B + b] = v[k];
+  }
+  float* da = m.da[l];
+  if (!da) return;
+  const float dot = v[MTA_MAX_T];
+  const float cg = 2.f * m.gscale / ((float)m.B * (float)HW);
+  const bool clamped = !(ns_raw > 1e-12f);
+  for (int c = 0; c < nch; ++c) {
+    if (nch > 1) load(c);
+#pragma unroll
+    for (int i = 0; i < AT_RC; ++i) {
+      const int j = c * 256 * AT_RC + tid + 256 * i;
+      const float ah = ra[i] / ns;
+      float G = 0.f;
+#pragma unroll
+      for (int k = 0; k < MTA_MAX_T; ++k) if (k < nt) G += ah - rt[k][i] / nk[k];
+      if (j < HW) da[(size_t)b * HW + j] = clamped ? cg * G / 1e-12f : cg * (G - ah * dot) / ns;
+    }
+  }
+}
+// loss[i] = sum_b part[i*B + b] / (B * HW[l]), b in order (i = t*nlev + l)
+__global__ __launch_bounds__(64) void at_loss_sum_kernel(const float* __restrict__ part, float* __restrict__ loss, AtMulti m, int n, int nlev) {
+  const int i = threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int b = 0; b < m.B; ++b) s += part[(size_t)i * m.B + b];
+  loss[i] = s / ((float)m.B * (float)m.HW[i % nlev]);
+}
+extern "C" int mmd_at_loss_multi(const float* const* a_s, const float* const* a_t, float* const* da_s, const int* HW, int nlev,
+                                 int nteachers, int B, float* loss, float gscale, float* ws, hipStream_t stream) {
+  if (!a_s || !a_t || !HW || !loss || !ws || nlev < 1 || nlev > MTA_MAX_LEV || nteachers < 1 || nteachers > MTA_MAX_T || B <= 0)
+    return MMD_EINVAL;
+  AtMulti m{};
+  for (int l = 0; l < nlev; ++l) {
+    if (!a_s[l] || HW[l] <= 0) return MMD_EINVAL;
+    m.a_s[l] = a_s[l]; m.HW[l] = HW[l]; m.da[l] = da_s ? da_s[l] : nullptr;
+    for (int t = 0; t < nteachers; ++t) {
+      if (!a_t[t * nlev + l]) return MMD_EINVAL;
+      m.a_t[t][l] = a_t[t * nlev + l];
+    }
+  }
+  m.nt = nteachers; m.B = B; m.gscale = gscale; m.part = ws;
+  hipLaunchKernelGGL(at_loss_multi_kernel, dim3(B, nlev), dim3(256), 0, stream, m);
+  hipLaunchKernelGGL(at_loss_sum_kernel, dim3(1), dim3(64), 0, stream, ws, loss, m, nteachers * nlev, nlev);
   return mmd_check_launch();
 }
 

@@ -3,6 +3,7 @@ arguments, forward signatures / return structures and state-dict keys, backed by
 
   YetAnotherEfficientDet ...... src/YetAnotherEfficientDet.py:605-685
   MTALoss ..................... src/loss/MTALoss.py:9-77
+  AttentionLoss ............... src/loss/AttentionLoss.py:17-41
   YetAnotherFocalLoss ......... src/loss/YetAnotherFocalLoss.py:23-190
   load_model, extract_criterions_from_config ... src/utils/utils.py:441-590,1556-1668
 
@@ -14,6 +15,7 @@ step.DistillEngine, which also fuses the losses, pseudo-labels and optimizer and
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Dict, List, Optional
 
@@ -25,6 +27,7 @@ from . import _lib
 from .arch import make_spec
 from .engine import Net, Feat
 from .layout import state_layout
+from .step import KD_LOSSES
 
 call = _lib.call
 
@@ -238,6 +241,67 @@ class MTALoss(nn.Module):
         return _MTAFn.apply(self.T, self.p, len(g_s), len(teachers), *g_s, *[m.detach() for m in flat])
 
 
+class _ATFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nlev, *maps):
+        fs, ts = maps[:nlev], maps[nlev:]
+        dev = fs[0].device
+        B = fs[0].shape[0]
+        a_s, a_t, das, rows, hw = [], [], [], [], []
+        for f, t in zip(fs, ts):
+            _, C, H, W = f.shape
+            fr = f.permute(0, 2, 3, 1).contiguous().view(B * H * W, C)
+            a = torch.empty(B * H * W, device=dev)
+            call("mmd_mta_attention", fr, a, B * H * W, C, 2.0)
+            at = torch.empty(B * H * W, device=dev)
+            call("mmd_mta_attention", t.permute(0, 2, 3, 1).contiguous().view(B * H * W, C), at, B * H * W, C, 2.0)
+            a_s.append(a); a_t.append(at); das.append(torch.empty(B * H * W, device=dev)); rows.append(fr); hw.append(H * W)
+        losses = torch.empty(nlev, device=dev)
+        vp = ctypes.c_void_p
+        call("mmd_at_loss_multi", (vp * nlev)(*[x.data_ptr() for x in a_s]), (vp * nlev)(*[x.data_ptr() for x in a_t]),
+             (vp * nlev)(*[x.data_ptr() for x in das]), (ctypes.c_int * nlev)(*hw), nlev, 1, B, losses, 1.0,
+             torch.empty(nlev * B, device=dev))
+        ctx.nlev = nlev
+        ctx.shapes = [tuple(f.shape) for f in fs]
+        ctx.save_for_backward(*das, *rows)
+        return losses
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.nlev
+        das, rows = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        out = []
+        for l in range(n):
+            B, C, H, W = ctx.shapes[l]
+            df = torch.empty(B * H * W, C, device=g.device)
+            call("mmd_mta_attention_bwd", rows[l], (das[l] * g[l]).contiguous(), df, B * H * W, C, 2.0, 0)
+            out.append(df.view(B, H, W, C).permute(0, 3, 1, 2))
+        return (None, *out, *([None] * n))
+
+
+class AttentionLoss(nn.Module):
+    """src/loss/AttentionLoss.py:17-41: per level mean((normalize(mean_c f_s^p) - normalize(mean_c f_t^p))^2), stacked.  The HIP path
+    has p = 2 only, which is what the reference's factory builds (AttentionLoss() with its default p)."""
+
+    def __init__(self, p=2):
+        super().__init__()
+        if float(p) != 2.0:
+            raise Exception(f"AttentionLoss supports p = 2 on the HIP path (got {p})")
+        self.p = 2
+
+    def forward(self, g_s, g_t):
+        if not all(torch.is_tensor(t) for t in g_t):
+            # ModelWithNMSKDListLoss hands a per-teacher list: upstream's at_loss fails on it (AttributeError: 'list' object has no
+            # attribute 'shape')
+            raise Exception("AttentionLoss takes one teacher's feature maps, not a list of teachers (kdlist train methods)")
+        if len(g_s) != len(g_t) or any(tuple(s.shape) != tuple(t.shape) for s, t in zip(g_s, g_t)):
+            # (upstream adaptive-avg-pools the larger map; student and teachers share image_size and compound_coef here)
+            raise Exception("AttentionLoss on the HIP path needs student and teacher maps of the same shape")
+        if len(g_s) > 5:
+            raise Exception("AttentionLoss supports up to 5 pyramid levels on the HIP path")
+        return _ATFn.apply(len(g_s), *g_s, *[t.detach() for t in g_t])
+
+
 class _FocalFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cls, reg, anchors, boxes, nbox, maxg):
@@ -321,13 +385,30 @@ def load_model(model_type: str, config, modality: Optional[str] = None, device=N
     return model
 
 
+def loss_names_from_config(config, kd_default: str = "None") -> str:
+    """Checks the cfg's loss keys against what the HIP path has (src/utils/utils.py:1594-1668) -> the kd_loss name, one of KD_LOSSES.
+    main_loss must be YetAnotherFocalLoss; div_loss may be None or DistillKL, both inert as upstream (src/optimization/traditional.py:177
+    sets loss_div = 0); an absent kd_loss key reads as `kd_default`.  Shared by extract_criterions_from_config and train.step_config."""
+    main = config.get('main_loss', 'YetAnotherFocalLoss')
+    if main != 'YetAnotherFocalLoss':
+        raise Exception(f"Unsupported main_loss {main} on the HIP path")
+    div = config.get('div_loss', 'None')
+    if div not in ('None', None, 'DistillKL'):
+        raise Exception(f"Unsupported div_loss {div} on the HIP path")
+    kd = config.get('kd_loss', kd_default)
+    kd = 'None' if kd is None else str(kd)
+    if kd not in KD_LOSSES:
+        raise Exception(f"Unsupported kd_loss {kd} on the HIP path")
+    return kd
+
+
 def extract_criterions_from_config(config):
-    """(criterion_main, criterion_div, criterion_kd) for the shipped recipe (src/utils/utils.py:1556-1668)."""
-    if config['main_loss'] != 'YetAnotherFocalLoss':
-        raise Exception(f"Unsupported main_loss {config['main_loss']} on the HIP path")
-    kd = None
-    if config.get('kd_loss', 'None') == 'MTALoss':
-        kd = MTALoss(T=config['T'], p=config['p'])
-    elif config.get('kd_loss', 'None') not in ('None', None):
-        raise Exception(f"Unsupported kd_loss {config['kd_loss']} on the HIP path")
-    return YetAnotherFocalLoss(), None, kd
+    """(criterion_main, criterion_div, criterion_kd) for the supported criteria (src/utils/utils.py:1556-1668).  AttentionLoss is built
+    with its default p = 2 as upstream: the cfg's `p` / `T` belong to MTALoss."""
+    kd = loss_names_from_config(config)
+    crit = None
+    if kd == 'MTALoss':
+        crit = MTALoss(T=config['T'], p=config['p'])
+    elif kd == 'AttentionLoss':
+        crit = AttentionLoss()
+    return YetAnotherFocalLoss(), None, crit

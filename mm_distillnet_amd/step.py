@@ -26,6 +26,7 @@ from .store import Arena
 call = _lib.call
 TEACHER_ORDER = ("rgb", "depth", "thermal")     # ModuleDict insertion order in train.py:123-135
 OPT_MODES = {"Adam": 0, "AdamW": 1, "SGD": 2}
+KD_LOSSES = ("MTALoss", "AttentionLoss", "None")
 
 
 @dataclass
@@ -47,6 +48,7 @@ class StepConfig:
     momentum: float = 0.0              # SGD
     weight_decay: float = 0.0          # SGD: cfg weight_decay; AdamW: torch's default 1e-2 (the reference passes none)
     kd_mode: str = "pairwise"          # "pairwise" = ModelWithNMSLoss(.Augmented); "list" = ModelWithNMSKDListLoss
+    kd_loss: str = "MTALoss"           # cfg `kd_loss`: MTALoss | AttentionLoss (src/loss/AttentionLoss.py, p = 2 whatever `p` says) | None
     valid_prediction_ids: tuple = (6,)  # VOC id of "car" (src/datasets/BaseDataset.py:141-165)
     label_map: Optional[List[int]] = None
     inclusive_nms: bool = False
@@ -61,6 +63,12 @@ class StepConfig:
 class DistillEngine:
     def __init__(self, student_spec: NetSpec, teacher_specs: Dict[str, NetSpec], device, cfg: StepConfig,
                  world_size: int = 1, process_group=None):
+        if cfg.kd_loss not in KD_LOSSES:
+            raise Exception(f"Unsupported kd_loss {cfg.kd_loss} on the HIP path")
+        if cfg.kd_loss == "AttentionLoss" and cfg.kd_mode == "list":
+            # upstream's ModelWithNMSKDListLoss hands AttentionLoss a per-teacher LIST per level: at_loss fails at the first step
+            # (AttributeError: 'list' object has no attribute 'shape')
+            raise Exception("kd_loss AttentionLoss does not run with the kdlist train methods (upstream fails on the teachers' list)")
         self.cfg = cfg
         self.device = device
         self.world_size = world_size
@@ -235,12 +243,16 @@ class DistillEngine:
              1 if self.cfg.inclusive_nms else 0, float(S), B, rows, cnt, mask_ws, self.overflow, cap, self._nms_ws(B, cap))
         return rows, cnt
 
+    def _att_p(self) -> float:
+        """exponent of the attention maps: cfg `p` for MTALoss; AttentionLoss is built with its default p = 2 upstream (src/utils/utils.py)"""
+        return 2.0 if self.cfg.kd_loss == "AttentionLoss" else float(self.cfg.p)
+
     def _attention(self, net: Net):
         """Spatial attention maps a[b, j] = mean_c f^p of the five BiFPN outputs of `net` in ONE launch: the final cell writes
         them into one pyramid row buffer (engine._bifpn), so the maps are row slices of one vector.  -> (all, [per level])"""
         pyr, fcat = net._pyr, net._fcat
         a = self.ws.alloc((pyr["total"],))
-        call("mmd_mta_attention", fcat, a, pyr["total"], fcat.shape[1], float(self.cfg.p))
+        call("mmd_mta_attention", fcat, a, pyr["total"], fcat.shape[1], self._att_p())
         return a, [a[pyr["row0"][l]:pyr["row0"][l] + pyr["rows"][l]] for l in range(len(pyr["rows"]))]
 
     def labels_from_rows(self, per_teacher: List[List], A: int) -> List[tuple]:
@@ -297,12 +309,14 @@ class DistillEngine:
         A = cls_s.shape[1]
         self._caps(A)
         nlv = len(feats_s)
-        _, a_s = self._attention(st)
-        # gradient w.r.t. the student's maps, one vector over the pyramid rows (zeroed: teachers accumulate into it
-        # with atomics, and the padding rows of a pyramid must read as zero in the backward)
-        da_all = self.ws.alloc((st._pyr["total"],))
-        call("mmd_memset_async", da_all, 0, da_all.numel() * 4)
-        da = [da_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
+        use_kd = cfg.kd_loss != "None"          # kd_loss = None: no attention maps, no KD term, no feature gradient (loss_kd = zeros upstream)
+        if use_kd:
+            _, a_s = self._attention(st)
+            # gradient w.r.t. the student's maps, one vector over the pyramid rows (zeroed: MTA teachers accumulate into it
+            # with atomics, and the padding rows of a pyramid must read as zero in the backward)
+            da_all = self.ws.alloc((st._pyr["total"],))
+            call("mmd_memset_async", da_all, 0, da_all.numel() * 4)
+            da = [da_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
         nt = len(self.teachers) + (1 if (cfg.kd_mode == "list" and batch.get("aug_rgb") is not None) else 0)
         kd = self.ws.alloc((nt if cfg.kd_mode == "pairwise" else 1, nlv))
         call("mmd_memset_async", kd, 0, kd.numel() * 4)
@@ -361,14 +375,15 @@ class DistillEngine:
                 cls_p, reg_p, feats_p = net0.forward([batch[m] for m in list(self.teachers)[:npk]], train=False, pack=nets)
                 if teacher_labels is None:
                     rows_p, cnt_p = self._pseudo_labels(net0, cls_p, reg_p, npk * B, A, S)
-                _, a_lv = self._attention(net0)
+                if use_kd:
+                    _, a_lv = self._attention(net0)
             for gi in range(npk):
                 if teacher_labels is not None:
                     r, c = teacher_labels[gi]
                 else:
                     r, c = rows_p[gi * B:(gi + 1) * B], cnt_p[gi * B:(gi + 1) * B]
                 rows_t.append(r); cnt_t.append(c)
-                att_t.append([a_lv[l][gi * B * f.H * f.W:(gi + 1) * B * f.H * f.W] for l, f in enumerate(feats_p)])
+                att_t.append([a_lv[l][gi * B * f.H * f.W:(gi + 1) * B * f.H * f.W] for l, f in enumerate(feats_p)] if use_kd else None)
             passes = [p_ for p_ in passes if p_[3] is not None or p_[2] >= npk]      # (the KD-list variant's extra RGB pass still runs on its own)
         for pi, (mod, net, si, xin) in enumerate(passes):
             ti = si if xin is None else G
@@ -382,30 +397,36 @@ class DistillEngine:
             with torch.cuda.stream(side):
                 net.begin_step()
                 cls_t, reg_t, feats_t = net.forward(xin if xin is not None else (audio if mod == "audio" else batch[mod]), train=False)
-                if aug and B >= 2:      # average_batch_0_1 on the (already consumed by the heads) feature maps
+                if aug and B >= 2 and use_kd:      # average_batch_0_1 on the (already consumed by the heads) feature maps
                     for f in feats_t:
                         call("mmd_avg_image01", f.z, f.H * f.W * f.C)
                 if teacher_labels is not None:
                     r, c = teacher_labels[ti]
                 else:
                     r, c = self._pseudo_labels(net, cls_t, reg_t, B, A, S)
-                _, at = self._attention(net)
+                at = self._attention(net)[1] if use_kd else None
             rows_t.append(r); cnt_t.append(c); att_t.append(at)
         if concurrent:
             for side in self.side_streams:
                 main_stream.wait_stream(side)
-        # every (level, teacher) KL of the step in one launch (pairwise: nt x 5 losses; list: 5), then one launch for d attention / d f
-        vp = ctypes.c_void_p
-        p_as = (vp * nlv)(*[t.data_ptr() for t in a_s])
-        p_at = (vp * (nt * nlv))(*[att_t[ti][l].data_ptr() for ti in range(nt) for l in range(nlv)])
-        p_da = (vp * nlv)(*[t.data_ptr() for t in da])
-        hw = (ctypes.c_int * nlv)(*[f.H * f.W for f in feats_s])
-        call("mmd_mta_kl_multi", p_as, p_at, p_da, hw, nlv, nt, 0 if cfg.kd_mode == "pairwise" else 1, B, float(cfg.T), kd,
-             float(cfg.w_kd))
+        # every (level, teacher) KD term of the step in one launch (pairwise: nt x 5 losses; list: 5), then one launch for d attention / d f
+        if use_kd:
+            vp = ctypes.c_void_p
+            p_as = (vp * nlv)(*[t.data_ptr() for t in a_s])
+            p_at = (vp * (nt * nlv))(*[att_t[ti][l].data_ptr() for ti in range(nt) for l in range(nlv)])
+            p_da = (vp * nlv)(*[t.data_ptr() for t in da])
+            hw = (ctypes.c_int * nlv)(*[f.H * f.W for f in feats_s])
+            if cfg.kd_loss == "AttentionLoss":
+                call("mmd_at_loss_multi", p_as, p_at, p_da, hw, nlv, nt, B, kd, float(cfg.w_kd), self.ws.alloc((nt * nlv * B,)))
+            else:
+                call("mmd_mta_kl_multi", p_as, p_at, p_da, hw, nlv, nt, 0 if cfg.kd_mode == "pairwise" else 1, B, float(cfg.T), kd,
+                     float(cfg.w_kd))
         if train:
-            d_all = st._alloc(st._pyr["total"], feats_s[0].C)
-            call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr["total"], feats_s[0].C, float(cfg.p), 0)
-            dfe = [d_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
+            d_all, dfe = None, [None] * nlv
+            if use_kd:
+                d_all = st._alloc(st._pyr["total"], feats_s[0].C)
+                call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr["total"], feats_s[0].C, self._att_p(), 0)
+                dfe = [d_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
         # cross-teacher merge -> annotations
         boxes, nbox, G = self._merge(rows_t, cnt_t, B, aug)
         # focal + smooth-L1 with gradients w.r.t. (pre-sigmoid) classifier logits and regression

@@ -39,7 +39,7 @@ from mm_distillnet_amd.data import (SyntheticMultimodalDetection, RawSyntheticMu
                                     CachedBatches, collate, collate_raw, valid_classes_dict)
 from mm_distillnet_amd import _lib  # noqa: E402
 from mm_distillnet_amd import trainer as TR  # noqa: E402
-from mm_distillnet_amd.model import filter_state_dict  # noqa: E402
+from mm_distillnet_amd.model import filter_state_dict, loss_names_from_config  # noqa: E402
 from mm_distillnet_amd.step import DistillEngine, StepConfig  # noqa: E402
 from mm_distillnet_amd.synth import synth_state  # noqa: E402
 
@@ -83,11 +83,15 @@ def step_config(cfg) -> StepConfig:
     # valid_labels -> VOC ids of the classes a teacher prediction must have (src/datasets/BaseDataset.py:141-165, utils.py:285-323)
     vl = cfg.get("valid_labels", "car")
     vcd = valid_classes_dict(tuple(v.strip() for v in vl.split(",")) if vl else None)
+    # main_loss / div_loss / kd_loss checked as the facade's extract_criterions_from_config does; an absent kd_loss keeps MTALoss
+    kd_loss = loss_names_from_config(cfg, kd_default="MTALoss")
+    if kd_loss == "AttentionLoss" and "kdlist" in method:
+        raise Exception(f"kd_loss AttentionLoss does not run with {method} (upstream's at_loss fails on the per-teacher list)")
     return StepConfig(image_size=cfg.getint("image_size"), conf_threshold=cfg.getfloat("conf_threshold", 0.3),
                       nms_threshold=cfg.getfloat("nms_threshold", 0.5), T=float(cfg.get("T", 9)), p=float(cfg.get("p", 2)),
                       w_main=cfg.getfloat("w_main", 1.0), w_kd=cfg.getfloat("w_kd", 0.005), lr=cfg.getfloat("lr", 1e-4),
                       b1=cfg.getfloat("b1", 0.9), b2=cfg.getfloat("b2", 0.999), grad_clip=cfg.getfloat("grad_clip", -1),
-                      kd_mode="list" if "kdlist" in method else "pairwise",
+                      kd_mode="list" if "kdlist" in method else "pairwise", kd_loss=kd_loss,
                       valid_prediction_ids=tuple(sorted(vcd["predictions_i2txt"].keys())),
                       # src/optimization/traditional.py:136: augment = config.getboolean('audio_augmentation_merge'); only
                       # ModelWithNMSLossAugmented acts on it (key absent from the shipped cfg -> off)
