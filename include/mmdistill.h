@@ -257,6 +257,11 @@ int mmd_mta_attention_bwd(const float* f, const float* da, float* df, int rows, 
 int mmd_at_loss_multi(const float* const* a_s, const float* const* a_t, float* const* da_s, const int* HW, int nlev, int nteachers, int B, float* loss, float gscale, float* ws, hipStream_t stream);
 
 // YetAnotherFocalLoss forward + gradients (src/loss/YetAnotherFocalLoss.py:27-190).
+// boxes [B, maxg, 5] (x1,y1,x2,y2,label), nbox [B]: image b has min(nbox[b], maxg) boxes (a larger count is clamped, not an error); the
+// rows at and behind that count are never read.  An anchor's box is its FIRST maximum of the IoU (duplicates: the lower index wins).
+// Workspaces assign_ws int[B*A], npos_ws int[B], acc_ws double[2B] need no zeroing: all three are written before they are read.
+// loss_out [2] (regression, classification), dcls / dreg (nullable: loss only) are stored for every element.  any_boxes (nullable) is
+// sticky: set to 1 when the batch has a box, never cleared - the caller zeroes it once.
 int mmd_focal_loss(const float* cls, const float* reg, const float* anchors, const float* boxes, const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws, double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale, int to_logit, int* any_boxes, hipStream_t stream);
 
 // torch.optim.Adam step on a flat segment (src/optimization/train_methods.py:825-833, traditional.py:190).
@@ -284,20 +289,42 @@ int mmd_clip_grad_norm(float* g, long long n, float max_norm, double* sumsq_ws, 
 
 // Box decode + clip + conf threshold + class filter, ordered compaction
 // (src/YetAnotherEfficientDet.py:574-602, src/utils/utils.py:123-204).
+// over_scores [B, cap]: scores of the over-threshold anchors, cand [B, cap, 6]: (x1,y1,x2,y2,score,class) of those whose class is in
+// valid_class_mask, both in anchor order; n_over / n_keep [B] their counts.  Rows at and behind a count are left as they were.
+// Capacity: more than `cap` valid candidates in an image -> *overflow = 1, n_keep = cap, rows [0, cap) are the first cap candidates in
+// anchor order.  More than `cap` over-threshold anchors alone is NOT an overflow (only over_scores[i < n_keep] is ever indexed):
+// n_over = cap, over_scores holds the first cap.  Nothing is written at or behind row `cap`.
+// Workspaces score_ws float[B*A], clsid_ws / flags_ws uchar[B*A] need no zeroing (every entry is written before it is read), nor do
+// the outputs.  `overflow` is sticky (set, never cleared): the caller zeroes it.
 int mmd_decode_filter(const float* cls, const float* reg, const float* anchors, int B, int A, int NC, float conf_threshold, unsigned long long valid_class_mask, float image_size, float* score_ws, unsigned char* clsid_ws, unsigned char* flags_ws, float* over_scores, float* cand, int* n_over, int* n_keep, int* overflow, int cap, hipStream_t stream);
 
 // Per-teacher batched_nms + int truncation + label remap (src/utils/utils.py:205-231,285-323).
 // cand / out: [B, cap, 6] rows; mask_ws: B*1024*16 words; big_ws (nullable when cap <= 1024): B * mmd_nms_ws_floats(cap) floats.
 // The reference runs torchvision's NMS over EVERY over-threshold anchor (src/utils/utils.py:179-205, no cap): lists longer than
 // 1024 rows take a chunked (1024 rows at a time, exact greedy) path through big_ws.
+// Order: score descending, equal scores by ascending row index.  out row = (int(max(x1,0)), int(max(y1,0)), int(min(x2,S)), int(min(y2,S)),
+// over_scores[row index], label_map[class]); rows of cand / over_scores at and behind n_keep[b] (clamped to cap) are never read, rows
+// of out at and behind out_cnt[b] are left as they were.
+// Capacity: an image with more than 1024 rows and big_ws == NULL -> *overflow = 1 and the result is the NMS of its FIRST 1024 rows in
+// source order (the other rows do not take part, not even in the class offset).
+// mask_ws and big_ws need no zeroing (they may hold anything, e.g. the previous step's bytes); `overflow` is sticky: the caller zeroes it.
 int mmd_nms_teacher(const float* cand, const int* n_keep, const float* over_scores, const int* label_map, float nms_threshold, int inclusive, float image_size, int B, float* out, int* out_cnt, unsigned long long* mask_ws, int* overflow, int cap, float* big_ws, hipStream_t stream);
 
 // Cross-teacher concat + nms(0.5) + drop score (src/optimization/train_methods.py:361-411).
-// merge01 != 0: image 1 also takes image 0's rows, in front of its own, when both have rows (augment=True, :379-387).
+// merge01 != 0: image 1 also takes image 0's rows, in front of its own, when both have rows (augment=True, :379-387); ignored for B = 1.
+// Sources are [B, cap, 6] rows (x1,y1,x2,y2,score,label) with counts c*[B]; a count above cap is clamped to cap, rows at and behind a
+// count are never read.  Class-agnostic; order: score descending, equal scores by source order, then row index (the earlier teacher wins).
+// boxes [B, maxg, 5] (x1,y1,x2,y2,label) in keep order, nbox [B]; rows at and behind nbox[b] are left as they were.
+// Capacity: more than maxg kept rows -> *overflow = 1, nbox = maxg, rows [0, maxg) are the first maxg kept rows.  A concatenation of
+// more than 1024 rows with big_ws == NULL -> *overflow = 1 and the NMS runs over its first 1024 rows in concatenation order.
+// mask_ws and big_ws need no zeroing; `overflow` is sticky: the caller zeroes it.  nteachers outside 1..3, a null source among the first
+// nteachers, maxg <= 0 or cap <= 0 -> MMD_EINVAL, nothing is launched.
 int mmd_nms_merge(const float* t0, const int* c0, const float* t1, const int* c1, const float* t2, const int* c2, int nteachers, float iou_threshold, int inclusive, int B, float* boxes, int* nbox, int maxg, unsigned long long* mask_ws, int* overflow, int merge01, int cap, float* big_ws, hipStream_t stream);
 
 // The same merge over 1..4 sources (host arrays of device pointers, teacher order); the 4th source is the "augmentation" pass of
 // ModelWithNMSKDListLossAugmented (src/optimization/train_methods.py:73-110).  big_ws: B * mmd_nms_ws_floats(nsrc * cap * (merge01 ? 2 : 1)).
+// Same outputs, overflow conditions and workspace rules as mmd_nms_merge (same bits for nsrc <= 3); nsrc outside 1..4 or a null entry
+// in srcs / cnts -> MMD_EINVAL, nothing is launched.
 int mmd_nms_merge_n(const float* const* srcs, const int* const* cnts, int nsrc, float iou_threshold, int inclusive, int B, float* boxes, int* nbox, int maxg, unsigned long long* mask_ws, int* overflow, int merge01, int cap, float* big_ws, hipStream_t stream);
 
 // Floats per image of `big_ws` for NMS lists of up to nmax rows (0 when nmax <= 1024).  mmd_nms_merge: nmax = nteachers * cap * (merge01 ? 2 : 1).

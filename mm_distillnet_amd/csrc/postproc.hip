@@ -214,7 +214,7 @@ __global__ __launch_bounds__(1024) void pp_nms_kernel(NmsArgs a) {
     for (int s = 0; s < a.nsrc; ++s) { cnts0[s] = min(a.cnt[s][0], a.in_cap); n0 += cnts0[s]; }
     n += n0;
   }
-  if (n > PP_CAP && (!a.big_ws || n > a.nmax)) { if (tid == 0) *a.overflow = 1; n = PP_CAP; }      // no workspace: the old hard limit
+  if (n > PP_CAP && (!a.big_ws || n > a.nmax)) { if (tid == 0) *a.overflow = 1; n = PP_CAP; }      // no workspace: the NMS of the FIRST 1024 rows in source order
   auto row_ptr = [&](int i) -> const float* {
     int s = 0, img = b;
     if (i < n0) {           // image 0's rows first, teacher order preserved

@@ -39,3 +39,28 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     fresh = _lib._Lib(str(tmp_path / "nope.so"))
     with pytest.raises(RuntimeError, match="no CPU or PyTorch fallback"):
         fresh.load()
+
+
+def test_pseudo_label_entry_points_document_overflow_and_workspaces():
+    """The header is the contract tests/test_gpu_pseudo_labels.py holds the kernels to: for each entry point of the pseudo-label
+    path it says which buffers need no zeroing, and what an overflow leaves in the outputs."""
+    from mm_distillnet_amd import _lib
+    text = open(_lib.HEADER).read()
+
+    def comment_of(name):
+        lines = text[:text.index("int %s(" % name)].rstrip("\n").split("\n")
+        out = []
+        while lines and lines[-1].startswith("//"):
+            out.append(lines.pop()[2:].strip())
+        return " ".join(reversed(out))
+
+    for name in ("mmd_decode_filter", "mmd_nms_teacher", "mmd_nms_merge", "mmd_focal_loss"):
+        c = comment_of(name)
+        assert "need no zeroing" in c and "sticky" in c, name
+    for name in ("mmd_decode_filter", "mmd_nms_teacher", "mmd_nms_merge"):
+        assert "*overflow = 1" in comment_of(name), name
+    assert "first cap candidates in anchor order" in comment_of("mmd_decode_filter")
+    assert "FIRST 1024 rows in source order" in comment_of("mmd_nms_teacher")
+    assert "first maxg kept rows" in comment_of("mmd_nms_merge")
+    assert "Same outputs, overflow conditions and workspace rules as mmd_nms_merge" in comment_of("mmd_nms_merge_n")
+    assert "clamped" in comment_of("mmd_focal_loss")
