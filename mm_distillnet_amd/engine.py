@@ -16,6 +16,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+import threading
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -26,7 +27,6 @@ from .arch import NetSpec, BN_EPS, BN_MOMENTUM, pyramid_sizes
 from .store import ParamStore, Arena
 
 NONE, SWISH, SIGMOID = 0, 1, 2
-import threading
 
 _PACK = threading.local()      # .on: this thread is inside a pack forward (Net.forward(pack=...))
 # entry points a pack forward may issue WITHOUT the group descriptor: they read no per-net parameters (or, the stems, are issued once per net)
@@ -41,7 +41,6 @@ def call(name: str, *args):
     return _lib.call(name, *args)
 
 
-
 class WgLayer(ctypes.Structure):
     """MmdWgradLayer of include/mmdistill.h: one 1x1-conv weight gradient of the grouped launch (csrc/pw_wgrad_grouped.hip)."""
     _fields_ = [("dy", ctypes.c_void_p), ("x", ctypes.c_void_p), ("dw", ctypes.c_void_p), ("in_scale", ctypes.c_void_p),
@@ -51,29 +50,22 @@ class WgLayer(ctypes.Structure):
                 ("ws_off", ctypes.c_longlong)]
 
 
-# 1x1-conv weight gradients: deferred to the end of their backward segment and run as ONE persistent launch + a deterministic fold
-# (MMD_NO_WG_GROUP=1: one launch per layer on the weight-gradient stream, fp32 atomics - the round-1 schedule)
-WG_GROUP = not os.environ.get("MMD_NO_WG_GROUP")
-# the OTHER leaves (depthwise / squeeze-excite / fusion-weight / bias gradients) stay forked off the main chain where they arise: small and
-# latency-bound, they fill the main chain's gaps - deferring them to the segment end as well measured 20.8-22.1 ms/step against 20.5
-WG_DEFER = WG_GROUP and bool(os.environ.get("MMD_WG_DEFER"))
-# flush the grouped launch every WG_CHUNK recorded layers.  D2 records 99 layers per backward: 60 (round 2) = two launches, the second - every backbone layer below block 19 - alone at
-# the very end of the backward (0.93 ms exposed); 45 = three, the last one only blocks 4..0 + stem while the second overlaps the high-resolution blocks' main chain
-# (round 3, alternating runs: 16.52 / 16.81 -> 16.55 / 16.66 ms/step, medians 16.65 -> 16.47; 50: 16.70 / 16.82, 80: 16.99 / 17.01; round 2: 30 / 15 layers 20.5 / 20.8 vs 19.7 for 60)
-# round 4 (alternating runs, four rounds): 45: 15.02 - 15.08, 46: 15.17 - 15.25, 47: 14.87 - 14.94, 48 / 49: 14.97 - 15.01 ms/step - the last flush is the step's exposed
-# tail (rocprofv3: ~0.45 ms behind the main chain's last kernel at 45), 47 leaves it the two 256^2 project convs only; D4 and the bf16 modes do not care
-WG_CHUNK = int(os.environ.get("MMD_WG_CHUNK", "47"))
-# (dev) explicit flush points instead of the fixed stride: "47,80,94" = flush when the 47th, 80th, 94th layer of the backward has been recorded
-WG_POINTS = frozenset(int(v) for v in os.environ.get("MMD_WG_POINTS", "").split(",") if v.strip())
-WG_ROWS = int(os.environ.get("MMD_WG_ROWS", "4096"))      # rows per item: 4096 x (64x64 tile) measured best (1.33 ms per step vs 2.58 at 256)
-WG_BLOCKS = int(os.environ.get("MMD_WG_GRID", "4096"))
-# rows per item of a segment's LAST flush: it runs alone at the end of the backward (the thin 256^2 / 128^2 layers: 416 items of 4096 rows =
-# 1.6 rounds of one block per CU, 278 us exposed); shorter items balance and keep more loads in flight
-WG_ROWS_FINAL = int(os.environ.get("MMD_WG_ROWS_FINAL", "4096"))
-# grid of a flush that runs BESIDE the backward's main chain (every flush but the last of a segment).  A chip-filling grid of these long-running
-# blocks starves the chain's kernels of CU slots (round 4 trace: the two M131072 K24 N144 input-gradient GEMMs next to the second flush took
-# 380 us apiece against 77 us alone); a thin persistent grid leaves the chain its slots and has ~2 ms of backward left to finish in
-WG_BLOCKS_MID = int(os.environ.get("MMD_WG_GRID_MID", "4096"))
+# 1x1-conv weight gradients are recorded and run as ONE persistent launch + a deterministic fold per WG_CHUNK recorded layers (round 1 ran
+# one launch per layer on the weight-gradient stream, fp32 atomics).  The OTHER leaves (depthwise / squeeze-excite / fusion-weight / bias
+# gradients) fork off the main chain where they arise: small and latency-bound, they fill the main chain's gaps - deferring them to the
+# segment end as well measured 20.8-22.1 ms/step against 20.5.
+# D2 records 99 layers per backward: 60 (round 2) = two launches, the second - every backbone layer below block 19 - alone at the very end
+# of the backward (0.93 ms exposed); 45 = three, the last one only blocks 4..0 + stem while the second overlaps the high-resolution blocks'
+# main chain (round 3, medians 16.65 -> 16.47 ms/step; 50: 16.70 / 16.82, 80: 16.99 / 17.01; round 2: 30 / 15 layers 20.5 / 20.8 vs 19.7 for 60).
+# Round 4 (alternating runs, four rounds): 45: 15.02 - 15.08, 46: 15.17 - 15.25, 47: 14.87 - 14.94, 48 / 49: 14.97 - 15.01 ms/step - the last
+# flush is the step's exposed tail (rocprofv3: ~0.45 ms behind the main chain's last kernel at 45), 47 leaves it the two 256^2 project convs
+# only; D4 and the bf16 modes do not care
+WG_CHUNK = 47
+WG_ROWS = 4096        # rows per item: 4096 x (64x64 tile) measured best (1.33 ms per step vs 2.58 at 256)
+# grid cap of a flush.  A thinner persistent grid for the flushes that run BESIDE the main chain (whose kernels they starve of CU slots: the two
+# M131072 K24 N144 input-gradient GEMMs 380 us apiece there against 77 alone) only made it worse - 4096 / 1024 / 512 / 256 / 128 blocks ->
+# 16.34 / 16.33 / 16.45 / 16.96 / 18.47 ms/step: the chip is full there, the window's work is conserved (profiles/r04_notes.md)
+WG_BLOCKS = 4096
 
 
 @dataclass
@@ -122,40 +114,10 @@ class LazyDz:
     count: int
 
 
-LAZY_BN = not os.environ.get("MMD_NO_LAZY_BN")
-# BatchNorm-backward reduce passes folded into the launches that complete their upstream gradient (MMD_NO_BNSUM_FOLD=1: the round-2
-# schedule - a bn_bwd_reduce launch per BatchNorm and scale_acc launches for the skip / multi-consumer accumulations - for A/B timing)
-FOLD_SUMS = not os.environ.get("MMD_NO_BNSUM_FOLD")
-BN1_IN_DW = not os.environ.get("MMD_NO_BN1_IN_DW")    # MBConv: BatchNorm-1 backward in the depthwise input-gradient launch's prologue (no bn_bwd_apply, no dz1 tensor)
-# BiFPN: the pooled operand's gradient scattered (fp32 atomics at the window arg-max) by the node backward launch itself, no dx tensor and no
-# max-pool gather launch over the 4x larger source map; the BatchNorm sums of pooled tensors are then kept linearly (every contribution adds its share)
-POOL_SCATTER = not os.environ.get("MMD_NO_POOL_SCATTER")
-P5_IN_GEMM = not os.environ.get("MMD_NO_P5_IN_GEMM")  # MBConv: the pooled squeeze-excite / BN-1 backward pass in the project GEMM's epilogue (no chan_pool_bwd launch)
-SE_WG_BATCH = not os.environ.get("MMD_NO_SE_WG_BATCH")
-DW_S2_WG = not os.environ.get("MMD_NO_DW_S2_WG")         # ... and the conv's weight gradient (no dw_wgrad_kernel<k, 2> leaf)
-DW_S2_SUMS = not os.environ.get("MMD_NO_DW_S2_SUMS")     # stride-2 depthwise input gradient takes the BatchNorm-0 backward sums (csrc/dwconv.hip dw_bwd_data_s2_sums_kernel)
-# both squeeze-excite FC data gradients in one launch (mmd_se_fc_bwd_fused): correct, but every block recomputes its image's hidden gradient
-# (S*C MACs, serial per wave) - measured 17.0 -> 17.7 ms/step against the two wide launches; off unless MMD_SE_FUSED=1
-SE_FUSED = bool(os.environ.get("MMD_SE_FUSED"))
-# stem weight gradient straight from the NCHW image (mmd_stem_conv_bwd_weight) instead of im2col + a GEMM item of the last grouped flush
-STEM_WG_DIRECT = not os.environ.get("MMD_NO_STEM_WG_DIRECT")
-# round 4: backward of the thin-input high-resolution expand convs (BatchNorm-0 backward, input gradient, weight gradient) in one pass over
-# the 6x expanded gradient (csrc/mbconv_bwd_fused.hip): dz0 is neither stored nor read back, and the layer leaves the grouped weight-gradient
-# launch at the exposed end of the backward.  Taken for layers with at least this many rows (MMD_NO_MBW=1: the two-GEMM form, for A/B timing)
-# round 4: "lazy" BiFPN operands of the trainable net - a node's / down-channel conv's train-mode BatchNorm is applied by the CONSUMING node
-# kernels while they load the operand (forward: from the live batch sums; backward: finalized coefficients) instead of by an mmd_affine_act
-# launch behind every producer: 40 launches less on the student's forward chain (MMD_NO_LAZY_NODE=1: the materialising form, for A/B timing)
-LAZY_NODE = not os.environ.get("MMD_NO_LAZY_NODE")
-# round 4: whole-node BiFPN backward - the node's 1x1 conv's input gradient (BatchNorm backward in its operand prologue) runs inside the node
-# backward launch (mmd_bifpn_node_bwd_full) instead of as a GEMM launch in front of it: 40 launches off the backward's serial chain
-NODE_BWD_FULL = not os.environ.get("MMD_NO_NODE_BWD_FULL")
-STEM_WG_SIDE = bool(os.environ.get("MMD_STEM_WG_SIDE"))      # (dev: the stem's weight gradient on the second side stream, the earlier placement)
-# bf16 modes: the whole-node backward (whose 1x1 input-gradient product runs exact fp32 MFMA - closer to the fp32 reference than the mode's
-# operand-rounding rule asks for, like the whole-node forward) up to width 160; D2 bf16 13.48 -> 13.25 ms/step, D4 (224) 49.9 -> 52.2: there
-# the bf16 GEMM + two-launch form stays
-NODE_FULL_BF16 = not os.environ.get("MMD_NO_NODE_FULL_BF16")
-MBW_FUSED = not os.environ.get("MMD_NO_MBW")
-MBW_MIN_ROWS = int(os.environ.get("MMD_MBW_MIN_ROWS", "32768"))      # squeeze-excite backward: one data-gradient launch per block, one weight-gradient launch per segment
+# MBConv expand convs with a thin input at high resolution (round 4): BatchNorm-0 backward, input gradient and weight gradient in one pass over
+# the 6x expanded gradient (csrc/mbconv_bwd_fused.hip) - dz0 is neither stored nor read back, and the layer leaves the grouped weight-gradient
+# launch at the exposed end of the backward.  Taken for layers with at least this many rows
+MBW_MIN_ROWS = 32768
 
 
 def pack_nets(nets: List["Net"]) -> bool:
@@ -235,7 +197,6 @@ class Net:
         self.mark_block, self.mark_event = -1, None
         self._wg_pending: list = []          # deferred 1x1-conv weight gradients of the current backward segment
         self._wg_count = 0                   # layers recorded so far in this backward
-        self._leaf_pending: list = []        # other deferred leaves (closures), issued by _wg_flush
         self._wg_plans: Dict[tuple, dict] = {}  # (segment index, operand signature) -> planned table (built once: arena addresses repeat every step)
         self._wg_segment = 0
         self._linear: set = set()              # train forward: tensors that are a BiFPN node's POOLED operand (their gradient is scattered: linear sums)
@@ -309,7 +270,6 @@ class Net:
     def begin_step(self):
         """Reset the bump arenas and zero the accumulator arena (one memset for all per-step sums)."""
         self.arena.reset()
-        used = self.zarena.used_bytes()
         self.zarena.reset()
         for c in self.zarena.chunks:
             call("mmd_memset_async", c, 0, c.numel())
@@ -343,16 +303,14 @@ class Net:
             return (None, None, x.act, x.bn[0], x.bn[1], x.bn[2], x.bn[3])
         return (x.scale, x.shift, x.act, None, None, None, 0)
 
-    STATS_SLOTS = 0 if os.environ.get("MMD_NO_SLOTS") else 64
-    DW_WG = not os.environ.get("MMD_NO_DW_WG")          # stride-1 backbone layers: depthwise weight gradient inside the input-gradient launch
-    NODE_WG = not os.environ.get("MMD_NO_NODE_WG")      # BiFPN nodes: depthwise weight gradient inside the node's backward launch
-    FUSE_NODE_TRAIN = not os.environ.get("MMD_NO_NODE_FUSE_TRAIN")   # trainable net: a BiFPN node's forward (fusion, depthwise, 1x1 conv, BN sums) in one kernel
-    FUSE_NODE = not os.environ.get("MMD_NO_NODE_FUSE")  # frozen nets: a BiFPN node (fusion, depthwise, 1x1 conv, BN) in one kernel
-    FUSE_FRONT = not os.environ.get("MMD_NO_MBX")       # frozen nets: expand + depthwise of the thin-input blocks in one kernel
+    STATS_SLOTS = 64
+    # frozen nets: a BiFPN node (fusion, depthwise, 1x1 conv, BN) in one kernel where _node_fusable() says so.  A test aid, not a switch:
+    # tests/test_gpu_net.py turns it off on its nets to send a D2 pack forward through the two-launch node path
+    FUSE_NODE = True
     # widths above 160 (D4's 224): the whole-node kernel holds two 8x8-pixel tiles in 157 KB of LDS (one block per CU) and reads its 1x1
     # weights from L2 - a win on the latency-bound small maps, a loss on the large ones, where the two-launch path runs a chip-filling GEMM
     # (round 4, D4 / 768^2 at B = 8: every level fused 56.7 ms/step against 54.0 unfused)
-    NODE_FUSE_WIDE_MAXROWS = int(os.environ.get("MMD_NODE_FUSE_WIDE_MAXROWS", "1152"))      # (neutral there: fewer launches, same time; 4608: +0.4 ms; every level: +2.7 ms)
+    NODE_FUSE_WIDE_MAXROWS = 1152      # (neutral there: fewer launches, same time; 4608: +0.4 ms; every level: +2.7 ms)
 
     def _node_fusable(self, in0: "Feat") -> bool:
         if not self.ps.flat.is_cuda or _lib.LIB.load().mmd_bifpn_node_fused_supported(in0.C) != 1:
@@ -363,7 +321,7 @@ class Net:
         """(workspace, slots) for a BatchNorm-sum producer over M rows: the thin full-resolution layers would send
         thousands of same-address f64 atomics (memory-side, ~17 ns each) to 2C addresses; the kernels spread them over
         `slots` zeroed copies and fold.  Only worth a buffer when M is large (the C side decides whether to use it)."""
-        if stats is None or M < 16384 or not self.STATS_SLOTS:
+        if stats is None or M < 16384:
             return None, 0
         return self._zalloc((self.STATS_SLOTS * 2 * C,), torch.float64), self.STATS_SLOTS
 
@@ -497,7 +455,7 @@ class Net:
             self._use(inp)                  # the block's own path ...
             if blk.skip:
                 self._use(inp)              # ... and the identity skip
-            fused_front = (not train and blk.expand != 1 and self.FUSE_FRONT and ps.flat.is_cuda
+            fused_front = (not train and blk.expand != 1 and ps.flat.is_cuda
                            and _lib.LIB.load().mmd_mbconv_expand_dw_supported(inp.C, blk.cmid, blk.kernel, blk.stride) == 1)
             if fused_front:
                 f0 = None           # frozen net, thin input: expand + depthwise in one kernel below, the expanded tensor stays in LDS
@@ -682,7 +640,7 @@ class Net:
             return Feat(y, in0.B, in0.H, in0.W, in0.C)
         # (also in the bf16 modes: the node's 1x1 conv then runs exact fp32 products in the forward - closer to the fp32 reference than the
         # mode's operand-rounding rule asks for; its two gradient GEMMs follow the mode)
-        if train and self.FUSE_NODE_TRAIN and self.NODE_WG and self._node_fusable(in0):
+        if train and self._node_fusable(in0):
             # trainable net: fusion + depthwise + 1x1 conv + BatchNorm sums in one launch (raw z out, depthwise output kept for the backward)
             name, W = f"{cell}.{conv}", in0.C
             bn_name = f"{name}.bn"
@@ -718,22 +676,20 @@ class Net:
                 call("mmd_affine_act", z, None, None, a[4][0], a[4][1], a[4][2], a[4][3], NONE, None, 0, None, y, in0.M, W)
                 out = Feat(y, in0.B, in0.H, in0.W, W)
                 self._bnout[y.data_ptr()] = (z, a[2], a[3], W, None, 0)
-            tape.setdefault(cell + ".nodes", []).append({"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "f": zdf, "conv": conv,
+            tape.setdefault(cell + ".nodes", []).append({"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "conv": conv,
                                                          "zd": zdf, "z": z, "bn": a, "out": out})
             return out
         # the fused activation is not materialised: the node's backward launch recomputes it, also for the depthwise weight gradient
-        # (MMD_NO_NODE_WG=1: the earlier form - f written here, weight gradient by its own launch on the side stream - for A/B timing)
-        f = self._alloc(in0.M, in0.C) if (train and not self.NODE_WG) else None
         zd = self._alloc(in0.M, in0.C)
         self._c("mmd_bifpn_node_dw_fwd", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                self.ps.w(f"{cell}.{conv}.depthwise_conv.conv.weight"), f, zd, in0.B, in0.H, in0.W, in0.C)
-        ff = Feat(f if f is not None else zd, in0.B, in0.H, in0.W, in0.C)
+                self.ps.w(f"{cell}.{conv}.depthwise_conv.conv.weight"), None, zd, in0.B, in0.H, in0.W, in0.C)
+        ff = Feat(zd, in0.B, in0.H, in0.W, in0.C)      # (stands for the fused input of _sep_bn, which only reads its geometry: zd is given)
         for operand in (in0, in1, up, pl):
             if operand is not None:
                 self._use(operand)
         if pl is not None and train:
             self._linear.add(pl.z.data_ptr())
-        rec = {"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "f": ff, "conv": conv}
+        rec = {"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "conv": conv}
         out = self._sep_bn(f"{cell}.{conv}", ff, train, rec, y=y, zd=zd)
         rec["out"] = out
         if train:
@@ -742,10 +698,11 @@ class Net:
 
     def _bifpn(self, taps: List[Feat], train: bool, tape: dict) -> List[Feat]:
         feats: List[Feat] = list(taps)
-        # lazy operands need every node on the whole-node train kernel (widths <= 160), the scatter form of the pooled operand's gradient
-        # (the gather launch reads operand values) and no test hooks that read / overwrite materialised outputs
-        self._lazy = (train and LAZY_NODE and self.FUSE_NODE_TRAIN and self.NODE_WG and FOLD_SUMS and POOL_SCATTER and self.ps.flat.is_cuda
-                      and self.probe is None and self.force_out is None and self.spec.fpn_w <= 160
+        # "lazy" BiFPN operands of the trainable net (round 4): a node's / down-channel conv's train-mode BatchNorm is applied by the CONSUMING
+        # node kernels while they load the operand (forward: from the live batch sums; backward: finalized coefficients) instead of by an
+        # mmd_affine_act launch behind every producer: 40 launches less on the student's forward chain.  They need every node on the
+        # whole-node train kernel (widths <= 160) and no test hooks that read / overwrite materialised outputs
+        self._lazy = (train and self.ps.flat.is_cuda and self.probe is None and self.force_out is None and self.spec.fpn_w <= 160
                       and _lib.LIB.load().mmd_bifpn_node_fused_supported(self.spec.fpn_w) == 1)
         lz = self._lazy
         for c in range(self.spec.fpn_cells):
@@ -913,7 +870,7 @@ class Net:
         s = self._slot(f)
         s.remaining -= 1
         info = self._bnout.get(f.z.data_ptr())
-        if FOLD_SUMS and POOL_SCATTER and info is not None and self.ps.flat.is_cuda and f.z.data_ptr() in self._linear:
+        if info is not None and self.ps.flat.is_cuda and f.z.data_ptr() in self._linear:
             # linear mode (the tensor is max-pooled by some node, whose backward scatters into its gradient): every contribution adds the
             # sums of its OWN share (7th element = 1); they are complete when the last one has, provided none was unable to
             # Exclusivity: the node backward's LDS-tile scatter reads the interior of this gradient at block start and stores it
@@ -933,7 +890,7 @@ class Net:
                 s.sums = self._zalloc((2 * C,), torch.float64)
             s.have_sums = s.remaining == 0 and s.linear_ok
             return s, (z, mu, istd, s.sums, mul_b, rpi, 1)
-        if not (FOLD_SUMS and can_sum and s.remaining == 0 and info is not None and self.ps.flat.is_cuda):
+        if not (can_sum and s.remaining == 0 and info is not None and self.ps.flat.is_cuda):
             return s, None
         z, mu, istd, C, mul_b, rpi = info
         s.sums = self._zalloc((2 * C,), torch.float64)
@@ -976,53 +933,37 @@ class Net:
 
     def _pw_wgrad(self, dy: torch.Tensor, xz: torch.Tensor, dw: torch.Tensor, M: int, K: int, N: int, in_scale=None, in_shift=None,
                   in_act: int = NONE, gate=None, rpi: int = 1):
-        """dW[N,K] (+)= dY^T pro(X).  Grouped mode: recorded, computed by _wg_flush() at the end of the backward segment."""
-        # precision "bf16": grouped as well (round 4, mmd_wgrad_grouped_bf16) where the per-layer launches are skeleton-bound - D2 / 512^2 in
-        # bf16 15.50 -> 14.64 ms/step; at D4 / 768^2 the layers are tall enough that the per-layer launches on the side stream measure the
-        # same or better (53.0-53.3 vs 53.5-53.8 ms), so tall nets keep them (rows of the stem output decide; MMD_WG_GROUP_BF16=0/1 forces)
-        if not WG_GROUP or not self.ps.flat.is_cuda or (self.precision != "fp32" and not self._group_bf16()):
+        """dW[N,K] (+)= dY^T pro(X): recorded, computed by _wg_flush() every WG_CHUNK layers and at the end of the backward segment."""
+        if not self.ps.flat.is_cuda or (self.precision != "fp32" and not self._group_bf16()):
             with self._wgrad_stream():
                 call("mmd_pwconv_bwd_weight" + self._sfx, dy, xz, dw, M, K, N, in_scale, in_shift, in_act, gate, rpi)
             return
         self._wg_pending.append((dy, xz, dw, M, K, N, in_scale, in_shift, in_act, gate, rpi))
         self._wg_count += 1
-        if WG_POINTS:
-            if self._wg_count in WG_POINTS:
-                self._wg_flush(final=False)
-        elif WG_CHUNK > 0 and self._wg_count % WG_CHUNK == 0:
+        if self._wg_count % WG_CHUNK == 0:
             # (counted over the whole backward, not per segment: the split backward of the data-parallel step then flushes at the same layers as
             # the one-segment form - its second segment's 11 layers would otherwise all sit in the exposed last flush)
-            self._wg_flush(final=False)
+            self._wg_flush()
 
     def _group_bf16(self) -> bool:
-        env = os.environ.get("MMD_WG_GROUP_BF16")
-        if env is not None:
-            return env not in ("", "0")
+        """precision "bf16": grouped as well (round 4, mmd_wgrad_grouped_bf16) where the per-layer launches are skeleton-bound - D2 / 512^2 in
+        bf16 15.50 -> 14.64 ms/step; at D4 / 768^2 the layers are tall enough that the per-layer launches on the side stream measure the
+        same or better (53.0-53.3 vs 53.5-53.8 ms), so tall nets keep them: the rows of the stem output decide."""
         stem = self.tape.get("stem")
         return stem is None or stem[1].M <= 600000
 
     def _leaf(self, fn):
         """A leaf of the backward graph other than a 1x1-conv weight gradient (depthwise / squeeze-excite / fusion-weight / bias
-        gradients): in grouped mode it is issued by _wg_flush() with the rest, behind ONE cross-stream dependency, instead of forking
-        off the main chain at ~160 points of the step (every fork is an event record + wait = a cross-branch edge of the graph)."""
-        if WG_DEFER and self.ps.flat.is_cuda:
-            self._leaf_pending.append(fn)
-        else:
-            with self._wgrad_stream():
-                fn()
+        gradients): issued on the weight-gradient stream at once (see WG_CHUNK: holding them back to the flushes measured worse)."""
+        with self._wgrad_stream():
+            fn()
 
-    def _wg_flush(self, final: bool = True):
-        """Launch the deferred weight gradients of this backward segment: one persistent grid over all (layer, tile, split) items
-        and one fold, on the weight-gradient stream behind everything issued so far.  final: nothing of the main chain runs beside
-        this flush (end of a backward segment): full-width grid; otherwise the thin one (WG_BLOCKS_MID)."""
+    def _wg_flush(self):
+        """Launch the recorded weight gradients: one persistent grid over all (layer, tile, split) items and one fold, on the
+        weight-gradient stream behind everything issued so far."""
         pend, self._wg_pending = self._wg_pending, []
-        leaves, self._leaf_pending = self._leaf_pending, []
         seg = self._wg_segment
         self._wg_segment += 1
-        if leaves:
-            with self._wgrad_stream():
-                for fn in leaves:
-                    fn()
         if not pend:
             return
         ptr = lambda t: 0 if t is None else t.data_ptr()
@@ -1040,7 +981,7 @@ class Net:
                 arr[i].in_scale, arr[i].in_shift, arr[i].gate = ptr(a) or None, ptr(b) or None, ptr(gt) or None
                 arr[i].M, arr[i].K, arr[i].N, arr[i].in_act, arr[i].rows_per_image = M, K, N, act, max(int(rpi), 1)
             ni, nt, wsf = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
-            rc = _lib.LIB.load().mmd_wgrad_plan(ctypes.cast(arr, ctypes.c_void_p), n, WG_ROWS_FINAL if final else WG_ROWS, ctypes.cast(ctypes.pointer(ni), ctypes.c_void_p),
+            rc = _lib.LIB.load().mmd_wgrad_plan(ctypes.cast(arr, ctypes.c_void_p), n, WG_ROWS, ctypes.cast(ctypes.pointer(ni), ctypes.c_void_p),
                                                 ctypes.cast(ctypes.pointer(nt), ctypes.c_void_p), ctypes.cast(ctypes.pointer(wsf), ctypes.c_void_p))
             if rc != 0:
                 raise RuntimeError(f"mmd_wgrad_plan failed with status {rc}")
@@ -1049,11 +990,11 @@ class Net:
                     "flops": float(sum(2.0 * M * K * N for _, _, _, M, K, N, *_ in pend)),
                     "bytes": float(sum(4.0 * (M * K + M * N + N * K) for _, _, _, M, K, N, *_ in pend)),
                     # every layer's M a multiple of 32 (any net at B >= 2): the launch runs without row clamps / masks (mmd_wgrad_grouped_form)
-                    "rows32": int(all(M % 32 == 0 for _, _, _, M, *_ in pend) and not os.environ.get("MMD_NO_WG_R32"))}
+                    "rows32": int(all(M % 32 == 0 for _, _, _, M, *_ in pend))}
             self._wg_plans[(seg, sig)] = plan
         ws = self._alloc(plan["ws"])
         with self._wgrad_stream():
-            call("mmd_wgrad_grouped_form", plan["table"], plan["n"], plan["items"], plan["tiles"], ws, WG_BLOCKS if final else WG_BLOCKS_MID,
+            call("mmd_wgrad_grouped_form", plan["table"], plan["n"], plan["items"], plan["tiles"], ws, WG_BLOCKS,
                  plan["flops"], plan["bytes"], 1 if self._sfx else 0, plan["rows32"])
 
     def _bn_bwd(self, g_in: torch.Tensor, z: torch.Tensor, aff, bn_name: str, act: int, M: int, C: int, rpi: int = 0,
@@ -1066,7 +1007,7 @@ class Net:
             sums = self._zalloc((2 * C,), torch.float64)
             call("mmd_bn_bwd_reduce", g_in, z, aff[0], aff[1], aff[2], aff[3], act, mul_bc, mul_b, add_bc, rpi, None, sums, M, C,
                  *self._stats_ws(sums, M, C))
-        if lazy and LAZY_BN and mul_bc is None and add_bc is None:
+        if lazy and mul_bc is None and add_bc is None:
             return LazyDz(g_in, z, aff, sums, act, mul_b, rpi, bn_name, M)
         dz = self._alloc(M, C)
         call("mmd_bn_bwd_apply", g_in, z, aff[2], aff[3], b["gamma"], sums, M, dz, b["dgamma"], b["dbeta"], M, C,
@@ -1095,7 +1036,7 @@ class Net:
                     self._wg_read_done = torch.cuda.current_stream().record_event() if ps.flat.is_cuda else None
                 return None
             dzm = self._alloc(M, N)
-            if (into is not None and FOLD_SUMS and MBW_FUSED and M >= MBW_MIN_ROWS and L.act == SWISH and L.mul_b is None and gate is None
+            if (into is not None and M >= MBW_MIN_ROWS and L.act == SWISH and L.mul_b is None and gate is None
                     and x.scale is None and x.bn is None and x.act == NONE and ps.flat.is_cuda
                     and _lib.LIB.load().mmd_mbconv_expand_bwd_supported(K, N) == 1):
                 # thin-input expand conv of a high-resolution block: one pass over (g0, z0) - input gradient, weight gradient, no dz0 in HBM
@@ -1108,7 +1049,7 @@ class Net:
                 call("mmd_mbconv_expand_bwd_fused", L.g, L.z, x.z, ps.w(wkey), slot.t, residual, ps.g(wkey), M, K, N, L.aff[0], L.aff[1], L.aff[2],
                      L.aff[3], L.sums, L.count, b["dgamma"], b["dbeta"], *xsa)
                 return None
-            if into is not None and FOLD_SUMS:
+            if into is not None:
                 slot, xs = self._contrib(into, True)
                 assert xs is None or not xs[6], "the GEMM epilogue sums the accumulated total: not a linear-sum (pooled) tensor"
                 residual = slot.t
@@ -1135,9 +1076,6 @@ class Net:
                 return dx
             call("mmd_pwconv_bwd_data_bn" + self._sfx, L.g, L.z, ps.w_t(wkey), dx, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"])
             self._pw_wgrad(dzm, x.z, ps.g(wkey), M, K, N, *xargs)
-            if into is not None:
-                self._acc(into, dx)
-                return None
             return dx
         if bias_key:
             self._leaf(lambda dz=dz, gb=ps.g(bias_key): call("mmd_colsum", dz, gb, M, N))
@@ -1152,43 +1090,34 @@ class Net:
             return None
         return dx
 
-    def _dw_bwd(self, dzd: torch.Tensor, x: Feat, wkey: str, k: int, s: int, want_dx: bool = True, bn_aff=None):
+    def _dw_bwd(self, dzd: torch.Tensor, x: Feat, wkey: str, k: int, s: int, bn_aff=None):
         """-> dx, or (dx, sums) when `bn_aff` = (scale, shift, mean, invstd) of the BatchNorm(+swish) that produced x: the
-        stride-1 input-gradient launch then also accumulates that BN's backward sums (no separate reduce pass) and the conv's weight
-        gradient (tile kernel; for the 3x3 layers that gives up the faster row-streaming input-gradient kernel and still wins: a
-        weight-gradient leaf costs its full kernel time on the saturated chip - 18.44 -> 18.27 ms/step)."""
+        input-gradient launch then also accumulates that BN's backward sums (no separate reduce pass; stride 2, round 5: they ride in the
+        gather launch too) and, except for thin stride-1 layers, the conv's weight gradient (tile kernel; for the 3x3 layers that gives up
+        the faster row-streaming input-gradient kernel and still wins: a weight-gradient leaf costs its full kernel time on the saturated
+        chip - 18.44 -> 18.27 ms/step)."""
         ps = self.ps
-        wg_inside = self.DW_WG and want_dx and bn_aff is not None and ((s == 1 and x.C >= 64) or (s == 2 and DW_S2_SUMS and DW_S2_WG))      # (block 0, 32 channels at 256^2: 221 us inside vs 47 + 67)
+        wg_inside = bn_aff is not None and (s == 2 or x.C >= 64)      # (block 0, 32 channels at 256^2: 221 us inside vs 47 + 67)
         if not wg_inside:
             self._leaf(lambda x=x, dzd=dzd, gw=ps.g(wkey): call("mmd_dwconv_bwd_weight", x.z, dzd, gw, x.B, x.H, x.W, x.C, k, s, x.scale, x.shift,
                                                                  x.act))
-        if not want_dx:
-            return None
         dx = self._alloc(x.M, x.C)
-        if bn_aff is not None and (s == 1 or DW_S2_SUMS):      # (stride 2, round 5: the sums ride in the gather launch too - no reduce pass)
-            sums = self._zalloc((2 * x.C,), torch.float64)
-            call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, x.z, bn_aff[0], bn_aff[1], bn_aff[2],
-                 bn_aff[3], sums, *self._stats_ws(sums, x.M, x.C), ps.g(wkey) if wg_inside else None)
-            return dx, sums
-        call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, None, None, None, None, None, None, None, 0, None)
-        return (dx, None) if bn_aff is not None else dx
+        if bn_aff is None:
+            call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, None, None, None, None, None, None, None, 0, None)
+            return dx
+        sums = self._zalloc((2 * x.C,), torch.float64)
+        call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, x.z, bn_aff[0], bn_aff[1], bn_aff[2],
+             bn_aff[3], sums, *self._stats_ws(sums, x.M, x.C), ps.g(wkey) if wg_inside else None)
+        return dx, sums
 
-    PYR_WG = not os.environ.get("MMD_NO_PYR_WG")
-
-    def _pyr_dw_bwd(self, dzd, wkey: str, g, desc, C: int, ls: int, x, sc, sh, act: int, bn=None) -> bool:
+    def _pyr_dw_bwd(self, dzd, wkey: str, g, desc, C: int, ls: int, x, sc, sh, act: int, bn=None):
         """Input gradient of a shared-weight pyramid depthwise conv; its weight gradient rides in the same launch, and so do the sums of
-        the BatchNorm(+swish) backward that consumes g when `bn` = (mean, invstd, sums) of x's producer is given (-> True: the caller
-        skips that reduce pass).  MMD_NO_PYR_WG=1: weight gradient by its own launch on the weight-gradient stream (earlier form, A/B)."""
+        the BatchNorm(+swish) backward that consumes g: `bn` = (mean, invstd, sums) of x's producer (None: x is the heads' input, whose
+        BatchNorms belong to the BiFPN)."""
         ps = self.ps
-        if self.PYR_WG:
-            mu, istd, sums = bn if bn is not None else (None, None, None)
-            call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, ls, x, sc, sh, act, ps.g(wkey),
-                 mu, istd, sums)
-            return bn is not None
-        self._leaf(lambda: call("mmd_dwconv3_pyr_bwd_weight", x, dzd, ps.g(wkey), desc, C, sc, sh, act, ls))
-        call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, 0, None, None, None, NONE, None,
-             None, None, None)
-        return False
+        mu, istd, sums = bn if bn is not None else (None, None, None)
+        call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, ls, x, sc, sh, act, ps.g(wkey),
+             mu, istd, sums)
 
     def _head_bwd(self, hname: str, per_anchor: int, dout: torch.Tensor, tape: dict, pyr: dict, A: int, C: int):
         """Backward of one head over the whole pyramid; returns the gradient w.r.t. the pyramid feature buffer."""
@@ -1206,20 +1135,18 @@ class Net:
         call("mmd_pwconv_bwd_data" + self._sfx, dy, ps.w_t(hw_key), dzd, Mt, C, nout, 0)
         xo = rec["hx_off"]
         # the depthwise weight gradient rides in the (flipped) input-gradient launch: a leaf launch's kernel time is paid in full; so do
-        # the sums of the BatchNorm backward that consumes g (x's producer), instead of a reduce pass over (g, z)
+        # the sums of the BatchNorm backward that consumes g (x's producer), instead of a reduce pass over (g, z): every layer's `sums`
+        # below were filled by the depthwise launch behind it
         bsums = self._zalloc((2 * 5 * ls,), torch.float64)
         off0 = rec["layers"][0]["off"]
         g = self._alloc_pyr(pyr, C)
-        have_sums = self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec["hx"], self.t_scale[xo:], self.t_shift[xo:],
-                                     SWISH, bn=(self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
+        self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec["hx"], self.t_scale[xo:], self.t_shift[xo:],
+                         SWISH, bn=(self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
         for i in reversed(range(spec.head_layers)):
             L = rec["layers"][i]
             cname = f"{hname}.conv_list.{i}"
             o = L["off"]
             sums = bsums[2 * (o - off0):]
-            if not have_sums:
-                call("mmd_bn_bwd_reduce_pyr", g, L["z"], self.t_scale[o:], self.t_shift[o:], self.t_mean[o:], self.t_invstd[o:],
-                     SWISH, desc, ls, None, sums, C)
             dz = self._alloc_pyr(pyr, C)
             call("mmd_bn_bwd_apply_pyr", g, L["z"], self.t_mean[o:], self.t_invstd[o:], ps.flat[ps.gamma_off + o:], sums,
                  desc, ls, dz, ps.grad[ps.gamma_off + o:], ps.grad[ps.beta_off + o:], C, self.t_scale[o:], self.t_shift[o:],
@@ -1230,9 +1157,9 @@ class Net:
             call("mmd_pwconv_bwd_data" + self._sfx, dz, ps.w_t(wkey), dzd, Mt, C, C, 0)
             xo = L["x_off"]
             g = self._alloc_pyr(pyr, C)
-            have_sums = self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L["x"], None if xo is None else self.t_scale[xo:],
-                                         None if xo is None else self.t_shift[xo:], NONE if xo is None else SWISH,
-                                         bn=None if xo is None else (self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
+            self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L["x"], None if xo is None else self.t_scale[xo:],
+                             None if xo is None else self.t_shift[xo:], NONE if xo is None else SWISH,
+                             bn=None if xo is None else (self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
         return g
 
     def backward(self, dcls_logit: torch.Tensor, dreg: torch.Tensor, dfeats: List[Optional[torch.Tensor]],
@@ -1248,10 +1175,10 @@ class Net:
         A = tape["A"]
         slots: Dict[int, GradSlot] = {}
         self._bw = {"slots": slots, "stem_sums": None}
-        self._wg_pending, self._leaf_pending, self._wg_segment, self._se_wg = [], [], 0, []
+        self._wg_pending, self._wg_segment, self._se_wg = [], 0, []
         self._wg_count = 0
         slot = self._slot
-        fold_heads = FOLD_SUMS and ps.flat.is_cuda and (dfeat_pyr is not None or all(d is None for d in dfeats))
+        fold_heads = ps.flat.is_cuda and (dfeat_pyr is not None or all(d is None for d in dfeats))
         if not fold_heads:
             for f, d in zip(feats, dfeats):
                 if d is not None:
@@ -1306,118 +1233,65 @@ class Net:
                     continue          # node output unused downstream (cannot happen in this topology)
                 name = f"{cell}.{rec['conv']}"
                 W = out.C
-                dz = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.bn", NONE, out.M, W, lazy=True,
-                                  sums=s.sums if s.have_sums else None)
-                in0, in1, up, pl = rec["in0"], rec["in1"], rec["up"], rec["pl"]
+                wkey, dwkey = f"{name}.pointwise_conv.conv.weight", f"{name}.depthwise_conv.conv.weight"
+                L = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.bn", NONE, out.M, W, lazy=True, sums=s.sums if s.have_sums else None)
+                ops = in0, in1, up, pl = rec["in0"], rec["in1"], rec["up"], rec["pl"]
                 mode_ = (1 if in1 is not None else 0) | (2 if up is not None else 0) | (4 if pl is not None else 0)
-                full = (NODE_BWD_FULL and isinstance(dz, LazyDz) and ps.flat.is_cuda and self.NODE_WG and W % 16 == 0 and W <= 224 and mode_ in (2, 5, 4)
-                        and (self.precision == "fp32" or (W <= 160 and NODE_FULL_BF16)) and (pl is None or (POOL_SCATTER and FOLD_SUMS)))
-                dzd = None if full else self._pw_bwd(dz, rec["zd"], f"{name}.pointwise_conv.conv.weight", W, None, True)
-                # the depthwise weight gradient and the depthwise input gradient both come out of the fusion-backward launch below
-                if not self.NODE_WG:
-                    self._dw_bwd(dzd, rec["f"], f"{name}.depthwise_conv.conv.weight", 3, 1, want_dx=False)
+                # whole-node backward (round 4): the node's BatchNorm backward + its 1x1 conv's input gradient (exact fp32 MFMA) + the depthwise /
+                # fusion backward in ONE launch instead of a GEMM launch in front of it - 40 launches off the backward's serial chain.  bf16
+                # modes: up to width 160 (closer to the fp32 reference than the mode's operand-rounding rule asks for, like the whole-node
+                # forward; D2 bf16 13.48 -> 13.25 ms/step); D4 (224) 49.9 -> 52.2: there the bf16 GEMM + two-launch form stays
+                full = W % 16 == 0 and W <= 224 and mode_ in (2, 5, 4) and (self.precision == "fp32" or W <= 160)
+                dzd = None if full else self._pw_bwd(L, rec["zd"], wkey, W, None, True)
                 th = ps.w(f"{cell}.{rec['theta']}")
-                nth = th.numel()
-                # gradients of the same-resolution operands (in0, in1) come straight out of the fuse backward launch; dx is
-                # only materialised for an upsampled / pooled operand
-                same, xsargs, own = [], [], 0
-                for oi, operand in enumerate((in0, in1)):
-                    if operand is None:
-                        same += [None, 0]
-                        xsargs += [None] * 4
+                # One gradient contribution per operand, in the order in0, in1, up, pl; all of them leave the one launch below: the
+                # same-resolution operands directly, the upsampled one as 2x2 block sums, the pooled one scattered - added to each
+                # window's arg-max with atomics, on top of the earlier contributions (or of zeros: a zero-initialised arena buffer when this
+                # is the first one), no dx tensor and no max-pool gather launch over the 4x larger source map.  The launch also takes the
+                # BatchNorm-backward sums of every operand gradient it completes (bnsums); `own` bits: an operand that is max-pooled by
+                # ANOTHER node keeps its sums linearly, this launch adds the sums of its share
+                grad, bnsums, own = [], [], 0
+                for oi, o in enumerate(ops):
+                    if o is None:
+                        grad.append((None, 0))
+                        bnsums.append((None, None, None, None))
                         continue
-                    sl, xs = self._contrib(operand, True)
+                    sl, xs = self._contrib(o, True)
                     accumulate = 0 if sl.t is None else 1
                     if sl.t is None:
-                        sl.t = self._alloc(operand.M, W)
-                    same += [sl.t, accumulate]
-                    xsargs += xsn(xs)
-                    own |= (1 << oi) if (xs is not None and xs[6]) else 0
-                assert in1 is None or same[0].data_ptr() != same[2].data_ptr()
-                # the gradient of an upsampled operand leaves the same launch (2x2 block sums); dx is only materialised for a
-                # pooled operand (its scatter follows the arg-max of overlapping windows)
-                scatter = POOL_SCATTER and FOLD_SUMS and pl is not None and ps.flat.is_cuda
-                dx = self._alloc(out.M, W) if (pl is not None and not scatter) else None
-                upargs = (None, 0)
-                if up is not None:
-                    su, xs = self._contrib(up, True)
-                    upargs = (su.t, 1) if su.t is not None else (self._alloc(up.M, W), 0)
-                    su.t = upargs[0]
-                    xsargs += xsn(xs)
-                    own |= 4 if (xs is not None and xs[6]) else 0
-                else:
-                    xsargs += [None] * 4
+                        sl.t = self._zalloc((o.M, W)) if oi == 3 else self._alloc(o.M, W)
+                    grad.append((sl.t, accumulate))
+                    bnsums.append(xsn(xs))
+                    if oi < 3 and xs is not None and xs[6]:
+                        own |= 1 << oi
+                assert in1 is None or grad[0][0].data_ptr() != grad[1][0].data_ptr()
                 # the fusion-weight gradients of all nodes are finished by ONE launch after the BiFPN (their dot products land in wdot_all)
                 wdot = wdot_all[4 * node_i:4 * node_i + 4]
-                theta_desc.append((ps.entries[f"{cell}.{rec['theta']}"].off, nth))
+                theta_desc.append((ps.entries[f"{cell}.{rec['theta']}"].off, th.numel()))
                 node_i += 1
-                lzb = [o is not None and o.bn is not None for o in (in0, in1, up, pl)]
-                if full:
-                    # whole-node backward: BatchNorm backward of the node + its 1x1 conv's input gradient + depthwise / fusion backward in ONE
-                    # launch; the evaluated dz is stored once for the conv's weight-gradient GEMM (grouped flush)
-                    dplargs = (None, None, None, None, None)
-                    if scatter:
-                        sl, xs = self._contrib(pl, True)
-                        if sl.t is None:
-                            sl.t = self._zalloc((pl.M, W))
-                        dplargs = (sl.t, *xsn(xs))
-                    vp = ctypes.c_void_p
-                    ops_ = (in0, in1, up, pl)
-                    scs = (vp * 4)(*[(o.scale.data_ptr() if l else None) for o, l in zip(ops_, lzb)])
-                    shs = (vp * 4)(*[(o.shift.data_ptr() if l else None) for o, l in zip(ops_, lzb)])
-                    L, bq = dz, ps.bn(dz.bn_name)
-                    wkey = f"{name}.pointwise_conv.conv.weight"
-                    dzm = self._alloc(out.M, W)
-                    call("mmd_bifpn_node_bwd_full", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                         ps.w(f"{name}.depthwise_conv.conv.weight"), wdot, in0.B, in0.H, in0.W, W, *same, *upargs,
-                         ps.g(f"{name}.depthwise_conv.conv.weight"), *xsargs, *dplargs, own, scs if any(lzb) else None, shs if any(lzb) else None,
-                         L.g, L.z, L.aff[0], L.aff[2], L.aff[3], L.sums, L.count, ps.w_t(wkey), dzm, bq["dgamma"], bq["dbeta"])
-                    zdf = rec["zd"]
-                    self._pw_wgrad(dzm, zdf.z, ps.g(wkey), out.M, W, W, None, None, NONE, None, zdf.H * zdf.W)
-                    continue
+                # lazy operands: their values are read as z * scale + shift (finalized coefficients) inside the launch
+                lzb = [o is not None and o.bn is not None for o in ops]
+                scs = shs = None
                 if any(lzb):
-                    # lazy operands: their values are read as z * scale + shift (finalized coefficients) inside the launch
-                    assert scatter or pl is None
-                    dplargs = (None, None, None, None, None)
-                    if scatter:
-                        sl, xs = self._contrib(pl, True)
-                        if sl.t is None:
-                            sl.t = self._zalloc((pl.M, W))
-                        dplargs = (sl.t, *xsn(xs))
                     vp = ctypes.c_void_p
-                    ops_ = (in0, in1, up, pl)
-                    scs = (vp * 4)(*[(o.scale.data_ptr() if l else None) for o, l in zip(ops_, lzb)])
-                    shs = (vp * 4)(*[(o.shift.data_ptr() if l else None) for o, l in zip(ops_, lzb)])
-                    call("mmd_bifpn_node_dw_bwd3_lz", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                         ps.w(f"{name}.depthwise_conv.conv.weight"), dzd, None, wdot, in0.B, in0.H, in0.W, W, *same, *upargs,
-                         ps.g(f"{name}.depthwise_conv.conv.weight") if self.NODE_WG else None, *xsargs, *dplargs, own, scs, shs)
-                    continue
-                if scatter or own:
-                    # scatter: the pooled operand's gradient leaves this launch too - added to each window's arg-max with atomics, on top of the
-                    # earlier contributions (or of zeros: a zero-initialised arena buffer when this is the first one); own: an operand that is
-                    # max-pooled by ANOTHER node keeps its BatchNorm sums linearly, this launch adds the sums of its share
-                    dplargs = (None, None, None, None, None)
-                    if scatter:
-                        sl, xs = self._contrib(pl, True)
-                        if sl.t is None:
-                            sl.t = self._zalloc((pl.M, W))
-                        dplargs = (sl.t, *xsn(xs))
-                    call("mmd_bifpn_node_dw_bwd3", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                         ps.w(f"{name}.depthwise_conv.conv.weight"), dzd, dx, wdot, in0.B, in0.H, in0.W, W, *same, *upargs,
-                         ps.g(f"{name}.depthwise_conv.conv.weight") if self.NODE_WG else None, *xsargs, *dplargs, own)
-                    if scatter or pl is None:
-                        continue
+                    scs = (vp * 4)(*[(o.scale.data_ptr() if l else None) for o, l in zip(ops, lzb)])
+                    shs = (vp * 4)(*[(o.shift.data_ptr() if l else None) for o, l in zip(ops, lzb)])
+                xargs = (*[o.z if o is not None else None for o in ops], th, ps.w(dwkey))
+                gargs = (in0.B, in0.H, in0.W, W, *grad[0], *grad[1], *grad[2], ps.g(dwkey), *bnsums[0], *bnsums[1], *bnsums[2])
+                plargs = (grad[3][0], *bnsums[3], own)
+                if full:
+                    # the evaluated dz is stored once for the conv's weight-gradient GEMM (grouped flush)
+                    bq, zdf = ps.bn(L.bn_name), rec["zd"]
+                    dzm = self._alloc(out.M, W)
+                    call("mmd_bifpn_node_bwd_full", *xargs, wdot, *gargs, *plargs, scs, shs, L.g, L.z, L.aff[0], L.aff[2], L.aff[3], L.sums,
+                         L.count, ps.w_t(wkey), dzm, bq["dgamma"], bq["dbeta"])
+                    self._pw_wgrad(dzm, zdf.z, ps.g(wkey), out.M, W, W, None, None, NONE, None, zdf.H * zdf.W)
+                elif scs is not None:
+                    call("mmd_bifpn_node_dw_bwd3_lz", *xargs, dzd, None, wdot, *gargs, *plargs, scs, shs)
+                elif pl is not None or own:
+                    call("mmd_bifpn_node_dw_bwd3", *xargs, dzd, None, wdot, *gargs, *plargs)
                 else:
-                    call("mmd_bifpn_node_dw_bwd2", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                         ps.w(f"{name}.depthwise_conv.conv.weight"), dzd, dx, wdot, in0.B, in0.H, in0.W, W, *same, *upargs,
-                         ps.g(f"{name}.depthwise_conv.conv.weight") if self.NODE_WG else None, *xsargs)
-                if pl is not None:      # the pooled operand's gradient: gather over the windows whose arg-max it is
-                    wi = 1 + (1 if in1 is not None else 0) + (1 if up is not None else 0)
-                    sl, xs = self._contrib(pl, _lib.LIB.load().mmd_maxpool_bwd_sums_ok(pl.B, pl.H, pl.W, W) == 1)
-                    accumulate = 0 if sl.t is None else 1
-                    if sl.t is None:
-                        sl.t = self._alloc(pl.M, W)
-                    call("mmd_maxpool_same_bwd_acc2", pl.z, dx, sl.t, th, nth, wi, accumulate, pl.B, pl.H, pl.W, W, *xsn(xs))
+                    call("mmd_bifpn_node_dw_bwd2", *xargs, dzd, None, wdot, *gargs)
             if c == 0:
                 first = tape[cell + ".first"]
                 c6, p6_in, p7_in = first["c6"], first["p6_in"], first["p7_in"]
@@ -1488,40 +1362,32 @@ class Net:
             # the project conv's input-gradient GEMM, which produces g1
             a1 = rec["bn1"]
             pool5 = self._zalloc((5, f1.B, blk.cmid))
-            p5 = (f1.z, a1[0], a1[1], a1[2], a1[3], pool5, f1.B) if (P5_IN_GEMM and isinstance(dz2, LazyDz) and ps.flat.is_cuda) else None
-            g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec["gate"], pool5=p5)
+            g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec["gate"],
+                              pool5=(f1.z, a1[0], a1[1], a1[2], a1[3], pool5, f1.B))
             # the skip branch may ADOPT dy as the gradient slot of the block input, and the block's own input gradient is later
             # accumulated into that buffer in place; with a lazy BatchNorm backward the project conv's weight-gradient GEMM (side
             # stream) still reads dy, so that later accumulation waits for it (the event is long past by then)
-            dy_read = self._wg_read_done if (blk.skip and isinstance(dz2, LazyDz)) else None
+            dy_read = self._wg_read_done if blk.skip else None
             if blk.skip:
                 self._acc(inp, dy)
-            if p5 is None:
-                call("mmd_chan_pool_bwd", f1.z, a1[0], a1[1], a1[2], a1[3], g1, pool5, f1.B, HW1, blk.cmid)
             dpe = self._alloc(f1.B, blk.cmid)
             dpr = self._alloc(f1.B, blk.se)
             dpooled = self._alloc(f1.B, blk.cmid)
             sums1 = self._zalloc((2 * blk.cmid,), torch.float64)
             segrads = (ps.g(f"{q}._se_reduce.conv.weight"), ps.g(f"{q}._se_reduce.conv.bias"), ps.g(f"{q}._se_expand.conv.weight"),
                        ps.g(f"{q}._se_expand.conv.bias"))
-            if SE_FUSED and ps.flat.is_cuda:
-                # both FC layers' data gradients in one launch
-                call("mmd_se_fc_bwd_fused", pool5[0], rec["gate"], rec["hpre"], ps.w(f"{q}._se_reduce.conv.weight"),
-                     ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dpooled, 1.0 / HW1, f1.B, blk.cmid, blk.se, pool5, sums1)
-            else:
-                dh = self._zalloc((f1.B, blk.se))
-                call("mmd_se_fc_bwd", pool5[0], rec["gate"], rec["hpre"], rec["pooled"], ps.w(f"{q}._se_reduce.conv.weight"),
-                     ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dh, dpooled, 1.0 / HW1, None, None, None, None,
-                     f1.B, blk.cmid, blk.se, pool5, sums1)
-            if SE_WG_BATCH and ps.flat.is_cuda:      # the FC weight gradients of all blocks of the segment in one launch at its end
-                self._se_wg.append((dpe, dpr, rec["hpre"], rec["pooled"], *segrads, blk.cmid, blk.se))
-            else:
-                self._leaf(lambda dpe=dpe, dpr=dpr, hp=rec["hpre"], po=rec["pooled"], gs=segrads, nb=f1.B, cm=blk.cmid, se=blk.se:
-                           call("mmd_se_fc_wgrad", dpe, dpr, hp, po, *gs, nb, cm, se))
+            # two wide launches for the two FC data gradients (both in one, mmd_se_fc_bwd_fused, is correct, but every block recomputes its
+            # image's hidden gradient - S*C MACs, serial per wave: measured 17.0 -> 17.7 ms/step)
+            dh = self._zalloc((f1.B, blk.se))
+            call("mmd_se_fc_bwd", pool5[0], rec["gate"], rec["hpre"], rec["pooled"], ps.w(f"{q}._se_reduce.conv.weight"),
+                 ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dh, dpooled, 1.0 / HW1, None, None, None, None,
+                 f1.B, blk.cmid, blk.se, pool5, sums1)
+            # the FC weight gradients of all blocks of the segment in one launch at its end
+            self._se_wg.append((dpe, dpr, rec["hpre"], rec["pooled"], *segrads, blk.cmid, blk.se))
             f0: Feat = rec.get("f0", inp)
             # BatchNorm-1 backward evaluated in the prologue of the depthwise input-gradient launch (stride-1 blocks with an expand conv and
             # >= 64 channels: 17 of D2's 23): dz1 is never written; the other blocks keep the apply pass
-            bn1_in_dw = (BN1_IN_DW and ps.flat.is_cuda and blk.expand != 1 and blk.stride == 1 and blk.cmid >= 64 and self.DW_WG)
+            bn1_in_dw = blk.expand != 1 and blk.stride == 1 and blk.cmid >= 64
             if not bn1_in_dw:
                 dz1 = self._bn_bwd(g1, f1.z, a1, f"{q}._bn1", SWISH, M1, blk.cmid, rpi=HW1, mul_bc=rec["gate"],
                                    add_bc=dpooled, sums=sums1)
@@ -1576,14 +1442,14 @@ class Net:
         s = self._slot(stem)
         Bi, Cin, Hi, Wi = ximg.shape
         dll = _lib.LIB.load() if ps.flat.is_cuda else None
+        # stem weight gradient straight from the NCHW image (mmd_stem_conv_bwd_weight_bn) where the kernel covers the geometry, else im2col + a
+        # GEMM item of the last grouped flush
         # (every precision mode: the bf16 rule rounds the operands of the 1x1 convs only - the stem is a 3x3 conv and stays fp32)
-        direct = bool(STEM_WG_DIRECT and dll is not None
-                      and dll.mmd_stem_conv_bwd_weight_supported(Cin, Hi, Wi, ps.stem_kp, stem.C) == 1)
+        direct = dll is not None and dll.mmd_stem_conv_bwd_weight_supported(Cin, Hi, Wi, ps.stem_kp, stem.C) == 1
         if direct:
-            # the last grouped flush (the thin 256^2 layers of blocks 0 - 2) starts NOW, beside the stem's BatchNorm backward, and the stem's
-            # own weight gradient runs beside it on the second side stream: the step's exposed tail is the longer of the two, not their sum
+            # the last grouped flush (the thin 256^2 layers of blocks 0 - 2) starts NOW, beside the stem's BatchNorm backward and the stem's
+            # own weight gradient: the step's exposed tail is the longer of the two, not their sum
             self._wg_flush()
-        if direct:
             # no im2col matrix (168 MB at 512^2 x 8 channels): the patches are gathered from the image rows while the dz tile is multiplied -
             # and no dz tensor either: the stem BatchNorm's backward is evaluated while that tile is staged (mmd_stem_conv_bwd_weight_bn)
             if stem_sums is None:
@@ -1592,20 +1458,11 @@ class Net:
                      *self._stats_ws(stem_sums, stem.M, stem.C))
             b0 = ps.bn(f"{P}._bn0")
             ws = self._alloc(int(dll.mmd_stem_wgrad_ws_floats(stem.C)))
-            if STEM_WG_SIDE:
-                main_stream = torch.cuda.current_stream()
-                if self._side is None:
-                    self._side = torch.cuda.Stream()
-                self._side.wait_event(main_stream.record_event())
-                with torch.cuda.stream(self._side):
-                    call("mmd_stem_conv_bwd_weight_bn", ximg, s.t, stem.z, ps.g(f"{P}._conv_stem.conv.weight"), ws, Bi, Cin, Hi, Wi, ps.stem_kp, stem.C,
-                         stem.scale, stem.shift, mu, istd, stem_sums, stem.M, SWISH, b0["dgamma"], b0["dbeta"])
-                main_stream.wait_stream(self._side)
-            else:
-                # on the MAIN stream, whose chain ends here: in the captured graph the side-stream branch came out serialised BEHIND the grouped
-                # flush (rocprofv3 trace: flush 278 us -> fold 46 -> stem 78 -> fold 12, all exposed), the main branch runs beside it
-                call("mmd_stem_conv_bwd_weight_bn", ximg, s.t, stem.z, ps.g(f"{P}._conv_stem.conv.weight"), ws, Bi, Cin, Hi, Wi, ps.stem_kp, stem.C,
-                     stem.scale, stem.shift, mu, istd, stem_sums, stem.M, SWISH, b0["dgamma"], b0["dbeta"])
+            # on the MAIN stream, whose chain ends here: on the second side stream (the earlier placement) the branch came out serialised BEHIND
+            # the grouped flush in the captured graph (rocprofv3 trace: flush 278 us -> fold 46 -> stem 78 -> fold 12, all exposed), the
+            # main branch runs beside it
+            call("mmd_stem_conv_bwd_weight_bn", ximg, s.t, stem.z, ps.g(f"{P}._conv_stem.conv.weight"), ws, Bi, Cin, Hi, Wi, ps.stem_kp, stem.C,
+                 stem.scale, stem.shift, mu, istd, stem_sums, stem.M, SWISH, b0["dgamma"], b0["dbeta"])
         else:
             dz = self._bn_bwd(s.t, stem.z, (stem.scale, stem.shift, mu, istd), f"{P}._bn0", SWISH, stem.M, stem.C, sums=stem_sums)
             with self._wgrad_stream():          # im2col of the input image + weight-gradient GEMM, both off the critical path

@@ -352,7 +352,7 @@ class DistillEngine:
         # launches on the skinny kernel, engine.Net._head - so D4 / 768^2 at B = 8, 288 rows per net on its 6 x 6 level, packs too)
         # (the 32-row relaxation holds only where EVERY per-net launch on that level is covered - the heads split it off themselves,
         # the BiFPN nodes only on the whole-node kernel, which has no row-tile constraint; a width without one (88 / 288 / 384: D1, D5 - D7), the
-        # wide form past its row cap or MMD_NO_NODE_FUSE send that level's nodes through mmd_pwconv_fwd, whose 64- / 128-row kernels refuse
+        # wide form past its row cap or a net with the `FUSE_NODE` test hook off send that level's nodes through mmd_pwconv_fwd, whose 64- / 128-row kernels refuse
         # a tile that straddles two nets: those geometries keep the whole-128-row-tile rule, i.e. run one net per stream as before)
         rows_small = B * (S // 128) ** 2
         net_f = next(iter(self.teachers.values()))

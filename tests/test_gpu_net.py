@@ -322,7 +322,7 @@ def test_d4_train_fwd_bwd_vs_oracle():
     print("d4 train gradient check: per-tensor max relative error p90 %.4f p95 %.4f max %.4f" % (
         errs[int(0.90 * len(errs))], errs[int(0.95 * len(errs))], errs[-1]))
     # fp32 atomics + max-pool ties make this statistic bimodal from run to run: p95 = 0.003 / 0.009 / 0.021 in three runs of the
-    # SAME build (and 0.003 / 0.008 / 0.021 with MMD_NO_LAZY_BN=1, the separate BatchNorm apply pass) - a flipped tie reroutes a
+    # SAME build (and 0.003 / 0.008 / 0.021 with the separate BatchNorm apply pass the engine ran before) - a flipped tie reroutes a
     # gradient through the tiny 2x2 / 4x4 levels of this 256x256 test; the direction / norm checks above are the tight ones
     assert errs[int(0.95 * len(errs))] < 3e-2, errs[-10:]
 
@@ -582,7 +582,7 @@ def _pack_case(coef, B, S, fuse_node=True, raw_logits=False):
 @pytest.mark.parametrize("coef,fuse_node", [(1, True), (2, False), (4, True)])
 def test_teacher_pack_unfused_nodes(coef, fuse_node):
     """a pack forward whose BiFPN nodes take the two-launch path - an fpn width without a whole-node kernel (D1: 88) or
-    MMD_NO_NODE_FUSE - must read every net's own fusion weights and depthwise taps (mmd_bifpn_node_dw_fwd honours the group descriptor
+    the `FUSE_NODE` test hook off - must read every net's own fusion weights and depthwise taps (mmd_bifpn_node_dw_fwd honours the group descriptor
     now), not net 0's: each net's slice of the packed result equals that net evaluated alone."""
     # (4: BASELINE configs[4]'s geometry, D4 at 768^2 - the 6 x 6 level holds 288 rows per net, not whole 128-row tiles: the heads run that
     # level as plain launches on the 32-row skinny kernel, round 5; its large BiFPN levels take the two-launch node path)

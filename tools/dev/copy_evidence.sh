@@ -1,5 +1,5 @@
 #!/bin/bash
-# copy the summaries of tools/dev/r06_final.sh (gpurun_out/) into profiles/ under the round's names: copy_evidence.sh [prefix, default r06]
+# copy the summaries that tools/dev/final_evidence.sh wrote (its output folder, see $f below) into profiles/ under the round's names: copy_evidence.sh [prefix, default r06]
 p=${1:-r06}; f=gpurun_out/final
 cp $f/bench.json profiles/${p}_bench.json
 cp $f/kernel_stats.csv profiles/${p}_bench_kernel_stats.csv
