@@ -505,6 +505,24 @@ int mmd_image_letterbox(const void* src, int dtype, int H, int W, int C, float s
 // Resizer's audio branch: cv2.resize(INTER_CUBIC) of an [h,w,C] spectrogram stack to [C,S,S] (transformations.py:435-441).
 int mmd_resize_cubic(const float* src, int h, int w, int C, int common_size, float* dst, hipStream_t stream);
 
+// ---- waveform front end (csrc/melspec.hip).  MultimodalDetection.merge_audios (src/datasets/MultimodalDetection.py:329-353, called per
+// sample from yield_batch, :355-367) and Audio2Spectogram (src/datasets/transformations.py:251-266):
+// librosa.feature.melspectrogram(sr=44100, n_fft=1024, hop_length=256, n_mels=80) of each microphone channel.  librosa's arithmetic
+// is restated (it is not in the reference tree): parity with librosa itself is unpinned, the kernel is pinned to tests/melspec_ref.py.
+// Frames of a center=True STFT over n_samples samples: 1 + n_samples / 256, or -22 for n_samples <= 512 (the reflect padding of 512
+// samples needs more than 512).  No GPU work.
+int mmd_melspec_frames(long long n_samples);
+
+// The melspectrogram call of merge_audios (src/datasets/MultimodalDetection.py:329-353) and Audio2Spectogram
+// (src/datasets/transformations.py:251-266) for all channels of one recording in ONE launch.
+// out[80, T, channels] (mel, frame, channel - the order np.transpose(np.stack(...), (1, 2, 0)) gives upstream and mmd_resize_cubic
+// reads), T = mmd_melspec_frames(n_samples): POWER mel spectrogram (no power_to_db, like merge_audios) of wav_a[channels, n_samples],
+// or of (wav_a + wav_b) / 2 in fp32 when wav_b is not null (merge_audios, :339).  Reflect padding, periodic Hann window, 1024-point
+// real FFT at hop 256, Slaney mel bank handed over in band form: row m = band_w[m * band_stride + j] on bins band_start[m] + j,
+// j < band_len[m] <= band_stride (80 * band_stride <= 4096; mm_distillnet_amd.audio.mel_bands).  One launch, raw device pointers,
+// no allocation; out needs no zeroing and two calls on the same input give the same bits.  -22 on null pointers / bad sizes before any launch.
+int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long long n_samples, const int* band_start, const int* band_len, const float* band_w, int band_stride, float* out, hipStream_t stream);
+
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction
 // (src/optimization/train_methods.py:944-961): student gradients only, sum (the 1/N average rides in the optimizer pass), plus the

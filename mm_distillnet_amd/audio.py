@@ -1,0 +1,95 @@
+"""Waveform front end of the student's audio input: power mel spectrograms (and the mix of two recordings) on the GPU.
+
+`MultimodalDetection.merge_audios` (src/datasets/MultimodalDetection.py:329-353, called per sample from `yield_batch`, :355-367) averages
+two recordings' eight microphone waveforms and runs `librosa.feature.melspectrogram(sr=44100, n_fft=1024, hop_length=256, n_mels=80)` on
+each channel, then resizes with cv2.INTER_CUBIC; `Audio2Spectogram` (src/datasets/transformations.py:251-266) is the same transform for
+one recording.  Here the host only builds the Slaney filter bank; the spectrogram is csrc/melspec.hip (`mmd_melspec_power`), the resize
+`mmd_resize_cubic`.  librosa's and cv2's arithmetic is restated, parity with the libraries themselves is unpinned."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+N_FFT, HOP = 1024, 256
+
+
+def _hz_to_mel(f):
+    # Slaney scale (htk=False): linear 200/3 Hz per mel below 1 kHz, logarithmic above with 27 mels per factor 6.4
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) / (np.log(6.4) / 27.0), f / (200.0 / 3.0))
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filters(sr: int = 44100, n_fft: int = N_FFT, n_mels: int = 80) -> np.ndarray:
+    """Dense float32 [n_mels, 1 + n_fft/2] Slaney bank (fmin = 0, fmax = sr/2): row m is the triangle that rises from 0 at edge[m] to 1
+    at edge[m + 1] and falls to 0 at edge[m + 2], scaled to unit area (height 2 / (edge[m + 2] - edge[m])), sampled at the FFT bin
+    frequencies.  Computed in float64 and rounded once."""
+    edge = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+    left, peak, right = edge[:-2, None], edge[1:-1, None], edge[2:, None]
+    hz = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)[None, :]
+    rising, falling = (hz - left) / (peak - left), (right - hz) / (right - peak)
+    tri = np.clip(np.minimum(rising, falling), 0.0, None)
+    return (tri * (2.0 / (right - left))).astype(np.float32)
+
+
+def mel_bands(sr: int = 44100, n_fft: int = N_FFT, n_mels: int = 80):
+    """The bank in band form, as `mmd_melspec_power` takes it: (start int32 [n_mels], length int32 [n_mels], weights float32
+    [n_mels, Lmax]) - every row of the bank is one contiguous run of bins (997 non-zero weights, at most 50 per row, at the defaults)."""
+    w = mel_filters(sr, n_fft, n_mels)
+    start, length = np.zeros(n_mels, np.int32), np.zeros(n_mels, np.int32)
+    for m in range(n_mels):
+        nz = np.flatnonzero(w[m])
+        if nz.size:
+            if nz[-1] - nz[0] + 1 != nz.size:
+                raise ValueError(f"mel row {m} is not one contiguous run of bins")
+            start[m], length[m] = nz[0], nz.size
+    band = np.zeros((n_mels, max(1, int(length.max()))), np.float32)
+    for m in range(n_mels):
+        band[m, :length[m]] = w[m, start[m]:start[m] + length[m]]
+    return start, length, band
+
+
+class MelFrontEnd:
+    """Holds the band-form filter bank on `device`; every call runs on the current stream and allocates only its result."""
+
+    def __init__(self, device):
+        from . import _lib
+        self.call = _lib.call
+        self.frames = _lib.LIB.load().mmd_melspec_frames
+        self.device = torch.device(device)
+        start, length, band = mel_bands()
+        self.n_mels, self.stride = band.shape
+        self.start = torch.from_numpy(start).to(self.device)
+        self.length = torch.from_numpy(length).to(self.device)
+        self.band = torch.from_numpy(band).to(self.device)
+
+    def n_frames(self, n_samples: int) -> int:
+        T = self.frames(int(n_samples))
+        if T < 0:
+            raise ValueError(f"a waveform of {n_samples} samples is too short for the reflect padding (more than {N_FFT // 2} needed)")
+        return T
+
+    def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None) -> torch.Tensor:
+        """[B, C, N] float32 device waveforms (the mean of the two when wav_b is given) -> power mel spectrograms [B, 80, T, C]."""
+        if wav_a.dim() != 3 or wav_a.dtype != torch.float32 or (wav_b is not None and (wav_b.shape != wav_a.shape or wav_b.dtype != wav_a.dtype)):
+            raise ValueError("melspec takes float32 [B, C, N] waveforms (two of one shape to mix them)")
+        B, C, N = wav_a.shape
+        out = torch.empty(B, self.n_mels, self.n_frames(N), C, device=self.device)
+        for b in range(B):
+            self.call("mmd_melspec_power", wav_a[b], None if wav_b is None else wav_b[b], C, N, self.start, self.length, self.band,
+                      self.stride, out[b])
+        return out
+
+    def student_input(self, wav_a: torch.Tensor, wav_b, S: int) -> torch.Tensor:
+        """-> [B, C, S, S]: the mel stacks resized with cv2.INTER_CUBIC's rule (`mmd_resize_cubic`).  S is the step's image_size;
+        upstream's merge_audios hard-codes common_size = 768 (:330), the image_size of its shipped cfg."""
+        mel = self.melspec(wav_a, wav_b)
+        B, M, T, C = mel.shape
+        out = torch.empty(B, C, S, S, device=self.device)
+        for b in range(B):
+            self.call("mmd_resize_cubic", mel[b], M, T, C, S, out[b])
+        return out

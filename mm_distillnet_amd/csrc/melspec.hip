@@ -1,0 +1,228 @@
+// Waveform front end: power mel spectrograms of (optionally mixed) microphone waveforms in one launch.
+//
+//   MultimodalDetection.merge_audios (src/datasets/MultimodalDetection.py:329-353, per sample from yield_batch, :355-367) and
+//   Audio2Spectogram (src/datasets/transformations.py:251-266): average two recordings' eight waveforms and run
+//   librosa.feature.melspectrogram(sr=44100, n_fft=1024, hop_length=256, n_mels=80) on each channel.
+//
+// librosa (0.7.2 in requirements.txt) is a third-party dependency that is neither part of the reference tree nor installed with this
+// project: the arithmetic below restates its published definition - y = (a + b) / 2 in fp32, reflect padding of n_fft / 2 samples
+// (edge sample not repeated), frames of 1024 at hop 256 times the periodic Hann window, |rfft|^2, Slaney mel bank - and is pinned to
+// tests/melspec_ref.py.  Parity with librosa itself is UNPINNED.  No power_to_db: merge_audios returns power.
+//
+// Shape: a block owns ONE channel and MEL_FPB = 8 consecutive frames.  Frames overlap by 75 %, so the block stages the (8 + 3) * 256
+// samples they cover in LDS once (mix and reflect index at that load; the index is clamped, never guarded: frames past the end compute
+// on clamped samples and only their stores are masked).  Each of the 4 waves then transforms TWO real frames as one 1024-point complex
+// FFT z = x0 + i x1 with 16 points per lane: radix-16, radix-16, radix-4 butterflies in registers, two exchanges through a wave-private
+// LDS buffer whose rows of 16 complex values are padded to 17 (the 16- and 256-strided accesses of the exchanges otherwise land on one
+// bank).  X0[k] = (Z[k] + conj Z[N-k]) / 2, X1[k] = (Z[k] - conj Z[N-k]) / 2i give the two power rows, which replace Z in LDS, and the
+// mel projection reads them through the band form of the filter bank (each mel row is one contiguous run of at most ~50 bins; a dense
+// 80 x 513 product would cost more than the FFT).  Twiddles and window are tables rounded once from double (melspec_tables.h).
+// Plain stores, no atomics, fixed summation order: the output needs no zeroing and two launches give the same bits.
+#include "common.h"
+#include "melspec_tables.h"
+
+#define MEL_NFFT 1024
+#define MEL_HOP 256
+#define MEL_NMEL 80
+#define MEL_BINS 513
+#define MEL_FPB 8                                   // frames per block: 4 waves x 2 frames
+#define MEL_STAGE ((MEL_FPB + 3) * MEL_HOP)         // samples the block's frames cover
+#define MEL_ZROW 1088                               // 1024 complex values in rows of 16 padded to 17
+#define MEL_PROW 520                                // second power row's offset inside the (reused) exchange buffer
+#define MEL_WMAX 4096                               // band weights kept in LDS: 80 * band_stride floats at most (stride <= 51)
+
+__device__ __forceinline__ float2 mel_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
+__device__ __forceinline__ float2 mel_tw(int m) { return reinterpret_cast<const float2*>(mmd_mel_twiddle)[m]; }
+
+// forward 4-point DFT (e^{-2 pi i nk/4}), in place
+__device__ __forceinline__ void mel_dft4(float2& a0, float2& a1, float2& a2, float2& a3) {
+  const float2 s0 = make_float2(a0.x + a2.x, a0.y + a2.y), s1 = make_float2(a0.x - a2.x, a0.y - a2.y);
+  const float2 s2 = make_float2(a1.x + a3.x, a1.y + a3.y), s3 = make_float2(a1.x - a3.x, a1.y - a3.y);
+  a0 = make_float2(s0.x + s2.x, s0.y + s2.y);
+  a1 = make_float2(s1.x + s3.y, s1.y - s3.x);        // s1 - i s3
+  a2 = make_float2(s0.x - s2.x, s0.y - s2.y);
+  a3 = make_float2(s1.x - s3.y, s1.y + s3.x);        // s1 + i s3
+}
+// e^{-2 pi i m/16} for the products b*c of the 4 x 4 split (m in {0,1,2,3,4,6,9}); constants after unrolling
+__device__ __forceinline__ float2 mel_w16(int m) {
+  const float c1 = 0.92387953251128674f, s1 = 0.38268343236508977f, h = 0.70710678118654752f;
+  switch (m) {
+    case 1: return make_float2(c1, -s1);
+    case 2: return make_float2(h, -h);
+    case 3: return make_float2(s1, -c1);
+    case 4: return make_float2(0.f, -1.f);
+    case 6: return make_float2(-h, -h);
+    case 9: return make_float2(-c1, s1);
+    default: return make_float2(1.f, 0.f);
+  }
+}
+// forward 16-point DFT in registers: n = 4a + b, k = c + 4d: DFT4 over a, times W16^{bc}, DFT4 over b
+__device__ __forceinline__ void mel_dft16(float2 v[16]) {
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    mel_dft4(v[b], v[4 + b], v[8 + b], v[12 + b]);           // v[4c + b] = y[b][c]
+#pragma unroll
+    for (int c = 1; c < 4; ++c)
+      if (b) v[4 * c + b] = mel_cmul(v[4 * c + b], mel_w16(b * c));
+  }
+  float2 o[16];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    mel_dft4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);       // v[4c + d] = X[c + 4d]
+#pragma unroll
+    for (int d = 0; d < 4; ++d) o[c + 4 * d] = v[4 * c + d];
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) v[i] = o[i];
+}
+__device__ __forceinline__ int mel_pad(int i) { return i + (i >> 4); }
+
+template <bool MIX>
+__global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restrict__ wav_a, const float* __restrict__ wav_b, long long N,
+                                                            int T, int C, const int* __restrict__ band_start,
+                                                            const int* __restrict__ band_len, const float* __restrict__ band_w,
+                                                            int band_stride, float* __restrict__ out) {
+  __shared__ float s_x[MEL_STAGE];
+  __shared__ float2 s_z[4][MEL_ZROW];
+  __shared__ float s_w[MEL_WMAX];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = blockIdx.y, f0 = blockIdx.x * MEL_FPB;
+  const float* pa = wav_a + (size_t)c * N;
+  const float* pb = MIX ? wav_b + (size_t)c * N : nullptr;
+
+  // ---- stage the block's samples: padded position p <-> sample p - 512, reflected at both ends, then clamped (frames >= T only)
+  const long long base = (long long)f0 * MEL_HOP - MEL_NFFT / 2;
+#pragma unroll
+  for (int it = 0; it < MEL_STAGE / 256; ++it) {
+    const int i = tid + 256 * it;
+    long long s = base + i;
+    s = s < 0 ? -s : s;
+    s = s >= N ? 2 * (N - 1) - s : s;
+    s = s < 0 ? 0 : (s > N - 1 ? N - 1 : s);
+    float v = pa[s];
+    if (MIX) v = (v + pb[s]) * 0.5f;
+    s_x[i] = v;
+  }
+  for (int i = tid; i < MEL_NMEL * band_stride; i += 256) s_w[i] = band_w[i];
+  __syncthreads();
+
+  // The exchange buffer s_z[wave] is WAVE-PRIVATE: from here on no wave reads what another wrote.  The __syncthreads below only order
+  // one wave's own LDS writes before its reads (and reads before the overwriting writes); they are block-wide for simplicity - all four
+  // waves run the same straight-line code - not because the buffer is shared.
+  // ---- pass 1: radix-16 over n = lane + 64 r (no twiddles), out[16 lane + r]
+  float2* zb = s_z[wave];
+  const float* x0 = s_x + wave * 2 * MEL_HOP;
+  const float* x1 = x0 + MEL_HOP;
+  float2 v[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int n = lane + 64 * r;
+    const float w = mmd_mel_hann[n];
+    v[r] = make_float2(w * x0[n], w * x1[n]);
+  }
+  mel_dft16(v);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) zb[lane * 17 + r] = v[r];
+  __syncthreads();
+
+  // ---- pass 2: radix-16 over in[lane + 64 r] with twiddle W256^{r k}, k = lane % 16; out[256 (lane / 16) + k + 16 r]
+  const int k16 = lane & 15;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    v[r] = zb[mel_pad(lane + 64 * r)];
+    if (r) v[r] = mel_cmul(v[r], mel_tw((4 * r * k16) & (MEL_NFFT - 1)));
+  }
+  __syncthreads();
+  mel_dft16(v);
+#pragma unroll
+  for (int r = 0; r < 16; ++r) zb[(lane >> 4) * 272 + k16 + 17 * r] = v[r];
+  __syncthreads();
+
+  // ---- pass 3: four radix-4 butterflies per lane over in[j + 256 r], j = lane + 64 q, twiddle W1024^{r j}; Z[j + 256 r] in place
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = lane + 64 * q;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      v[4 * q + r] = zb[mel_pad(j + 256 * r)];
+      if (r) v[4 * q + r] = mel_cmul(v[4 * q + r], mel_tw(r * j));
+    }
+    mel_dft4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) zb[lane + 64 * q + 256 * r] = v[4 * q + r];         // natural order, unpadded
+  __syncthreads();
+
+  // ---- split the two real spectra, power of bins 0..512 (bin index clamped, store masked)
+  float p0[9], p1[9];
+#pragma unroll
+  for (int m = 0; m < 9; ++m) {
+    const int k = min(lane + 64 * m, MEL_BINS - 1);
+    const float2 zk = zb[k], zn = zb[(MEL_NFFT - k) & (MEL_NFFT - 1)];
+    const float ar = zk.x + zn.x, ai = zk.y - zn.y;          // 2 X0[k]
+    const float br = zk.y + zn.y, bi = zk.x - zn.x;          // 2 X1[k] (up to the factor -i)
+    p0[m] = 0.25f * (ar * ar + ai * ai);
+    p1[m] = 0.25f * (br * br + bi * bi);
+  }
+  __syncthreads();
+  float* pw = reinterpret_cast<float*>(zb);
+#pragma unroll
+  for (int m = 0; m < 9; ++m) {
+    const int k = lane + 64 * m;
+    if (k < MEL_BINS) { pw[k] = p0[m]; pw[MEL_PROW + k] = p1[m]; }
+  }
+  __syncthreads();
+
+  // (The unoptimised part of the kernel, small against the FFT: per-lane trip counts of 2..50 diverge, 64 then 32 of 64 lanes work, and
+  // lanes store T * C floats apart.  Follow-up together with batching the samples of a batch into one launch.)
+  // ---- mel projection from the band form: mel rows 0..63 one per lane (both frames share the weight), rows 64..79 on lanes 0..31
+  const int t0 = f0 + wave * 2;
+  {
+    const int mel = lane;
+    const int st = min(max(band_start[mel], 0), MEL_BINS - 1);
+    const int ln = min(max(band_len[mel], 0), min(MEL_BINS - st, band_stride));
+    const float* w = s_w + mel * band_stride;
+    float a0 = 0.f, a1 = 0.f;
+    for (int j = 0; j < ln; ++j) {
+      a0 = fmaf(w[j], pw[st + j], a0);
+      a1 = fmaf(w[j], pw[MEL_PROW + st + j], a1);
+    }
+    if (t0 < T) out[((size_t)mel * T + t0) * C + c] = a0;
+    if (t0 + 1 < T) out[((size_t)mel * T + t0 + 1) * C + c] = a1;
+  }
+  {
+    const int mel = 64 + (lane & 15), fr = (lane >> 4) & 1;
+    const int st = min(max(band_start[mel], 0), MEL_BINS - 1);
+    const int ln = lane < 32 ? min(max(band_len[mel], 0), min(MEL_BINS - st, band_stride)) : 0;
+    const float* w = s_w + mel * band_stride;
+    const float* p = pw + fr * MEL_PROW + st;
+    float acc = 0.f;
+    for (int j = 0; j < ln; ++j) acc = fmaf(w[j], p[j], acc);
+    if (lane < 32 && t0 + fr < T) out[((size_t)mel * T + t0 + fr) * C + c] = acc;
+  }
+}
+
+// 1 + n_samples / 256 frames (center=True), or MMD_EINVAL: reflect padding of 512 needs more than 512 samples
+extern "C" int mmd_melspec_frames(long long n_samples) {
+  if (n_samples <= MEL_NFFT / 2 || n_samples / MEL_HOP >= 0x7fffffffLL) return MMD_EINVAL;
+  return (int)(1 + n_samples / MEL_HOP);
+}
+
+extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long long n_samples, const int* band_start,
+                                 const int* band_len, const float* band_w, int band_stride, float* out, hipStream_t stream) {
+  if (!wav_a || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535) return MMD_EINVAL;
+  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX) return MMD_EINVAL;
+  const int T = mmd_melspec_frames(n_samples);
+  if (T < 0) return MMD_EINVAL;
+  const dim3 grid(cdiv(T, MEL_FPB), channels), block(256);
+  if (wav_b)
+    hipLaunchKernelGGL(melspec_power_kernel<true>, grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, band_len,
+                       band_w, band_stride, out);
+  else
+    hipLaunchKernelGGL(melspec_power_kernel<false>, grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, band_len,
+                       band_w, band_stride, out);
+  return mmd_check_launch();
+}

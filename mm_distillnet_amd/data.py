@@ -31,6 +31,7 @@ class SyntheticMultimodalDetection(Dataset):
         self.classes = CLASSES
         vl = config.get('valid_labels', None)
         self.valid_classes_dict = valid_classes_dict(tuple(vl.split(',')) if vl else None)
+        self.wave_samples = int(config.get('synthetic_wave_samples', 44100))      # extension key: samples per microphone waveform (1 s)
 
     def __len__(self):
         return self.length
@@ -47,6 +48,42 @@ class SyntheticMultimodalDetection(Dataset):
 
     def yield_batch(self, batch_size, ids):
         return _yield_batch(self, batch_size, ids)
+
+    def waveforms(self, i):
+        """The eight microphone waveforms of recording i, float32 [8, N] at 44.1 kHz (what `librosa.load(path, sr=44100)` hands
+        `merge_audios`, MultimodalDetection.py:335-336): deterministic in (seed, i), independent of __getitem__'s draws."""
+        return synthetic_waveforms(self.seed, int(i), self.wave_samples)
+
+    def yield_batch_waves(self, batch_size, ids):
+        """`yield_batch` for the waveform front end (cfg audio_mix = waveform): the partner recordings are drawn exactly as `_yield_batch`
+        draws them (numpy's global RNG), but the two recordings' WAVEFORMS are returned and the mix, mel spectrogram and resize of
+        `merge_audios` happen on the device (mm_distillnet_amd.audio.MelFrontEnd.student_input).
+        -> (rgb [B,3,S,S], wav_a [B,8,N] of `ids`, wav_b [B,8,N] of the partners)"""
+        import numpy as np
+        mine = set(int(i) for i in ids)
+        pool = [i for i in range(len(self)) if i not in mine]
+        picks = np.random.choice(pool, size=batch_size)
+        rgbs = [self[int(picks[k])][0] for k in range(batch_size)]
+        wav_a = [self.waveforms(int(ids[k])) for k in range(batch_size)]
+        wav_b = [self.waveforms(int(picks[k])) for k in range(batch_size)]
+        return torch.stack(rgbs), torch.stack(wav_a), torch.stack(wav_b)
+
+
+def synthetic_waveforms(seed: int, i: int, n: int, channels: int = 8, sr: int = 44100) -> torch.Tensor:
+    """Stand-in recording: per channel three steady tones (100 Hz - 8 kHz), one linear chirp and a broadband noise floor (sigma 0.1),
+    so every mel band of every frame carries energy.  float32 [channels, n]."""
+    import math
+    g = torch.Generator().manual_seed((seed * 1000003 + i) * 31 + 17)
+    p = torch.rand(channels, 12, generator=g, dtype=torch.float64)
+    t = (torch.arange(n, dtype=torch.float64) / sr)[None, :]
+    y = torch.zeros(channels, n, dtype=torch.float64)
+    for k in range(3):
+        f = 100.0 * torch.pow(torch.tensor(80.0, dtype=torch.float64), p[:, k:k + 1])
+        y += (0.1 + 0.2 * p[:, 3 + k:4 + k]) * torch.sin(2.0 * math.pi * (f * t + p[:, 6 + k:7 + k]))
+    f0, f1 = 200.0 + 2000.0 * p[:, 9:10], 4000.0 + 12000.0 * p[:, 10:11]
+    y += 0.2 * torch.sin(2.0 * math.pi * (f0 * t + 0.5 * (f1 - f0) * t * t / (n / sr) + p[:, 11:12]))
+    y += 0.1 * torch.randn(channels, n, generator=g, dtype=torch.float64)
+    return y.to(torch.float32)
 
 
 def _yield_batch(ds, batch_size, ids):
@@ -83,6 +120,13 @@ class RawSyntheticMultimodalDetection(Dataset):
         self.length = int(config.get('synthetic_length', length))
         self.seed = int(config.get('seed', 24)) + {"train": 0, "val": 50021}.get(mode, 100003)
         self.frame_hw, self.mel_hw = frame_hw, mel_hw
+        # extension key audio_format = waveform: the sample carries "audio_wave" float32 [8, N] (the decoded microphone waveforms,
+        # N = synthetic_wave_samples) instead of "audio", and DeviceInputPipeline makes the mel spectrograms on the device
+        fmt = config.get('audio_format', 'spectrogram')
+        if fmt not in ("spectrogram", "waveform"):
+            raise Exception(f"Unsupported audio_format {fmt} provided")
+        self.waveform = fmt == "waveform"
+        self.wave_samples = int(config.get('synthetic_wave_samples', 44100))
 
     def __len__(self):
         return self.length
@@ -93,19 +137,29 @@ class RawSyntheticMultimodalDetection(Dataset):
         rgb = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8)
         thermal = torch.randint(19000, 29000, (H, W), generator=g, dtype=torch.int32).to(torch.int16)   # uint16 bit pattern
         depth = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8)
+        if self.waveform:
+            return {"rgb": rgb, "thermal": thermal, "depth": depth, "audio_wave": synthetic_waveforms(self.seed, i, self.wave_samples),
+                    "id": i}
         audio = torch.randn(self.mel_hw[0], self.mel_hw[1], 8, generator=g) * 15.0 - 40.0
         return {"rgb": rgb, "thermal": thermal, "depth": depth, "audio": audio, "id": i}
 
 
 RAW_KEYS = ("rgb", "thermal", "depth", "audio")
+WAVE_KEYS = ("rgb", "thermal", "depth", "audio_wave")
+
+
+def raw_keys(sample) -> tuple:
+    """The tensor keys of a raw sample: its audio is either the mel stack "audio" [h,w,8] or the waveforms "audio_wave" [8,N]."""
+    return WAVE_KEYS if "audio_wave" in sample else RAW_KEYS
 
 
 def collate_raw(batch):
     """Raw samples of one batch -> ONE dict of stacked tensors {"rgb": [B,H,W,3], "thermal": [B,H,W], "depth": [B,H,W,3], "audio": [B,h,w,8],
     "id": [...]} when every frame of the batch has the same size (the corpus' fixed camera / mel geometry): 4 shared-memory segments,
     pinned copies and H2D copies per batch instead of 4 per sample.  Mixed sizes: the list of per-sample dicts, unchanged."""
-    if all(s[k].shape == batch[0][k].shape for s in batch for k in RAW_KEYS):
-        out = {k: torch.stack([s[k] for s in batch]) for k in RAW_KEYS}
+    keys = raw_keys(batch[0])
+    if all(raw_keys(s) == keys and s[k].shape == batch[0][k].shape for s in batch for k in keys):
+        out = {k: torch.stack([s[k] for s in batch]) for k in keys}
         out["id"] = [s["id"] for s in batch]
         return out
     return batch
@@ -133,6 +187,7 @@ class DeviceInputPipeline:
         self._held = []
         self._event = None
         self._batch = None
+        self._front = None
 
     def _stage(self, key, t: torch.Tensor) -> torch.Tensor:
         if t.is_pinned():
@@ -149,9 +204,13 @@ class DeviceInputPipeline:
 
     def submit(self, samples):
         """samples: list of per-sample dicts from RawSyntheticMultimodalDetection (or a real decoder with the same raw formats), or the
-        stacked dict `collate_raw` makes of them."""
+        stacked dict `collate_raw` makes of them.  A sample's audio is either "audio" [h,w,8] (ready-made mel stack: resized) or
+        "audio_wave" [8,N] (waveforms: mel spectrogram, then resized - `Audio2Spectogram` + `Resizer` on this stream)."""
         stacked = isinstance(samples, dict)
         B, S, call = (samples["rgb"].shape[0] if stacked else len(samples)), self.S, self.call
+        if self._front is None and ("audio_wave" in samples if stacked else any("audio_wave" in smp for smp in samples)):
+            from .audio import MelFrontEnd
+            self._front = MelFrontEnd(self.device)
         if self._event is not None:
             self._event.synchronize()          # the pinned buffers of the previous submit have been consumed
         self._held = []
@@ -163,10 +222,11 @@ class DeviceInputPipeline:
                    "depth": torch.empty(B, 3, S, S, device=self.device), "audio": torch.empty(B, 8, S, S, device=self.device)}
             mm = torch.empty(B, 2, device=self.device)
             if stacked:
-                whole = {k: self._stage((k, "batch"), samples[k]) for k in RAW_KEYS}
+                keys = raw_keys(samples)
+                whole = {k: self._stage((k, "batch"), samples[k]) for k in keys}
             for b in range(B):
                 if stacked:
-                    smp, stage = {k: whole[k][b] for k in RAW_KEYS}, (lambda key, t: t)
+                    smp, stage = {k: whole[k][b] for k in keys}, (lambda key, t: t)
                 else:
                     smp, stage = samples[b], self._stage
                 rgb = stage(("rgb", b), smp["rgb"]); H, W = rgb.shape[:2]
@@ -177,7 +237,11 @@ class DeviceInputPipeline:
                 call("mmd_image_minmax", t, 1, H * W, self.ir[0], self.ir[1], mm[b])
                 call("mmd_image_letterbox", t, 1, H, W, 1, 1.0 / 255.0, None, None, 1, self.ir[0], self.ir[1], mm[b], S,
                      out["thermal"][b])
-                a = stage(("audio", b), smp["audio"]); h, w, c = a.shape
+                if "audio_wave" in smp:
+                    a = self._front.melspec(stage(("audio_wave", b), smp["audio_wave"])[None])[0]
+                else:
+                    a = stage(("audio", b), smp["audio"])
+                h, w, c = a.shape
                 call("mmd_resize_cubic", a, h, w, c, S, out["audio"][b])
             self._event = self.stream.record_event()
         self._batch = out

@@ -228,6 +228,25 @@ def main(argv=None):
     kdlist_pass = kdlist_aug and cfg.getboolean("audio_augmentation_merge", False)
     if kdlist_aug and raw:
         raise Exception("traditional_nms_kdlist_augmented needs the dataset's yield_batch: not available with input_pipeline = raw")
+    # audio_mix (extension key, absent -> spectrogram): how the augmented KD-list step mixes two recordings' audio.  "spectrogram": the
+    # synthetic dataset's dB-domain mix of ready-made spectrograms (_yield_batch).  "waveform": what upstream's merge_audios does - the
+    # two recordings' waveforms are averaged and their mel spectrograms made and resized on the device (mm_distillnet_amd.audio)
+    audio_mix = cfg.get("audio_mix", "spectrogram")
+    if audio_mix not in ("spectrogram", "waveform"):
+        raise Exception(f"Unsupported audio_mix {audio_mix} provided")
+    front, wave_pin, wave_done = None, {}, None
+    if kdlist_aug and audio_mix == "waveform":
+        from mm_distillnet_amd.audio import MelFrontEnd
+        front = MelFrontEnd(dev)
+
+    def stage_waves(key, t):
+        # page-locked staging buffer kept across steps: the H2D copy is then asynchronous on the copy stream (from pageable memory it
+        # would be a staged copy the host waits for)
+        p = wave_pin.get(key)
+        if p is None or p.shape != t.shape:
+            p = wave_pin[key] = torch.empty(t.shape, dtype=t.dtype).pin_memory()
+        p.copy_(t)
+        return p.to(dev, non_blocking=True)
     no_validation = cfg.getboolean("no_validation", False)
     steps, captured, loss, val_loss = 0, False, float("nan"), float("nan")
     stop = False
@@ -273,8 +292,22 @@ def main(argv=None):
                 # then go through the RGB teacher as a 4th list entry is NOT decided by this draw: upstream hands the model
                 # augment=cfg audio_augmentation_merge (traditional.py:136), so with the flag off only the mixed audio is used.
                 # (Flag on and no draw: upstream would feed the dataset's `label` to the RGB teacher - not reproduced, see INTEGRATION.md.)
-                aug_rgb, mixed = train_set.yield_batch(batch["audio"].shape[0], item[5])
-                batch = dict(batch, audio=mixed.to(dev, non_blocking=True))
+                if front is not None:
+                    # waveform mix: both waveform batches go through pinned staging buffers and cross PCIe on the input pipeline's copy
+                    # stream, and the front end runs there, beside the steps still in flight on the compute stream; outside the captured
+                    # graphs, ordered before replay()
+                    aug_rgb, wav_a, wav_b = train_set.yield_batch_waves(batch["audio"].shape[0], item[5])
+                    if wave_done is not None:
+                        wave_done.synchronize()          # the staging buffers' previous copies (an earlier step: long finished)
+                    with torch.cuda.stream(pipe.stream):
+                        mixed = front.student_input(stage_waves("a", wav_a), stage_waves("b", wav_b), cfg.getint("image_size"))
+                        mixed_ready = wave_done = pipe.stream.record_event()
+                    torch.cuda.current_stream().wait_event(mixed_ready)
+                    mixed.record_stream(torch.cuda.current_stream())
+                    batch = dict(batch, audio=mixed)
+                else:
+                    aug_rgb, mixed = train_set.yield_batch(batch["audio"].shape[0], item[5])
+                    batch = dict(batch, audio=mixed.to(dev, non_blocking=True))
                 if kdlist_pass:
                     batch["aug_rgb"] = aug_rgb.to(dev, non_blocking=True)
             ts = tick()
