@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 import train as T  # noqa: E402
 from mm_distillnet_amd.data import SyntheticMultimodalDetection, collate  # noqa: E402
-from mm_distillnet_amd.metrics import evaluate_table  # noqa: E402
+from mm_distillnet_amd.metrics import evaluate_table, table_from_stats  # noqa: E402
 from mm_distillnet_amd.step import DistillEngine  # noqa: E402
 
 
@@ -50,19 +50,34 @@ def main(argv=None):
     eng.load(sstate, tstates)
     test_set = SyntheticMultimodalDetection(cfg, "test")
     loader = torch.utils.data.DataLoader(test_set, batch_size=cfg.getint("batch_size"), shuffle=False, collate_fn=collate)
-    # get_predictions_multiteacher (src/utils/utils.py:1720-1830): per batch the student's detections and the merged teacher
-    # pseudo ground truth, plus the flat list of ground-truth class ids
-    all_pred, all_lab, labels = [], [], []
-    for rgb, thermal, depth, audio, _, ids in loader:
-        batch = {"rgb": rgb.to(dev), "thermal": thermal.to(dev), "depth": depth.to(dev), "audio": audio.to(dev)}
-        p, l = eng.predict(batch)
-        all_pred.append(p); all_lab.append(l)
-        labels += [float(r[4]) for t in l for r in np.asarray(t, np.float32).reshape(-1, 5)]
-    eng.check_overflow()
     # evaluate() (src/utils/utils.py:2018-2181): one row per testing point; 'ALL' when the three teachers are in use
     mods = [m for m in ("rgb", "depth", "thermal") if cfg.getboolean(f"use_{m}", True)]
     modality = "ALL" if len(mods) == 3 else ",".join(mods)
-    table = evaluate_table(all_pred, all_lab, labels, cfg.getint("image_size"))
+    mode = cfg.get("eval_metrics", "host")      # host until the device path is timed against it: profiles/eval_metrics_notes.md
+    if mode not in ("device", "host"):
+        raise Exception(f"Unsupported eval_metrics {mode} (device | host)")
+    if mode == "device":
+        # the matching and the central distances run on the device behind every batch (csrc/evalstats.hip): no per-batch synchronize,
+        # the record is copied once, at the end.  Record capacity: cfg eval_record_rows (predictions of images with ground truth, and
+        # ground-truth boxes, over the whole test set); exceeded -> end_eval raises, nothing is truncated silently
+        rows = cfg.getint("eval_record_rows", 0) or max(1 << 16, 256 * len(test_set))
+        eng.begin_eval(len(test_set), rows)
+        for i, (rgb, thermal, depth, audio, _, ids) in enumerate(loader):
+            eng.eval_batch({"rgb": rgb.to(dev), "thermal": thermal.to(dev), "depth": depth.to(dev), "audio": audio.to(dev)})
+            if i % 64 == 63:
+                eng.check_overflow()      # a record that is too small ends the run here, not after the last batch
+        table = table_from_stats(eng.end_eval(), cfg.getint("image_size"))
+    else:
+        # get_predictions_multiteacher (src/utils/utils.py:1720-1830): per batch the student's detections and the merged teacher
+        # pseudo ground truth, plus the flat list of ground-truth class ids
+        all_pred, all_lab, labels = [], [], []
+        for rgb, thermal, depth, audio, _, ids in loader:
+            batch = {"rgb": rgb.to(dev), "thermal": thermal.to(dev), "depth": depth.to(dev), "audio": audio.to(dev)}
+            p, l = eng.predict(batch)
+            all_pred.append(p); all_lab.append(l)
+            labels += [float(r[4]) for t in l for r in np.asarray(t, np.float32).reshape(-1, 5)]
+        eng.check_overflow()
+        table = evaluate_table(all_pred, all_lab, labels, cfg.getint("image_size"))
     print({k: round(v, 3) for k, v in table.items()})
     if os.path.exists(cfg["exp_name"]):
         import pandas as pd

@@ -333,6 +333,32 @@ int mmd_nms_ws_floats(int nmax);
 // Rows per image the single-pass (all-in-LDS) NMS handles; the arrays' capacity itself is the run-time `cap` argument.
 int mmd_pp_cap(void);
 
+// Detection statistics of one evaluation batch, appended to a device-side record (csrc/evalstats.hip; get_batch_statistics and
+// get_batch_central_distances, src/utils/utils.py:979-1136, bit for bit as mm_distillnet_amd/metrics.py computes them on the host).
+// In: predictions rows [B, cap, 6] (x1,y1,x2,y2,score,class) with cnt [B], ground truth boxes [B, G, 5] (x1,y1,x2,y2,class) with
+// nbox [B]; counts are clamped to [0, cap] / [0, G], rows at and behind a count are never read.
+// Record, in image order then row order, behind cursor int[3] = {rows, images, classes}:
+//   rec_rows [max_rows, 2] (score, class) and rec_tp [max_rows]: one row per prediction of every image that has predictions AND boxes,
+//     in the given prediction order; bit k of rec_tp = true positive at IoU threshold fp32(0.5 + 0.05 k), k = 0..8 (best box by +1-pixel
+//     IoU, first index on ties, each box taken once per threshold; a prediction whose class no box of the image has is never one);
+//   rec_cd [max_images, 3] (sum dx, sum dy, n_boxes): one row per image, all zero for an image without boxes; the host divides;
+//   rec_gt [max_gt]: the classes of every image's boxes.
+// The call advances the cursor by the batch (a second small launch behind the first: calls append one after another in stream order).
+// Workspace ws: B * mmd_eval_ws_floats(cap, G) floats, NULL when that is 0.  An image of up to mmd_eval_lds_cap(0) predictions and
+// mmd_eval_lds_cap(1) boxes runs in LDS; a larger one runs the same algorithm through ws - any count the arrays can hold is exact.
+// ws and the record need no zeroing (every entry is written before it is read); the caller zeroes `cursor` when it starts a record and
+// `overflow`, which is sticky (set, never cleared).
+// Capacity: a row, image or class that does not fit max_rows / max_images / max_gt -> *overflow = 1, it is dropped (the entries that
+// fit are written, in order), nothing is written at or behind a capacity, and the cursor stops at the capacity.
+// Null pointers (ws when the query is not 0), B, cap, G or a capacity <= 0 -> MMD_EINVAL, nothing is launched.
+int mmd_eval_match(const float* rows, const int* cnt, int cap, const float* boxes, const int* nbox, int G, int B, float* rec_rows, int* rec_tp, int max_rows, float* rec_cd, int max_images, float* rec_gt, int max_gt, int* cursor, float* ws, int* overflow, hipStream_t stream);
+
+// Floats PER IMAGE of mmd_eval_match's `ws` for arrays of cap predictions and G boxes per image: 0 when both fit the LDS path.
+int mmd_eval_ws_floats(int cap, int G);
+
+// Counts up to which mmd_eval_match keeps an image in LDS: which = 0 predictions, 1 boxes.
+int mmd_eval_lds_cap(int which);
+
 // Profiling hooks for bench.py (hipEvents on the launch stream).
 int mmd_prof_is_on(int family);
 

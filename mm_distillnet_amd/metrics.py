@@ -62,32 +62,38 @@ def get_batch_central_distances(outputs: Sequence, targets: Sequence, width: flo
     predictions is compared against zeros."""
     cd_x, cd_y = [], []
     for out, tgt in zip(outputs, targets):
-        tgt = _rows(tgt, 5)
-        if len(tgt) < 1:
+        if len(_rows(tgt, 5)) < 1:
             continue
-        tpt = tgt[:, 2:4] - tgt[:, 0:2]
-        tlab = tgt[:, -1]
-        out = _rows(out, 6)
-        if len(out) < 1:
-            plab = np.zeros_like(tlab)
-            opt = np.zeros_like(tpt)
-        else:
-            plab = out[:, -1].copy()
-            opt = out[:, 2:4] - out[:, 0:2]
-        dx, dy = [], []
-        for i in range(len(tpt)):
-            sel = plab == tlab[i]
-            valid = opt[sel]
-            orig = np.arange(len(plab))[sel]
-            if len(valid) < 1:
-                dx.append(tpt[i, 0]); dy.append(tpt[i, 1])
-            else:
-                j = int(np.argmin(np.sum((valid - tpt[i]) ** 2, axis=1)))
-                plab[orig[j]] = -1
-                dx.append(np.abs(tpt[i, 0] - valid[j, 0])); dy.append(np.abs(tpt[i, 1] - valid[j, 1]))
+        dx, dy = _box_distances(out, tgt)
         cd_x.append(np.mean(dx) / width)
         cd_y.append(np.mean(dy) / height)
     return cd_x, cd_y
+
+
+def _box_distances(out, tgt):
+    """One image with ground truth -> the per-box float32 (dx, dy) lists get_batch_central_distances averages."""
+    tgt = _rows(tgt, 5)
+    tpt = tgt[:, 2:4] - tgt[:, 0:2]
+    tlab = tgt[:, -1]
+    out = _rows(out, 6)
+    if len(out) < 1:
+        plab = np.zeros_like(tlab)
+        opt = np.zeros_like(tpt)
+    else:
+        plab = out[:, -1].copy()
+        opt = out[:, 2:4] - out[:, 0:2]
+    dx, dy = [], []
+    for i in range(len(tpt)):
+        sel = plab == tlab[i]
+        valid = opt[sel]
+        orig = np.arange(len(plab))[sel]
+        if len(valid) < 1:
+            dx.append(tpt[i, 0]); dy.append(tpt[i, 1])
+        else:
+            j = int(np.argmin(np.sum((valid - tpt[i]) ** 2, axis=1)))
+            plab[orig[j]] = -1
+            dx.append(np.abs(tpt[i, 0] - valid[j, 0])); dy.append(np.abs(tpt[i, 1] - valid[j, 1]))
+    return dx, dy
 
 
 def compute_ap(recall, precision):
@@ -145,6 +151,65 @@ def evaluate_table(all_predictions: List[List], all_labels: List[List], labels: 
         else:
             tp, sc, lb = [np.concatenate(x, 0) for x in zip(*sm)]
             _, _, ap, _, _, _ = ap_per_class(tp, sc, lb, labels)
+            mean = float(ap.mean()) if ap.size else float("nan")
+        if iou == 0.5:
+            out["AP@0.5"] = mean * 100
+            out["CDx"] = float(np.mean(cd_x)) * 100
+            out["CDy"] = float(np.mean(cd_y)) * 100
+        if iou == 0.75:
+            out["AP@0.75"] = mean * 100
+        rec.append(mean)
+    out["AP@Ave"] = float(np.mean(rec)) * 100
+    return out
+
+
+def stats_from_lists(all_predictions: List[List], all_labels: List[List]) -> dict:
+    """The evaluation record DistillEngine.end_eval returns, built on the host by the functions above (the definition the device
+    kernel csrc/evalstats.hip is held to): score / label float32 [n] and tp int32 [n] (bit k: true positive at threshold k) of the
+    predictions of every image with predictions and ground truth, cd float32 [images, 3] = (sum dx, sum dy, n_boxes) per image,
+    gt float32 [m] = the ground-truth classes."""
+    tp = sc = lb = None
+    for k, iou in enumerate(np.arange(0.5, 0.95, 0.05)):
+        sm = [m for bp, bl in zip(all_predictions, all_labels) for m in get_batch_statistics(bp, bl, np.around(iou, decimals=2))]
+        if k == 0:
+            sc = np.concatenate([m[1] for m in sm] + [np.zeros(0, np.float32)]).astype(np.float32)
+            lb = np.concatenate([m[2] for m in sm] + [np.zeros(0, np.float32)]).astype(np.float32)
+            tp = np.zeros(sc.shape[0], np.int32)
+        tp |= np.concatenate([m[0] for m in sm] + [np.zeros(0)]).astype(np.int32) << k
+    cd, gt = [], []
+    for bp, bl in zip(all_predictions, all_labels):
+        for out, tgt in zip(bp, bl):
+            tgt = _rows(tgt, 5)
+            gt.append(tgt[:, 4])
+            if len(tgt) < 1:
+                cd.append((0.0, 0.0, 0.0))
+                continue
+            dx, dy = _box_distances(out, tgt)
+            cd.append((np.sum(np.asarray(dx, np.float32)), np.sum(np.asarray(dy, np.float32)), len(tgt)))
+    return {"score": sc, "label": lb, "tp": tp, "cd": np.asarray(cd, np.float32).reshape(-1, 3),
+            "gt": np.concatenate(gt + [np.zeros(0, np.float32)]).astype(np.float32)}
+
+
+def table_from_stats(stats: dict, image_size: int) -> dict:
+    """evaluate_table from an evaluation record (DistillEngine.end_eval, or stats_from_lists on the host): the same dict, value for
+    value.  The match of a prediction to its box is in the record once; per threshold only the TP bit is unpacked before ap_per_class.
+    CDx / CDy: per image sum / n_boxes / image_size in float32, as get_batch_central_distances divides."""
+    out = {"AP@Ave": 0.0, "AP@0.5": 0.0, "AP@0.75": 0.0, "CDx": 0.0, "CDy": 0.0}
+    sc, lb, mask = np.asarray(stats["score"], np.float32), np.asarray(stats["label"], np.float32), np.asarray(stats["tp"])
+    labels = np.asarray(stats["gt"], np.float64)
+    cd = np.asarray(stats["cd"], np.float32).reshape(-1, 3)
+    cd = cd[cd[:, 2] > 0]                     # images with ground truth
+    if sc.size == 0:                          # no image had both predictions and ground truth: the reference's sentinel row
+        cd_x = cd_y = np.array([100.0])
+    else:
+        cd_x = cd[:, 0] / cd[:, 2] / image_size
+        cd_y = cd[:, 1] / cd[:, 2] / image_size
+    rec = []
+    for k, iou in enumerate(np.around(np.arange(0.5, 0.95, 0.05), decimals=2)):
+        if sc.size == 0:
+            mean = 0.0
+        else:
+            _, _, ap, _, _, _ = ap_per_class(((mask >> k) & 1).astype(np.float64), sc, lb, labels)
             mean = float(ap.mean()) if ap.size else float("nan")
         if iou == 0.5:
             out["AP@0.5"] = mean * 100

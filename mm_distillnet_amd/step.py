@@ -16,6 +16,7 @@ import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -108,6 +109,7 @@ class DistillEngine:
         for i in cfg.valid_prediction_ids:
             self.valid_mask |= 1 << int(i)
         self.cap = int(cfg.cand_cap)     # 0: set to the anchor count at the first step
+        self._eval: Optional[dict] = None  # the evaluation record between begin_eval and end_eval
         self.graph = None
         self._graphs: Dict[str, tuple] = {}       # step variant ("plain" / "aug") -> (static inputs, g_main, g_tail, g_opt, outputs)
         self.concurrent_teachers = True
@@ -636,11 +638,10 @@ class DistillEngine:
         self.g_opt.replay()
         return self.out
 
-    @torch.no_grad()
-    def predict(self, batch: Dict[str, torch.Tensor]):
-        """Evaluation path (SURVEY §8f-1, get_predictions_multiteacher): student detections [n,6] per image from an
-        eval-mode forward, and the merged multi-teacher pseudo ground truth [m,5] per image, as numpy lists."""
-        cfg, S = self.cfg, self.cfg.image_size
+    def _predict_device(self, batch: Dict[str, torch.Tensor]):
+        """The device half of the evaluation path: eval-mode student detections and the merged multi-teacher pseudo ground truth.
+        -> (rows_s [B,cap,6], cnt_s [B], boxes [B,G,5], nbox [B], G, B), all in the step workspace."""
+        S = self.cfg.image_size
         B = batch["audio"].shape[0]
         self.ws.reset()
         self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
@@ -657,11 +658,72 @@ class DistillEngine:
             r, c = self._pseudo_labels(net, cls_t, reg_t, B, A, S)
             rows_t.append(r); cnt_t.append(c)
         boxes, nbox, G = self._merge(rows_t, cnt_t, B, False)
+        return rows_s, cnt_s, boxes, nbox, G, B
+
+    @torch.no_grad()
+    def predict(self, batch: Dict[str, torch.Tensor]):
+        """Evaluation path (SURVEY §8f-1, get_predictions_multiteacher): student detections [n,6] per image from an
+        eval-mode forward, and the merged multi-teacher pseudo ground truth [m,5] per image, as numpy lists."""
+        rows_s, cnt_s, boxes, nbox, G, B = self._predict_device(batch)
         torch.cuda.synchronize()
         cs, nb = cnt_s.cpu().tolist(), nbox.cpu().tolist()
         preds = [rows_s[i, :cs[i]].cpu().numpy() for i in range(B)]
         labels = [boxes[i, :nb[i]].cpu().numpy() for i in range(B)]
         return preds, labels
+
+    # ---- evaluation statistics on the device (csrc/evalstats.hip): begin_eval, eval_batch x N, end_eval -> metrics.table_from_stats
+    def begin_eval(self, max_images: int, max_rows: int, max_gt: Optional[int] = None):
+        """Allocate and reset the evaluation record: up to max_images images, max_rows predictions (of images that have ground truth) and
+        max_gt ground-truth boxes (default max_rows) over the whole evaluation.  One int32 buffer (12 bytes per row, 12 per image, 4 per box):
+        cursor[3] + overflow | tp mask [max_rows] | (score, class) [max_rows, 2] | (sum dx, sum dy, n) [max_images, 3] | gt class [max_gt]."""
+        max_images, max_rows = int(max_images), int(max_rows)
+        max_gt = max_rows if max_gt is None else int(max_gt)
+        if min(max_images, max_rows, max_gt) <= 0:
+            raise ValueError("begin_eval: capacities must be positive")
+        buf = torch.empty(4 + 3 * max_rows + 3 * max_images + max_gt, dtype=torch.int32, device=self.device)
+        buf[:4].zero_()          # cursor and sticky flag; the kernel writes every entry of the record before anyone reads it
+        o = 4
+        tp = buf[o:o + max_rows]; o += max_rows
+        rows = buf[o:o + 2 * max_rows].view(torch.float32); o += 2 * max_rows
+        cd = buf[o:o + 3 * max_images].view(torch.float32); o += 3 * max_images
+        gt = buf[o:o + max_gt].view(torch.float32)
+        self._eval = dict(buf=buf, cursor=buf[0:3], overflow=buf[3:4], tp=tp, rows=rows, cd=cd, gt=gt,
+                          max_rows=max_rows, max_images=max_images, max_gt=max_gt)
+
+    @torch.no_grad()
+    def eval_batch(self, batch: Dict[str, torch.Tensor]):
+        """predict's device work, then ONE mmd_eval_match call that appends the batch's statistics to the record: no synchronize, no
+        device-to-host copy."""
+        ev = self._eval
+        if ev is None:
+            raise RuntimeError("eval_batch without begin_eval")
+        rows_s, cnt_s, boxes, nbox, G, B = self._predict_device(batch)
+        n = int(_lib.LIB.load().mmd_eval_ws_floats(self.cap, G))
+        if n < 0:
+            raise RuntimeError(f"mmd_eval_ws_floats({self.cap}, {G}) failed with status {n}")
+        ws = self.ws.alloc((B * n,)) if n else None
+        call("mmd_eval_match", rows_s, cnt_s, self.cap, boxes, nbox, G, B, ev["rows"], ev["tp"], ev["max_rows"], ev["cd"],
+             ev["max_images"], ev["gt"], ev["max_gt"], ev["cursor"], ws, ev["overflow"])
+
+    def end_eval(self) -> dict:
+        """The record -> plain numpy: score / label float32 [n] and tp int32 [n] (bit k: true positive at IoU 0.5 + 0.05 k) of the
+        predictions in image order, cd float32 [images, 3] (sum dx, sum dy, n_boxes), gt float32 [m] ground-truth classes.  The 4-int
+        header is read first (the one synchronize of the evaluation), then only the rows in front of the cursor are copied: the
+        traffic follows the data, not the capacity.  Raises when the record (or a pseudo-label array, check_overflow) was too small."""
+        ev = self._eval
+        if ev is None:
+            raise RuntimeError("end_eval without begin_eval")
+        self._eval = None
+        if int(ev["overflow"].item()):
+            raise RuntimeError("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
+                               % (ev["max_images"], ev["max_rows"], ev["max_gt"]))
+        self.check_overflow()
+        nr, ni, ng = (int(v) for v in ev["cursor"].cpu().tolist())
+        tp = ev["tp"][:nr].cpu().numpy()
+        rows = ev["rows"][:2 * nr].cpu().numpy().reshape(-1, 2)
+        cd = ev["cd"][:3 * ni].cpu().numpy().reshape(-1, 3)
+        gt = ev["gt"][:ng].cpu().numpy()
+        return {"score": rows[:, 0].copy(), "label": rows[:, 1].copy(), "tp": tp, "cd": cd, "gt": gt}
 
     @torch.no_grad()
     def eval_losses(self, batch: Dict[str, torch.Tensor], teacher_labels: Optional[List[tuple]] = None):
@@ -672,6 +734,10 @@ class DistillEngine:
         return out["reg"].item(), out["cls"].item(), out["kd"].sum().item()
 
     def check_overflow(self):
+        ev = self._eval
+        if ev is not None and int(ev["overflow"].item()):
+            raise RuntimeError("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
+                               % (ev["max_images"], ev["max_rows"], ev["max_gt"]))
         if int(self.overflow.item()):
             raise RuntimeError("pseudo-label capacity exceeded (cfg cand_cap = %d rows / max_boxes = %d per image; 0 = unlimited)"
                                % (self.cfg.cand_cap, self.cfg.max_boxes))
