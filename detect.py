@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Audio-only detection with the trained student: a checkpoint plus microphone waveforms in, boxes out.
+
+    python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
+
+X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
+samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
+image_size: what mp3_to_pkl.py:31-41, `MultimodalDetection.__getitem__` and `Resizer` make of a recording upstream), the student's
+eval-mode forward and the post-processing of the reference's evaluation (score > conf_threshold, class filter, NMS).  The detection
+settings (image_size, conf_threshold, nms_threshold, valid_labels, precision, compound_coef) are read from the cfg file like train.py
+and evaluate.py read them.  No teacher is built or loaded.  Output: one CSV row per box, columns clip,x1,y1,x2,y2,score,label.
+"""
+import argparse
+import csv
+import os
+import sys
+import wave
+
+import numpy as np
+
+if os.environ.get("MMD_HW_QUEUES"):       # as train.py / evaluate.py: must be set before the HIP runtime starts
+    os.environ.setdefault("GPU_MAX_HW_QUEUES", os.environ["MMD_HW_QUEUES"])
+import torch
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+import train as T  # noqa: E402
+from mm_distillnet_amd.detector import AudioDetector  # noqa: E402
+
+CHANNELS, SAMPLE_RATE = 8, 44100
+COLUMNS = ("clip", "x1", "y1", "x2", "y2", "score", "label")
+
+
+def read_npy(path: str) -> np.ndarray:
+    a = np.load(path, allow_pickle=False)
+    if a.dtype != np.float32:
+        raise ValueError(f"{path}: waveforms must be float32, found {a.dtype}")
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[1] != CHANNELS:
+        raise ValueError(f"{path}: expected [{CHANNELS}, N] or [B, {CHANNELS}, N] waveforms, found shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def read_wav(path: str) -> np.ndarray:
+    with wave.open(path, "rb") as w:
+        if w.getframerate() != SAMPLE_RATE:
+            raise ValueError(f"{path}: sample rate {w.getframerate()} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
+        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+            raise ValueError(f"{path}: only 16-bit PCM is supported, found {8 * w.getsampwidth()}-bit {w.getcomptype()}")
+        if w.getnchannels() != CHANNELS:
+            raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {w.getnchannels()}")
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, CHANNELS)
+    return np.ascontiguousarray((pcm.astype(np.float32) / np.float32(32768.0)).T)[None]
+
+
+def read_input(path: str) -> np.ndarray:
+    """-> float32 [B, 8, N]"""
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        return read_npy(path)
+    if ext == ".wav":
+        return read_wav(path)
+    raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+
+
+def write_csv(path: str, rows_per_clip) -> int:
+    n = 0
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(COLUMNS)
+        for clip, rows in enumerate(rows_per_clip):
+            for r in np.asarray(rows, np.float32).reshape(-1, 6):
+                out.writerow([clip] + ["%.9g" % float(v) for v in r])      # 9 digits: float32 round-trips
+                n += 1
+    return n
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config_file", required=True)
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--input", required=True)
+    ap.add_argument("--output", required=True)
+    ap.add_argument("--overwrite", type=str, default=None)
+    a = ap.parse_args(argv)
+    cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
+    waves = read_input(a.input)
+    torch.cuda.set_device(0)
+    dev = "cuda:0"
+    sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
+    c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
+    det.load(c["state_dict"] if "state_dict" in c else c)
+    rows = det.detect(torch.from_numpy(waves).to(dev))
+    det.check_overflow()
+    n = write_csv(a.output, rows)
+    print("%d clips, %d boxes -> %s" % (len(rows), n, a.output))
+    return rows
+
+
+if __name__ == "__main__":
+    main()

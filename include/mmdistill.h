@@ -531,6 +531,10 @@ int mmd_image_letterbox(const void* src, int dtype, int H, int W, int C, float s
 // Resizer's audio branch: cv2.resize(INTER_CUBIC) of an [h,w,C] spectrogram stack to [C,S,S] (transformations.py:435-441).
 int mmd_resize_cubic(const float* src, int h, int w, int C, int common_size, float* dst, hipStream_t stream);
 
+// mmd_resize_cubic (Resizer's audio branch, transformations.py:435-441) for a batch in ONE launch: src[batch, h, w, C] ->
+// dst[batch, C, S, S], the sample index in the grid; every sample's bits are those of the per-sample entry point.
+int mmd_resize_cubic_batch(const float* src, int batch, int h, int w, int C, int common_size, float* dst, hipStream_t stream);
+
 // ---- waveform front end (csrc/melspec.hip).  MultimodalDetection.merge_audios (src/datasets/MultimodalDetection.py:329-353, called per
 // sample from yield_batch, :355-367) and Audio2Spectogram (src/datasets/transformations.py:251-266):
 // librosa.feature.melspectrogram(sr=44100, n_fft=1024, hop_length=256, n_mels=80) of each microphone channel.  librosa's arithmetic
@@ -548,6 +552,28 @@ int mmd_melspec_frames(long long n_samples);
 // j < band_len[m] <= band_stride (80 * band_stride <= 4096; mm_distillnet_amd.audio.mel_bands).  One launch, raw device pointers,
 // no allocation; out needs no zeroing and two calls on the same input give the same bits.  -22 on null pointers / bad sizes before any launch.
 int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long long n_samples, const int* band_start, const int* band_len, const float* band_w, int band_stride, float* out, hipStream_t stream);
+
+// mmd_melspec_power for a whole batch, and the dB map the student's stored input is (mp3_to_pkl.py:31-41: melspectrogram(...), then
+// librosa.power_to_db(S, ref=np.max); stacked by MultimodalDetection.__getitem__, src/datasets/MultimodalDetection.py:219-224; the
+// melspectrogram call is merge_audios', MultimodalDetection.py:329-353, and Audio2Spectogram's, transformations.py:251-266).
+// wav_a[batch, channels, n_samples] (wav_b: the partner recordings of the same shape, or null) -> out[batch, 80, T, channels], the sample
+// index in the grid: one launch for db = 0, and every sample's bits are those mmd_melspec_power gives that sample alone.
+// db = 1: power_to_db per (sample, channel) map S[80, T] as published - ls = 10 log10(max(1e-10, S)) - 10 log10(max(1e-10, max S)),
+// then max(ls, max(ls) - 80) - in fp32 with each product and the difference rounded on its own.  librosa is not in the reference tree:
+// the rule is restated and pinned to tests/melspec_db_ref.py, parity with librosa's power_to_db itself is UNPINNED.  The maxima go
+// through max_ws[batch * channels] (any 4-byte words; null allowed for db = 0) as unsigned atomic maxima of the float bits (power is
+// >= +0), so they do not depend on the order of arrival: two calls give the same bits.  Launch sequence for db = 1: one memset node on
+// max_ws, the spectrogram launch, one elementwise launch.  max_ws and out need no zeroing; no allocation, no host synchronisation
+// (capturable in a hipGraph).  -22 on null pointers / bad sizes / db outside {0, 1} before any launch.
+int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
+
+// The same power_to_db(S, ref=np.max) (mp3_to_pkl.py:31-41), in place, for a ready-made POWER stack x[batch, h, w, channels] (what
+// Audio2Spectogram, src/datasets/transformations.py:251-266, hands on): the maximum is again per (sample, channel) map.  On the db = 0
+// output of mmd_melspec_batch it gives the bits of db = 1.  Values below +0 count as 0 in the maximum (max(1e-10, .) floors them anyway).
+// One memset node on max_ws[batch * channels] (needs no zeroing), one maximum launch, one elementwise launch; channels <= 1024.
+// Restated from the published rule, pinned to tests/melspec_db_ref.py; parity with librosa's power_to_db itself is UNPINNED.
+// -22 on null pointers / bad sizes before any launch.
+int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_ws, hipStream_t stream);
 
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction

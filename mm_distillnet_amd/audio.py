@@ -1,10 +1,12 @@
-"""Waveform front end of the student's audio input: power mel spectrograms (and the mix of two recordings) on the GPU.
+"""Waveform front end of the student's audio input: mel spectrograms (power or dB, and the mix of two recordings) on the GPU.
 
 `MultimodalDetection.merge_audios` (src/datasets/MultimodalDetection.py:329-353, called per sample from `yield_batch`, :355-367) averages
 two recordings' eight microphone waveforms and runs `librosa.feature.melspectrogram(sr=44100, n_fft=1024, hop_length=256, n_mels=80)` on
 each channel, then resizes with cv2.INTER_CUBIC; `Audio2Spectogram` (src/datasets/transformations.py:251-266) is the same transform for
-one recording.  Here the host only builds the Slaney filter bank; the spectrogram is csrc/melspec.hip (`mmd_melspec_power`), the resize
-`mmd_resize_cubic`.  librosa's and cv2's arithmetic is restated, parity with the libraries themselves is unpinned."""
+one recording.  The student's stored input is the dB map `librosa.power_to_db(S, ref=np.max)` of each microphone's spectrogram
+(mp3_to_pkl.py:31-41): `db=True`.  Here the host only builds the Slaney filter bank; the spectrogram and the dB conversion are
+csrc/melspec.hip (`mmd_melspec_batch`, `mmd_power_to_db`), the resize `mmd_resize_cubic_batch`.  librosa's and cv2's arithmetic is
+restated, parity with the libraries themselves is unpinned."""
 from __future__ import annotations
 
 import numpy as np
@@ -73,23 +75,44 @@ class MelFrontEnd:
             raise ValueError(f"a waveform of {n_samples} samples is too short for the reflect padding (more than {N_FFT // 2} needed)")
         return T
 
-    def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None) -> torch.Tensor:
-        """[B, C, N] float32 device waveforms (the mean of the two when wav_b is given) -> power mel spectrograms [B, 80, T, C]."""
+    def _check(self, wav_a, wav_b):
         if wav_a.dim() != 3 or wav_a.dtype != torch.float32 or (wav_b is not None and (wav_b.shape != wav_a.shape or wav_b.dtype != wav_a.dtype)):
             raise ValueError("melspec takes float32 [B, C, N] waveforms (two of one shape to mix them)")
+
+    def melspec_into(self, wav_a, wav_b, db: bool, max_ws, out):
+        """`melspec` into the caller's buffers, nothing allocated (a captured graph replays it): out [B, 80, T, C]; max_ws: B * C 4-byte
+        words for the per-(sample, channel) maxima of the dB conversion (needs no zeroing; None for db=False)."""
         B, C, N = wav_a.shape
-        out = torch.empty(B, self.n_mels, self.n_frames(N), C, device=self.device)
-        for b in range(B):
-            self.call("mmd_melspec_power", wav_a[b], None if wav_b is None else wav_b[b], C, N, self.start, self.length, self.band,
-                      self.stride, out[b])
+        self.call("mmd_melspec_batch", wav_a, wav_b, B, C, N, self.start, self.length, self.band, self.stride, 1 if db else 0, max_ws, out)
         return out
 
-    def student_input(self, wav_a: torch.Tensor, wav_b, S: int) -> torch.Tensor:
-        """-> [B, C, S, S]: the mel stacks resized with cv2.INTER_CUBIC's rule (`mmd_resize_cubic`).  S is the step's image_size;
-        upstream's merge_audios hard-codes common_size = 768 (:330), the image_size of its shipped cfg."""
-        mel = self.melspec(wav_a, wav_b)
+    def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None, db: bool = False) -> torch.Tensor:
+        """[B, C, N] float32 device waveforms (the mean of the two when wav_b is given) -> mel spectrograms [B, 80, T, C], the whole batch
+        in one launch sequence (`mmd_melspec_batch`).  db=False: power, as merge_audios returns it.  db=True: the dB map of the student's
+        stored input, power_to_db(S, ref=np.max) per sample and microphone (mp3_to_pkl.py:31-41)."""
+        self._check(wav_a, wav_b)
+        B, C, N = wav_a.shape
+        out = torch.empty(B, self.n_mels, self.n_frames(N), C, device=self.device)
+        ws = torch.empty(B * C, device=self.device) if db else None
+        return self.melspec_into(wav_a.contiguous(), None if wav_b is None else wav_b.contiguous(), db, ws, out)
+
+    def power_to_db(self, power: torch.Tensor) -> torch.Tensor:
+        """A ready-made POWER stack [B, h, w, C] (Audio2Spectogram's output) -> its dB map, in place (`mmd_power_to_db`)."""
+        if power.dim() != 4 or power.dtype != torch.float32:
+            raise ValueError("power_to_db takes a float32 [B, h, w, C] stack")
+        B, h, w, C = power.shape
+        self.call("mmd_power_to_db", power, B, h, w, C, torch.empty(B * C, device=self.device))
+        return power
+
+    def resize_into(self, mel, S: int, out):
         B, M, T, C = mel.shape
-        out = torch.empty(B, C, S, S, device=self.device)
-        for b in range(B):
-            self.call("mmd_resize_cubic", mel[b], M, T, C, S, out[b])
+        self.call("mmd_resize_cubic_batch", mel, B, M, T, C, S, out)
         return out
+
+    def student_input(self, wav_a: torch.Tensor, wav_b, S: int, db: bool = False) -> torch.Tensor:
+        """-> [B, C, S, S]: the mel stacks (power, or dB with db=True) resized with cv2.INTER_CUBIC's rule (`mmd_resize_cubic_batch`): at
+        most three launches and one memset node for the whole batch.  S is the step's image_size; upstream's merge_audios hard-codes
+        common_size = 768 (:330), the image_size of its shipped cfg."""
+        mel = self.melspec(wav_a, wav_b, db)
+        B, M, T, C = mel.shape
+        return self.resize_into(mel, S, torch.empty(B, C, S, S, device=self.device))

@@ -123,10 +123,13 @@ __device__ __forceinline__ void cubic_w(float x, float w[4]) {
   w[2] = ((A + 2.f) * (1.f - x) - (A + 3.f)) * (1.f - x) * (1.f - x) + 1.f;
   w[3] = 1.f - w[0] - w[1] - w[2];
 }
+// blockIdx.z = the sample of a batch: src[B, h, w, C] -> dst[B, C, S, S]
 __global__ __launch_bounds__(256) void resize_cubic_kernel(const float* __restrict__ src, int h, int w, int C, int S,
                                                            float* __restrict__ dst) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= S) return;
+  src += (size_t)blockIdx.z * h * w * C;
+  dst += (size_t)blockIdx.z * C * S * S;
   double fy = ((double)y + 0.5) * ((double)h / S) - 0.5, fx = ((double)x + 0.5) * ((double)w / S) - 0.5;
   int sy = (int)floor(fy), sx = (int)floor(fx);
   float wy[4], wx[4];
@@ -149,6 +152,13 @@ __global__ __launch_bounds__(256) void resize_cubic_kernel(const float* __restri
 extern "C" int mmd_resize_cubic(const float* src, int h, int w, int C, int common_size, float* dst, hipStream_t stream) {
   if (!src || !dst || h <= 0 || w <= 0 || C <= 0 || common_size <= 0) return MMD_EINVAL;
   hipLaunchKernelGGL(resize_cubic_kernel, dim3(cdiv(common_size, 256), common_size), dim3(256), 0, stream, src, h, w, C,
+                     common_size, dst);
+  return mmd_check_launch();
+}
+extern "C" int mmd_resize_cubic_batch(const float* src, int batch, int h, int w, int C, int common_size, float* dst, hipStream_t stream) {
+  if (!src || !dst || batch <= 0 || batch > 65535 || h <= 0 || w <= 0 || C <= 0 || common_size <= 0 || common_size > 65535)
+    return MMD_EINVAL;
+  hipLaunchKernelGGL(resize_cubic_kernel, dim3(cdiv(common_size, 256), common_size, batch), dim3(256), 0, stream, src, h, w, C,
                      common_size, dst);
   return mmd_check_launch();
 }

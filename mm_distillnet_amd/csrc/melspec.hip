@@ -7,7 +7,14 @@
 // librosa (0.7.2 in requirements.txt) is a third-party dependency that is neither part of the reference tree nor installed with this
 // project: the arithmetic below restates its published definition - y = (a + b) / 2 in fp32, reflect padding of n_fft / 2 samples
 // (edge sample not repeated), frames of 1024 at hop 256 times the periodic Hann window, |rfft|^2, Slaney mel bank - and is pinned to
-// tests/melspec_ref.py.  Parity with librosa itself is UNPINNED.  No power_to_db: merge_audios returns power.
+// tests/melspec_ref.py.  Parity with librosa itself is UNPINNED.  mmd_melspec_power has no power_to_db: merge_audios returns power.
+//
+// The student's ordinary input is the dB map of mp3_to_pkl.py:31-41: melspectrogram(...) then librosa.power_to_db(S, ref=np.max) per
+// microphone.  mmd_melspec_batch (db = 1) and mmd_power_to_db restate that published rule - ls = 10 log10(max(1e-10, S)) -
+// 10 log10(max(1e-10, max S)), then max(ls, max(ls) - 80) - pinned to tests/melspec_db_ref.py; parity with librosa's power_to_db itself
+// is UNPINNED.  The maximum is per (sample, channel): each block's epilogue sends the maximum of what it stored to one word of a
+// [B * C] workspace with an unsigned atomic max on the float's bits (power is >= +0, so the bit patterns order like the values; a
+// maximum does not depend on arrival order, so two launches give the same bits), and a second, elementwise launch converts in place.
 //
 // Shape: a block owns ONE channel and MEL_FPB = 8 consecutive frames.  Frames overlap by 75 %, so the block stages the (8 + 3) * 256
 // samples they cover in LDS once (mix and reflect index at that load; the index is clamped, never guarded: frames past the end compute
@@ -30,6 +37,7 @@
 #define MEL_ZROW 1088                               // 1024 complex values in rows of 16 padded to 17
 #define MEL_PROW 520                                // second power row's offset inside the (reused) exchange buffer
 #define MEL_WMAX 4096                               // band weights kept in LDS: 80 * band_stride floats at most (stride <= 51)
+#define MEL_DB_CMAX 1024                            // mmd_power_to_db: channels whose maxima one block keeps in LDS
 
 __device__ __forceinline__ float2 mel_cmul(float2 a, float2 w) { return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x); }
 __device__ __forceinline__ float2 mel_tw(int m) { return reinterpret_cast<const float2*>(mmd_mel_twiddle)[m]; }
@@ -77,18 +85,21 @@ __device__ __forceinline__ void mel_dft16(float2 v[16]) {
 }
 __device__ __forceinline__ int mel_pad(int i) { return i + (i >> 4); }
 
-template <bool MIX>
+// blockIdx.z = the sample of a batch ([B, C, N] waveforms -> [B, 80, T, C]); TRACK: also the block's maximum into mx_ws[sample * C + c]
+template <bool MIX, bool TRACK>
 __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restrict__ wav_a, const float* __restrict__ wav_b, long long N,
                                                             int T, int C, const int* __restrict__ band_start,
                                                             const int* __restrict__ band_len, const float* __restrict__ band_w,
-                                                            int band_stride, float* __restrict__ out) {
+                                                            int band_stride, float* __restrict__ out, unsigned int* __restrict__ mx_ws) {
   __shared__ float s_x[MEL_STAGE];
   __shared__ float2 s_z[4][MEL_ZROW];
   __shared__ float s_w[MEL_WMAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = blockIdx.y, f0 = blockIdx.x * MEL_FPB;
-  const float* pa = wav_a + (size_t)c * N;
-  const float* pb = MIX ? wav_b + (size_t)c * N : nullptr;
+  const size_t smp = blockIdx.z;
+  const float* pa = wav_a + (smp * C + c) * (size_t)N;
+  const float* pb = MIX ? wav_b + (smp * C + c) * (size_t)N : nullptr;
+  out += smp * MEL_NMEL * (size_t)T * C;
 
   // ---- stage the block's samples: padded position p <-> sample p - 512, reflected at both ends, then clamped (frames >= T only)
   const long long base = (long long)f0 * MEL_HOP - MEL_NFFT / 2;
@@ -180,6 +191,7 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
   // lanes store T * C floats apart.  Follow-up together with batching the samples of a batch into one launch.)
   // ---- mel projection from the band form: mel rows 0..63 one per lane (both frames share the weight), rows 64..79 on lanes 0..31
   const int t0 = f0 + wave * 2;
+  float mx = 0.f;                                    // TRACK: maximum of what this lane stores (frames >= T hold clamped samples: left out)
   {
     const int mel = lane;
     const int st = min(max(band_start[mel], 0), MEL_BINS - 1);
@@ -192,6 +204,7 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
     }
     if (t0 < T) out[((size_t)mel * T + t0) * C + c] = a0;
     if (t0 + 1 < T) out[((size_t)mel * T + t0 + 1) * C + c] = a1;
+    if (TRACK) mx = fmaxf(t0 < T ? a0 : 0.f, t0 + 1 < T ? a1 : 0.f);
   }
   {
     const int mel = 64 + (lane & 15), fr = (lane >> 4) & 1;
@@ -202,7 +215,59 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
     float acc = 0.f;
     for (int j = 0; j < ln; ++j) acc = fmaf(w[j], p[j], acc);
     if (lane < 32 && t0 + fr < T) out[((size_t)mel * T + t0 + fr) * C + c] = acc;
+    if (TRACK && lane < 32 && t0 + fr < T) mx = fmaxf(mx, acc);
   }
+  if (TRACK) {
+    // one atomic per block: waves through LDS (s_x was last read in pass 1, many barriers ago), then the bits of a value >= +0
+    mx = wave_max(mx);
+    if (lane == 0) s_x[wave] = mx;
+    __syncthreads();
+    if (tid == 0) {
+      mx = fmaxf(fmaxf(s_x[0], s_x[1]), fmaxf(s_x[2], s_x[3]));
+      atomicMax(mx_ws + smp * C + c, __float_as_uint(mx > 0.f ? mx : 0.f));
+    }
+  }
+}
+
+// ---- librosa.power_to_db(S, ref=np.max, amin=1e-10, top_db=80) per (sample, channel) map, as published:
+//        ls = 10 log10(max(amin, S)) - 10 log10(max(amin, max S));  ls = max(ls, max(ls) - top_db)
+// max(ls) is the value at the map's maximum, 10 log10(m) - 10 log10(m) = +0 exactly (log10f is monotone), so the floor is -80.
+// Each product and the difference are rounded on their own like numpy's three array operations (contraction is off), and both
+// entry points convert through this one function: their bits agree.
+#define MEL_AMIN 1e-10f
+#define MEL_TOPDB 80.f
+__device__ __forceinline__ float mel_power_to_db(float s, float ref) {
+#pragma clang fp contract(off)      // a fused 10 * a - (10 * b) leaves the product's rounding error, not 0, at the maximum (s == ref)
+  const float a = 10.f * log10f(fmaxf(MEL_AMIN, s));
+  const float b = 10.f * log10f(fmaxf(MEL_AMIN, ref));
+  const float ls = a - b;
+  return fmaxf(ls, 0.f - MEL_TOPDB);
+}
+
+// x[B, P, C] in place; mx_ws[B * C] = the bits of each map's maximum.  blockIdx.y = sample.
+__global__ __launch_bounds__(256) void power_to_db_kernel(float* __restrict__ x, size_t per_sample, int C,
+                                                          const unsigned int* __restrict__ mx_ws) {
+  const size_t b = blockIdx.y;
+  float* xs = x + b * per_sample;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (size_t)gridDim.x * 256)
+    xs[i] = mel_power_to_db(xs[i], __uint_as_float(mx_ws[b * C + (int)(i % C)]));
+}
+
+// mx_ws[b * C + c] = max(mx_ws[..], bits of max(0, x[b, :, c])): values below +0 (none in a power map) count as 0, like max(amin, S)
+__global__ __launch_bounds__(256) void power_max_kernel(const float* __restrict__ x, size_t per_sample, int C,
+                                                        unsigned int* __restrict__ mx_ws) {
+  __shared__ unsigned int s_m[MEL_DB_CMAX];
+  const size_t b = blockIdx.y;
+  const float* xs = x + b * per_sample;
+  for (int i = threadIdx.x; i < C; i += 256) s_m[i] = 0u;
+  __syncthreads();
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (size_t)gridDim.x * 256) {
+    const float v = xs[i];
+    if (v > 0.f) atomicMax(&s_m[(int)(i % C)], __float_as_uint(v));
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < C; i += 256)
+    if (s_m[i]) atomicMax(mx_ws + b * C + i, s_m[i]);
 }
 
 // 1 + n_samples / 256 frames (center=True), or MMD_EINVAL: reflect padding of 512 needs more than 512 samples
@@ -218,11 +283,57 @@ extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int cha
   const int T = mmd_melspec_frames(n_samples);
   if (T < 0) return MMD_EINVAL;
   const dim3 grid(cdiv(T, MEL_FPB), channels), block(256);
+  unsigned int* none = nullptr;
   if (wav_b)
-    hipLaunchKernelGGL(melspec_power_kernel<true>, grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, band_len,
-                       band_w, band_stride, out);
+    hipLaunchKernelGGL((melspec_power_kernel<true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, none);
   else
-    hipLaunchKernelGGL(melspec_power_kernel<false>, grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, band_len,
-                       band_w, band_stride, out);
+    hipLaunchKernelGGL((melspec_power_kernel<false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, none);
+  return mmd_check_launch();
+}
+
+static void power_to_db_launch(float* x, int batch, size_t per_sample, int C, const unsigned int* mx_ws, hipStream_t stream) {
+  const size_t blocks = (per_sample + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 4096 ? blocks : 4096), batch);
+  hipLaunchKernelGGL(power_to_db_kernel, grid, dim3(256), 0, stream, x, per_sample, C, mx_ws);
+}
+
+extern "C" int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples,
+                                 const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws,
+                                 float* out, hipStream_t stream) {
+  if (!wav_a || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 || batch > 65535)
+    return MMD_EINVAL;
+  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
+  const int T = mmd_melspec_frames(n_samples);
+  if (T < 0) return MMD_EINVAL;
+  const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
+  unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
+  if (db && hipMemsetAsync(mx, 0, sizeof(unsigned int) * (size_t)batch * channels, stream) != hipSuccess) return MMD_ELAUNCH;
+  if (wav_b && db)
+    hipLaunchKernelGGL((melspec_power_kernel<true, true>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx);
+  else if (wav_b)
+    hipLaunchKernelGGL((melspec_power_kernel<true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx);
+  else if (db)
+    hipLaunchKernelGGL((melspec_power_kernel<false, true>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx);
+  else
+    hipLaunchKernelGGL((melspec_power_kernel<false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx);
+  if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
+  return mmd_check_launch();
+}
+
+extern "C" int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_ws, hipStream_t stream) {
+  if (!x || !max_ws || batch <= 0 || batch > 65535 || h <= 0 || w <= 0 || channels <= 0 || channels > MEL_DB_CMAX) return MMD_EINVAL;
+  const size_t per_sample = (size_t)h * w * channels;
+  unsigned int* mx = reinterpret_cast<unsigned int*>(max_ws);
+  if (hipMemsetAsync(mx, 0, sizeof(unsigned int) * (size_t)batch * channels, stream) != hipSuccess) return MMD_ELAUNCH;
+  const size_t blocks = (per_sample + 255) / 256;
+  const dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), batch);
+  hipLaunchKernelGGL(power_max_kernel, grid, dim3(256), 0, stream, x, per_sample, channels, mx);
+  power_to_db_launch(x, batch, per_sample, channels, mx, stream);
   return mmd_check_launch();
 }

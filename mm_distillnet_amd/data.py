@@ -111,6 +111,16 @@ def collate(batch):
             list(items[5])]
 
 
+def cfg_bool(config, key, default: bool = False) -> bool:
+    """A boolean cfg key from a configparser section (strings, as getboolean reads them) or a plain dict (bools or strings)."""
+    v = config.get(key, default)
+    if isinstance(v, str):
+        if v.strip().lower() not in ("1", "yes", "true", "on", "0", "no", "false", "off"):
+            raise Exception(f"Unsupported {key} {v} provided")
+        return v.strip().lower() in ("1", "yes", "true", "on")
+    return bool(v)
+
+
 class RawSyntheticMultimodalDetection(Dataset):
     """Raw-format samples as the reference decodes them BEFORE its transforms: rgb uint8 [H,W,3], thermal uint16 [H,W]
     (sensor counts), depth uint8 [H,W,3], audio float32 [h,w,8] (8 dB-mel spectrograms stacked, MultimodalDetection.py:223-227).
@@ -126,6 +136,12 @@ class RawSyntheticMultimodalDetection(Dataset):
         if fmt not in ("spectrogram", "waveform"):
             raise Exception(f"Unsupported audio_format {fmt} provided")
         self.waveform = fmt == "waveform"
+        # extension key audio_db (absent -> False), with audio_format = waveform: DeviceInputPipeline converts the waveforms' power mel
+        # spectrograms to dB (power_to_db per microphone, what the student's stored input is: mp3_to_pkl.py:31-41).  The samples themselves
+        # do not change: they carry waveforms
+        self.audio_db = cfg_bool(config, 'audio_db', False)
+        if self.audio_db and not self.waveform:
+            raise Exception("audio_db = True needs audio_format = waveform (ready-made spectrogram stacks are dB already)")
         self.wave_samples = int(config.get('synthetic_wave_samples', 44100))
 
     def __len__(self):
@@ -174,8 +190,9 @@ class DeviceInputPipeline:
     MEAN = (0.485, 0.456, 0.406)
     STD = (0.229, 0.224, 0.225)
 
-    def __init__(self, image_size: int, device, ir_min: float = 20800.0, ir_max: float = 27000.0):
+    def __init__(self, image_size: int, device, ir_min: float = 20800.0, ir_max: float = 27000.0, audio_db: bool = False):
         from . import _lib
+        self.audio_db = bool(audio_db)      # cfg audio_db: "audio_wave" samples become dB maps before the resize; "audio" stacks are untouched
         self.call = _lib.call
         self.S = int(image_size)
         self.device = torch.device(device)
@@ -205,7 +222,7 @@ class DeviceInputPipeline:
     def submit(self, samples):
         """samples: list of per-sample dicts from RawSyntheticMultimodalDetection (or a real decoder with the same raw formats), or the
         stacked dict `collate_raw` makes of them.  A sample's audio is either "audio" [h,w,8] (ready-made mel stack: resized) or
-        "audio_wave" [8,N] (waveforms: mel spectrogram, then resized - `Audio2Spectogram` + `Resizer` on this stream)."""
+        "audio_wave" [8,N] (waveforms: mel spectrogram - in dB with audio_db -, then resized: `Audio2Spectogram` + `Resizer` on this stream)."""
         stacked = isinstance(samples, dict)
         B, S, call = (samples["rgb"].shape[0] if stacked else len(samples)), self.S, self.call
         if self._front is None and ("audio_wave" in samples if stacked else any("audio_wave" in smp for smp in samples)):
@@ -238,7 +255,7 @@ class DeviceInputPipeline:
                 call("mmd_image_letterbox", t, 1, H, W, 1, 1.0 / 255.0, None, None, 1, self.ir[0], self.ir[1], mm[b], S,
                      out["thermal"][b])
                 if "audio_wave" in smp:
-                    a = self._front.melspec(stage(("audio_wave", b), smp["audio_wave"])[None])[0]
+                    a = self._front.melspec(stage(("audio_wave", b), smp["audio_wave"])[None], db=self.audio_db)[0]
                 else:
                     a = stage(("audio", b), smp["audio"])
                 h, w, c = a.shape

@@ -1,0 +1,142 @@
+"""Audio-only inference: the trained student alone, from eight microphone waveforms (or their ready-made spectrogram stack) to boxes.
+
+What the reference's evaluation does with the student (get_predictions_multiteacher, src/utils/utils.py:1720-1830: eval-mode forward,
+EfficientDet_post_processing, logits_to_ground_truth) WITHOUT the three teachers it runs beside it: one frozen `Net` through the
+folded-BatchNorm kernels, the post-processing kernels the distillation step uses for its pseudo-labels (`postproc.decode_nms`), and
+the waveform front end (`audio.MelFrontEnd`, dB maps: the student's stored input is power_to_db of each microphone's mel spectrogram,
+mp3_to_pkl.py:31-41).  No teacher, no optimizer state, no gradient arena.
+
+After the first call for an input shape the whole chain - front end, forward, decode, NMS - is one captured hipGraph replayed on
+static input buffers, as `DistillEngine.capture` / `replay` do for the training step; a new shape captures anew."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .arch import NetSpec
+from .audio import MelFrontEnd
+from .engine import Net
+from .postproc import decode_nms, valid_class_mask
+from .store import Arena
+
+
+class AudioDetector:
+    def __init__(self, spec: NetSpec, device, image_size: int = 512, conf_threshold: float = 0.3, nms_threshold: float = 0.5,
+                 valid_prediction_ids: Sequence[int] = (6,), label_map: Optional[List[int]] = None, inclusive_nms: bool = False,
+                 cand_cap: int = 0, precision: str = "fp32"):
+        """The detection settings are the ones `DistillEngine` reads from its StepConfig (`from_step_config`).  cand_cap: rows per image
+        of the detection arrays; 0 = every anchor (the reference has no cap), so nothing can overflow."""
+        self.device = device
+        self.S = int(image_size)
+        self.conf_threshold, self.nms_threshold, self.inclusive_nms = float(conf_threshold), float(nms_threshold), bool(inclusive_nms)
+        self.net = Net(spec, device, trainable=False, arena=Arena(device, 256 << 20), precision=precision)      # activations only: no tape
+        self.front = MelFrontEnd(device)
+        self.ws = Arena(device, 64 << 20)         # post-processing workspaces (bump, reset per call)
+        lm = label_map if label_map is not None else list(range(spec.num_classes))
+        self.label_map = torch.tensor(lm, dtype=torch.int32, device=device)
+        self.valid_mask = valid_class_mask(valid_prediction_ids)
+        self.cand_cap = int(cand_cap)
+        self.cap = int(cand_cap)                  # 0: set to the anchor count at the first call
+        self.overflow = torch.zeros(1, dtype=torch.int32, device=device)
+        self._graphs: Dict[tuple, dict] = {}      # ("wave", B, N) / ("spec", B, S) -> static input, front-end buffers, graph, outputs
+        self.graph_replays = 0                    # calls served by a captured graph
+        self.use_graph = True                     # False: every call runs eagerly (timing the graph against the plain launch sequence)
+        self.last_cls: Optional[torch.Tensor] = None   # head outputs of the last call (views of the net's arena: valid until the next call)
+        self.last_reg: Optional[torch.Tensor] = None
+
+    @classmethod
+    def from_step_config(cls, spec: NetSpec, device, cfg) -> "AudioDetector":
+        """cfg: the `StepConfig` train.py / evaluate.py build from the cfg file (`train.step_config`)."""
+        return cls(spec, device, image_size=cfg.image_size, conf_threshold=cfg.conf_threshold, nms_threshold=cfg.nms_threshold,
+                   valid_prediction_ids=cfg.valid_prediction_ids, label_map=cfg.label_map, inclusive_nms=cfg.inclusive_nms,
+                   cand_cap=cfg.cand_cap, precision=cfg.precision)
+
+    def load(self, state):
+        """A student state_dict (a checkpoint's `c["state_dict"]`), as `DistillEngine.load` takes it for the student."""
+        self.net.load_state(state)
+
+    # ------------------------------------------------------------------ the chain
+    def _buffers(self, kind: str, shape) -> dict:
+        """static input (and, for waveforms, the front end's buffers) of one input shape"""
+        g = {"x": torch.empty(shape, device=self.device)}
+        if kind == "wave":
+            B, C, N = shape
+            g["mel"] = torch.empty(B, self.front.n_mels, self.front.n_frames(N), C, device=self.device)
+            g["max_ws"] = torch.empty(B * C, device=self.device)
+            g["audio"] = torch.empty(B, C, self.S, self.S, device=self.device)
+        return g
+
+    def _chain(self, kind: str, g: dict):
+        """Issues front end -> forward -> decode -> NMS on the current stream; nothing is allocated outside the bump arenas."""
+        S = self.S
+        if kind == "wave":
+            self.front.melspec_into(g["x"], None, True, g["max_ws"], g["mel"])
+            audio = self.front.resize_into(g["mel"], S, g["audio"])
+        else:
+            audio = g["x"]
+        B = audio.shape[0]
+        self.ws.reset()
+        self.net.begin_step()
+        cls, reg, _ = self.net.forward(audio, train=False)
+        A = cls.shape[1]
+        if self.cap <= 0:
+            self.cap = A
+        rows, cnt = decode_nms(self.ws, self.net, cls, reg, B, A, S, self.cap, self.conf_threshold, self.valid_mask, self.label_map,
+                               self.nms_threshold, self.inclusive_nms, self.overflow)
+        g.update(cls=cls, reg=reg, rows=rows, cnt=cnt)
+
+    def _rows(self, g: dict) -> List[np.ndarray]:
+        torch.cuda.synchronize()
+        self.last_cls, self.last_reg = g["cls"], g["reg"]
+        cnt = g["cnt"].cpu().tolist()
+        return [g["rows"][i, :cnt[i]].cpu().numpy() for i in range(len(cnt))]
+
+    @torch.no_grad()
+    def _detect(self, kind: str, x: torch.Tensor) -> List[np.ndarray]:
+        key = (kind,) + tuple(x.shape)
+        g = self._graphs.get(key)
+        if g is not None and self.use_graph and "graph" in g:
+            g["x"].copy_(x, non_blocking=True)
+            g["graph"].replay()
+            self.graph_replays += 1
+            return self._rows(g)
+        # no graph for this shape yet: run eagerly on the static buffers (the first run sizes the arenas), then capture
+        arenas = (self.ws, self.net.arena, self.net.zarena)
+        if g is None:
+            for a in arenas:
+                a.frozen = False                  # chunks are only ever appended: the graphs of earlier shapes stay valid
+            g = self._graphs[key] = self._buffers(kind, tuple(x.shape))
+        g["x"].copy_(x, non_blocking=True)
+        self._chain(kind, g)
+        out = self._rows(g)
+        for a in arenas:
+            a.frozen = True
+        if self.use_graph:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self._chain(kind, g)
+            torch.cuda.synchronize()
+            g["graph"] = graph
+        return out
+
+    def detect_spectrogram(self, audio: torch.Tensor) -> List[np.ndarray]:
+        """audio [B, 8, S, S] float32 on the device (dB mel maps resized to the image size: the student's input) -> per image float32
+        [n, 6] rows (x1, y1, x2, y2, score, label), the row format `DistillEngine.predict` returns for the student."""
+        if audio.dim() != 4 or audio.dtype != torch.float32 or audio.shape[1] != self.net.spec.in_channels or \
+                audio.shape[2] != self.S or audio.shape[3] != self.S:
+            raise ValueError("detect_spectrogram takes float32 [B, %d, %d, %d]" % (self.net.spec.in_channels, self.S, self.S))
+        return self._detect("spec", audio)
+
+    def detect(self, wave: torch.Tensor) -> List[np.ndarray]:
+        """wave [B, 8, N] float32 on the device (the microphones' waveforms at 44.1 kHz) -> rows as `detect_spectrogram`, through the
+        dB front end: `front.student_input(wave, None, S, db=True)`."""
+        if wave.dim() != 3 or wave.dtype != torch.float32 or wave.shape[1] != self.net.spec.in_channels:
+            raise ValueError("detect takes float32 [B, %d, N] waveforms" % self.net.spec.in_channels)
+        self.front.n_frames(wave.shape[2])        # raises on a waveform too short for the reflect padding
+        return self._detect("wave", wave)
+
+    def check_overflow(self):
+        if int(self.overflow.item()):
+            raise RuntimeError("detection capacity exceeded (cand_cap = %d rows per image; 0 = unlimited)" % self.cand_cap)

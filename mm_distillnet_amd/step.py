@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .arch import NetSpec, make_spec
 from .engine import Net, Feat, NONE, SWISH, pack_nets
+from .postproc import decode_nms, nms_workspace, valid_class_mask
 from .store import Arena
 
 call = _lib.call
@@ -105,9 +106,7 @@ class DistillEngine:
         nc = student_spec.num_classes
         lm = cfg.label_map if cfg.label_map is not None else list(range(nc))
         self.label_map = torch.tensor(lm, dtype=torch.int32, device=device)
-        self.valid_mask = 0
-        for i in cfg.valid_prediction_ids:
-            self.valid_mask |= 1 << int(i)
+        self.valid_mask = valid_class_mask(cfg.valid_prediction_ids)
         self.cap = int(cfg.cand_cap)     # 0: set to the anchor count at the first step
         self._eval: Optional[dict] = None  # the evaluation record between begin_eval and end_eval
         self.graph = None
@@ -215,8 +214,7 @@ class DistillEngine:
         return self.cap
 
     def _nms_ws(self, B: int, nmax: int):
-        n = int(_lib.LIB.load().mmd_nms_ws_floats(nmax))
-        return self.ws.alloc((B * n,)) if n else None
+        return nms_workspace(self.ws, B, nmax)
 
     def _merge(self, rows_t, cnt_t, B: int, augment: bool):
         """cross-teacher concat + NMS -> (boxes [B,G,5], nbox [B], G).  Up to 4 sources: the teachers in ModuleDict order, then the
@@ -232,18 +230,8 @@ class DistillEngine:
         return boxes, nbox, G
 
     def _pseudo_labels(self, net: Net, cls, reg, B: int, A: int, S: int):
-        ws, cap = self.ws, self._caps(A)
-        nc = net.spec.num_classes
-        score = ws.alloc((B * A,)); clsid = ws.alloc((B * A,), torch.uint8); flags = ws.alloc((B * A,), torch.uint8)
-        over = ws.alloc((B, cap)); cand = ws.alloc((B, cap, 6))
-        n_over = ws.alloc((B,), torch.int32); n_keep = ws.alloc((B,), torch.int32)
-        call("mmd_decode_filter", cls, reg, net.anchors(S), B, A, nc, float(self.cfg.conf_threshold), self.valid_mask, float(S),
-             score, clsid, flags, over, cand, n_over, n_keep, self.overflow, cap)
-        rows = ws.alloc((B, cap, 6)); cnt = ws.alloc((B,), torch.int32)
-        mask_ws = ws.alloc((B * 1024 * 16,), torch.int64)      # per teacher: teachers run concurrently
-        call("mmd_nms_teacher", cand, n_keep, over, self.label_map, float(self.cfg.nms_threshold),
-             1 if self.cfg.inclusive_nms else 0, float(S), B, rows, cnt, mask_ws, self.overflow, cap, self._nms_ws(B, cap))
-        return rows, cnt
+        return decode_nms(self.ws, net, cls, reg, B, A, S, self._caps(A), self.cfg.conf_threshold, self.valid_mask, self.label_map,
+                          self.cfg.nms_threshold, self.cfg.inclusive_nms, self.overflow)
 
     def _att_p(self) -> float:
         """exponent of the attention maps: cfg `p` for MTALoss; AttentionLoss is built with its default p = 2 upstream (src/utils/utils.py)"""

@@ -116,12 +116,18 @@ def load_states(cfg, coef=2):
         else:
             logger.warning("teacher weights %s not found: using deterministic synthetic weights", _MOD_PATH[m])
         tstates[m] = st
+    sspec, sstate = load_student_state(coef)
+    return sspec, sstate, tspecs, tstates
+
+
+def load_student_state(coef=2):
+    """The student half of load_states: the 8-channel spec and its reference weight file when present, synthetic weights otherwise."""
     sspec = make_spec(coef, 8)
     sstate = synth_state(sspec, seed=7)
     for pth in ["trained_models/yet-another-efficientdet-d2.pth", "trained_models/yet-another-efficientdet-d2-embedding.pth"]:
         if os.path.exists(pth):
             sstate.update(filter_state_dict({k: v.shape for k, v in sstate.items()}, torch.load(pth, map_location="cpu")))
-    return sspec, sstate, tspecs, tstates
+    return sspec, sstate
 
 
 class AsyncScalars:
@@ -202,8 +208,10 @@ def main(argv=None):
     raw = cfg.get("input_pipeline", "tensor") == "raw"
     Set = RawSyntheticMultimodalDetection if raw else SyntheticMultimodalDetection
     train_set, val_set = Set(cfg, "train"), Set(cfg, "val")
-    pipe = DeviceInputPipeline(cfg.getint("image_size"), dev) if raw else TensorInputPipeline(dev)
-    vpipe = DeviceInputPipeline(cfg.getint("image_size"), dev) if raw else None
+    # audio_db (extension key, absent -> False; with audio_format = waveform): the pipeline hands the student dB mel maps, not power
+    audio_db = cfg.getboolean("audio_db", False)
+    pipe = DeviceInputPipeline(cfg.getint("image_size"), dev, audio_db=audio_db) if raw else TensorInputPipeline(dev)
+    vpipe = DeviceInputPipeline(cfg.getint("image_size"), dev, audio_db=audio_db) if raw else None
     collate_fn = collate_raw if raw else collate
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, num_replicas=world, rank=rank) if world > 1 else None
     loader = torch.utils.data.DataLoader(train_set, batch_size=cfg.getint("batch_size"), shuffle=sampler is None,
