@@ -2,6 +2,7 @@
 """Audio-only detection with the trained student: a checkpoint plus microphone waveforms in, boxes out.
 
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
+                     [--window_s SECONDS [--hop_s SECONDS] [--batch N]]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -9,6 +10,11 @@ image_size: what mp3_to_pkl.py:31-41, `MultimodalDetection.__getitem__` and `Res
 eval-mode forward and the post-processing of the reference's evaluation (score > conf_threshold, class filter, NMS).  The detection
 settings (image_size, conf_threshold, nms_threshold, valid_labels, precision, compound_coef) are read from the cfg file like train.py
 and evaluate.py read them.  No teacher is built or loaded.  Output: one CSV row per box, columns clip,x1,y1,x2,y2,score,label.
+
+With --window_s the input is ONE recording (a `.wav`, or a `.npy` of shape [8, N]) and the detector slides over it on the device
+(`AudioDetector.detect_stream`): windows of round(window_s * 44100) samples every round(hop_s * 44100) samples (hop_s defaults to
+window_s), --batch windows per launch sequence; a tail shorter than a window is dropped.  The CSV then has the columns
+window,t_start_s,x1,y1,x2,y2,score,label with t_start_s = window * hop / 44100.
 """
 import argparse
 import csv
@@ -30,6 +36,7 @@ from mm_distillnet_amd.detector import AudioDetector  # noqa: E402
 
 CHANNELS, SAMPLE_RATE = 8, 44100
 COLUMNS = ("clip", "x1", "y1", "x2", "y2", "score", "label")
+STREAM_COLUMNS = ("window", "t_start_s", "x1", "y1", "x2", "y2", "score", "label")
 
 
 def read_npy(path: str) -> np.ndarray:
@@ -77,6 +84,25 @@ def write_csv(path: str, rows_per_clip) -> int:
     return n
 
 
+def write_stream_csv(path: str, rows, window, hop: int) -> int:
+    """rows [R, 6] / window [R] of `AudioDetector.detect_stream` at a hop of `hop` samples"""
+    rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(STREAM_COLUMNS)
+        for w, r in zip(window.tolist(), rows):
+            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r])
+    return len(rows)
+
+
+def stream_sizes(window_s: float, hop_s, n_total: int):
+    """-> (win_len, hop, number of windows) in samples; raises ValueError as `stream_window_starts` does"""
+    from mm_distillnet_amd.audio import stream_window_starts
+    win_len = int(round(window_s * SAMPLE_RATE))
+    hop = win_len if hop_s is None else int(round(hop_s * SAMPLE_RATE))
+    return win_len, hop, len(stream_window_starts(n_total, win_len, hop))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_file", required=True)
@@ -84,15 +110,28 @@ def main(argv=None):
     ap.add_argument("--input", required=True)
     ap.add_argument("--output", required=True)
     ap.add_argument("--overwrite", type=str, default=None)
+    ap.add_argument("--window_s", type=float, default=None, help="slide a window of this many seconds over ONE recording")
+    ap.add_argument("--hop_s", type=float, default=None, help="seconds between window starts (default: --window_s)")
+    ap.add_argument("--batch", type=int, default=8, help="windows per launch sequence (with --window_s)")
     a = ap.parse_args(argv)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     waves = read_input(a.input)
+    if a.window_s is not None:
+        if waves.shape[0] != 1:
+            raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
+                             f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
+        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, waves.shape[2])
     torch.cuda.set_device(0)
     dev = "cuda:0"
     sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
+    if a.window_s is not None:
+        rows, window = det.detect_stream(torch.from_numpy(waves[0]).to(dev), win_len, hop, batch=a.batch)
+        n = write_stream_csv(a.output, rows, window, hop)
+        print("%d windows, %d boxes -> %s" % (n_win, n, a.output))
+        return rows, window
     rows = det.detect(torch.from_numpy(waves).to(dev))
     det.check_overflow()
     n = write_csv(a.output, rows)

@@ -562,7 +562,7 @@ int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long
 // then max(ls, max(ls) - 80) - in fp32 with each product and the difference rounded on its own.  librosa is not in the reference tree:
 // the rule is restated and pinned to tests/melspec_db_ref.py, parity with librosa's power_to_db itself is UNPINNED.  The maxima go
 // through max_ws[batch * channels] (any 4-byte words; null allowed for db = 0) as unsigned atomic maxima of the float bits (power is
-// >= +0), so they do not depend on the order of arrival: two calls give the same bits.  Launch sequence for db = 1: one memset node on
+// >= +0), so they do not depend on the order of arrival: two calls give the same bits.  Launch sequence for db = 1: one zero-fill launch on
 // max_ws, the spectrogram launch, one elementwise launch.  max_ws and out need no zeroing; no allocation, no host synchronisation
 // (capturable in a hipGraph).  -22 on null pointers / bad sizes / db outside {0, 1} before any launch.
 int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
@@ -570,10 +570,37 @@ int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int cha
 // The same power_to_db(S, ref=np.max) (mp3_to_pkl.py:31-41), in place, for a ready-made POWER stack x[batch, h, w, channels] (what
 // Audio2Spectogram, src/datasets/transformations.py:251-266, hands on): the maximum is again per (sample, channel) map.  On the db = 0
 // output of mmd_melspec_batch it gives the bits of db = 1.  Values below +0 count as 0 in the maximum (max(1e-10, .) floors them anyway).
-// One memset node on max_ws[batch * channels] (needs no zeroing), one maximum launch, one elementwise launch; channels <= 1024.
+// One zero-fill launch on max_ws[batch * channels] (needs no zeroing), one maximum launch, one elementwise launch; channels <= 1024.
 // Restated from the published rule, pinned to tests/melspec_db_ref.py; parity with librosa's power_to_db itself is UNPINNED.
 // -22 on null pointers / bad sizes before any launch.
 int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_ws, hipStream_t stream);
+
+// mmd_melspec_batch over overlapping windows read straight out of ONE recording (streaming detection, AudioDetector.detect_stream;
+// the melspectrogram call is merge_audios', src/datasets/MultimodalDetection.py:329-353, the dB map mp3_to_pkl.py:31-41's):
+// wav[channels, n_total], win_start[batch] (DEVICE int64 sample offsets, so one captured hipGraph serves every group of a recording),
+// win_len samples per window -> out[batch, 80, T, channels], T = mmd_melspec_frames(win_len).  Window b is exactly the clip
+// wav[:, win_start[b] : win_start[b] + win_len]: the reflect padding happens at the window's own two ends (edge sample not repeated)
+// and never reads the recording's samples outside the window, nor before wav or past n_total; the dB maximum is per (window, channel).
+// For db = 0 and db = 1 the output is bit for bit what mmd_melspec_batch gives on the materialised [batch, channels, win_len] stack of
+// those slices (one kernel body; the window offset enters the base pointer only).  The table's contents cannot be checked on the
+// host: a start outside [0, n_total - win_len] is the CALLER'S ERROR (the kernel clamps it into that range, so such a window is the
+// wrong one but no read leaves the recording).  Launch sequence, max_ws[batch * channels] and out as mmd_melspec_batch: they need no
+// zeroing, two calls give the same bits, no allocation, no host synchronisation.  -22 before any launch on null pointers, batch < 1,
+// channels < 1, win_len <= 512 (too short for the padding), win_len > n_total, a bad band_stride or db outside {0, 1}.
+int mmd_melspec_windows(const float* wav, int channels, long long n_total, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
+
+// ---- device-side detection record (csrc/stream.hip): the rows mmd_nms_teacher leaves for a group of windows, appended behind every
+// group with one host copy at the end of the recording (the shape of mmd_eval_match's record).
+// rows[B, cap_img, 6] / cnt[B]: decode / NMS output (counts are clamped to 0 .. cap_img).  ctl[2] (DEVICE) = {n_valid, first_window}:
+// the rows of images 0 .. n_valid-1 are appended at *rec_count in image order, then the NMS output order within an image - the order
+// AudioDetector.detect returns - and each appended row i gets rec_win[i] = first_window + image.  Images at or behind n_valid
+// contribute nothing, whatever their counts hold (n_valid is clamped to 0 .. B).  rec_rows[rec_cap, 6], rec_win[rec_cap]; *rec_count
+// (one device int32) is zeroed by the caller once per stream, and so is *rec_overflow; neither record array needs zeroing.  Offsets
+// are an exclusive scan of the B counts inside the kernel (one block, no atomics): two runs give the same record.  *rec_count advances
+// by the TRUE total even behind rec_cap: rows that do not fit are not written (nothing behind rec_cap is touched) and *rec_overflow = 1
+// (sticky), so the host can say how many rows were needed.  -22 before any launch on null pointers, B < 1, B > 1024, cap_img < 1,
+// rec_cap < 1.
+int mmd_det_record_append(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, float* rec_rows, int* rec_win, int rec_cap, int* rec_count, int* rec_overflow, hipStream_t stream);
 
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction

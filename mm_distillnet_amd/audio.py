@@ -55,6 +55,20 @@ def mel_bands(sr: int = 44100, n_fft: int = N_FFT, n_mels: int = 80):
     return start, length, band
 
 
+def stream_window_starts(n_total: int, win_len: int, hop: int) -> list:
+    """Sample offsets of the windows streaming detection cuts out of a recording of n_total samples: window w starts at w * hop, for
+    w = 0 .. W-1 with W = 1 + (n_total - win_len) // hop.  A tail shorter than a full window is dropped.  hop is any positive number of
+    samples (it may exceed win_len: the windows then leave gaps)."""
+    n_total, win_len, hop = int(n_total), int(win_len), int(hop)
+    if hop < 1:
+        raise ValueError(f"hop = {hop}: the windows must advance by at least one sample")
+    if win_len <= N_FFT // 2:
+        raise ValueError(f"a window of {win_len} samples is too short for the reflect padding (more than {N_FFT // 2} needed)")
+    if n_total < win_len:
+        raise ValueError(f"a recording of {n_total} samples is shorter than one window of {win_len}")
+    return [w * hop for w in range(1 + (n_total - win_len) // hop)]
+
+
 class MelFrontEnd:
     """Holds the band-form filter bank on `device`; every call runs on the current stream and allocates only its result."""
 
@@ -86,6 +100,15 @@ class MelFrontEnd:
         self.call("mmd_melspec_batch", wav_a, wav_b, B, C, N, self.start, self.length, self.band, self.stride, 1 if db else 0, max_ws, out)
         return out
 
+    def melspec_windows_into(self, wav, win_start, win_len: int, db: bool, max_ws, out):
+        """`melspec_into` for windows read straight out of ONE recording (`mmd_melspec_windows`): wav [C, n_total], win_start int64 [B]
+        on the device (each in [0, n_total - win_len]: the caller's duty), out [B, 80, n_frames(win_len), C].  The bits are those of
+        `melspec_into` on the stacked slices wav[:, s : s + win_len]."""
+        C, n_total = wav.shape
+        self.call("mmd_melspec_windows", wav, C, n_total, win_start, win_start.shape[0], int(win_len), self.start, self.length, self.band,
+                  self.stride, 1 if db else 0, max_ws, out)
+        return out
+
     def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None, db: bool = False) -> torch.Tensor:
         """[B, C, N] float32 device waveforms (the mean of the two when wav_b is given) -> mel spectrograms [B, 80, T, C], the whole batch
         in one launch sequence (`mmd_melspec_batch`).  db=False: power, as merge_audios returns it.  db=True: the dB map of the student's
@@ -111,7 +134,7 @@ class MelFrontEnd:
 
     def student_input(self, wav_a: torch.Tensor, wav_b, S: int, db: bool = False) -> torch.Tensor:
         """-> [B, C, S, S]: the mel stacks (power, or dB with db=True) resized with cv2.INTER_CUBIC's rule (`mmd_resize_cubic_batch`): at
-        most three launches and one memset node for the whole batch.  S is the step's image_size; upstream's merge_audios hard-codes
+        most four launches (one a zero fill of the maxima workspace) for the whole batch.  S is the step's image_size; upstream's merge_audios hard-codes
         common_size = 768 (:330), the image_size of its shipped cfg."""
         mel = self.melspec(wav_a, wav_b, db)
         B, M, T, C = mel.shape

@@ -86,22 +86,35 @@ __device__ __forceinline__ void mel_dft16(float2 v[16]) {
 __device__ __forceinline__ int mel_pad(int i) { return i + (i >> 4); }
 
 // blockIdx.z = the sample of a batch ([B, C, N] waveforms -> [B, 80, T, C]); TRACK: also the block's maximum into mx_ws[sample * C + c]
-template <bool MIX, bool TRACK>
+// WIN (mmd_melspec_windows): sample b is the window wav_a[:, win_start[b] : win_start[b] + N] of ONE recording wav_a[C, n_total]; only
+// the base pointer differs - every index below stays in window coordinates 0 .. N-1, so the reflection sees the window's own two ends
+// and the bits are those of the materialised [B, C, N] stack.  The start is clamped into [0, n_total - N]: a bad table reads the wrong
+// window, never outside the recording.
+template <bool MIX, bool TRACK, bool WIN>
 __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restrict__ wav_a, const float* __restrict__ wav_b, long long N,
                                                             int T, int C, const int* __restrict__ band_start,
                                                             const int* __restrict__ band_len, const float* __restrict__ band_w,
-                                                            int band_stride, float* __restrict__ out, unsigned int* __restrict__ mx_ws) {
+                                                            int band_stride, float* __restrict__ out, unsigned int* __restrict__ mx_ws,
+                                                            const long long* __restrict__ win_start, long long n_total) {
   __shared__ float s_x[MEL_STAGE];
   __shared__ float2 s_z[4][MEL_ZROW];
   __shared__ float s_w[MEL_WMAX];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = blockIdx.y, f0 = blockIdx.x * MEL_FPB;
   const size_t smp = blockIdx.z;
-  const float* pa = wav_a + (smp * C + c) * (size_t)N;
+  const float* pa;
+  if (WIN) {
+    long long w0 = win_start[smp];
+    w0 = w0 < 0 ? 0 : (w0 > n_total - N ? n_total - N : w0);
+    pa = wav_a + (size_t)c * (size_t)n_total + (size_t)w0;
+  } else {
+    pa = wav_a + (smp * C + c) * (size_t)N;
+  }
   const float* pb = MIX ? wav_b + (smp * C + c) * (size_t)N : nullptr;
   out += smp * MEL_NMEL * (size_t)T * C;
 
-  // ---- stage the block's samples: padded position p <-> sample p - 512, reflected at both ends, then clamped (frames >= T only)
+  // ---- stage the block's samples: padded position p <-> sample p - 512, reflected at both ends, then clamped (frames >= T only);
+  //      WIN: s is an index into the window (pa points at its first sample), so 0 <= s <= N - 1 keeps every read inside it
   const long long base = (long long)f0 * MEL_HOP - MEL_NFFT / 2;
 #pragma unroll
   for (int it = 0; it < MEL_STAGE / 256; ++it) {
@@ -285,12 +298,20 @@ extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int cha
   const dim3 grid(cdiv(T, MEL_FPB), channels), block(256);
   unsigned int* none = nullptr;
   if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, none);
+    hipLaunchKernelGGL((melspec_power_kernel<true, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
   else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, none);
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
   return mmd_check_launch();
+}
+
+// The maxima workspace is cleared by the project's zero-fill KERNEL (mmd_zero_bytes, optim.hip), not by hipMemsetAsync: a memset node
+// recorded by stream capture is not reliably executed on later replays of the graph (optim.hip found the same on the accumulator arenas).
+// Seen here as: from the second replay of AudioDetector's waveform graph on, max_ws held stale or foreign words in front of the
+// atomicMax, the dB reference was wrong and detect() returned other rows than the eager run on the same clip.
+static int mel_zero_max(unsigned int* mx, int batch, int channels, hipStream_t stream) {
+  return mmd_zero_bytes(mx, sizeof(unsigned int) * (size_t)batch * channels, stream);
 }
 
 static void power_to_db_launch(float* x, int batch, size_t per_sample, int C, const unsigned int* mx_ws, hipStream_t stream) {
@@ -309,19 +330,42 @@ extern "C" int mmd_melspec_batch(const float* wav_a, const float* wav_b, int bat
   if (T < 0) return MMD_EINVAL;
   const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
   unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
-  if (db && hipMemsetAsync(mx, 0, sizeof(unsigned int) * (size_t)batch * channels, stream) != hipSuccess) return MMD_ELAUNCH;
+  if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
   if (wav_b && db)
-    hipLaunchKernelGGL((melspec_power_kernel<true, true>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx);
+    hipLaunchKernelGGL((melspec_power_kernel<true, true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx);
+    hipLaunchKernelGGL((melspec_power_kernel<true, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx);
+    hipLaunchKernelGGL((melspec_power_kernel<false, true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx);
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
+  if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
+  return mmd_check_launch();
+}
+
+extern "C" int mmd_melspec_windows(const float* wav, int channels, long long n_total, const long long* win_start, int batch,
+                                   long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride,
+                                   int db, float* max_ws, float* out, hipStream_t stream) {
+  if (!wav || !win_start || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 ||
+      batch > 65535)
+    return MMD_EINVAL;
+  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
+  const int T = mmd_melspec_frames(win_len);
+  if (T < 0 || win_len > n_total) return MMD_EINVAL;
+  const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
+  unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
+  const float* none = nullptr;
+  if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
+  if (db)
+    hipLaunchKernelGGL((melspec_power_kernel<false, true, true>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, win_start, n_total);
+  else
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, true>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
+                       band_len, band_w, band_stride, out, mx, win_start, n_total);
   if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
   return mmd_check_launch();
 }
@@ -330,7 +374,7 @@ extern "C" int mmd_power_to_db(float* x, int batch, int h, int w, int channels, 
   if (!x || !max_ws || batch <= 0 || batch > 65535 || h <= 0 || w <= 0 || channels <= 0 || channels > MEL_DB_CMAX) return MMD_EINVAL;
   const size_t per_sample = (size_t)h * w * channels;
   unsigned int* mx = reinterpret_cast<unsigned int*>(max_ws);
-  if (hipMemsetAsync(mx, 0, sizeof(unsigned int) * (size_t)batch * channels, stream) != hipSuccess) return MMD_ELAUNCH;
+  if (mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
   const size_t blocks = (per_sample + 255) / 256;
   const dim3 grid((unsigned)(blocks < 1024 ? blocks : 1024), batch);
   hipLaunchKernelGGL(power_max_kernel, grid, dim3(256), 0, stream, x, per_sample, channels, mx);

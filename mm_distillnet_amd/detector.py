@@ -7,7 +7,11 @@ the waveform front end (`audio.MelFrontEnd`, dB maps: the student's stored input
 mp3_to_pkl.py:31-41).  No teacher, no optimizer state, no gradient arena.
 
 After the first call for an input shape the whole chain - front end, forward, decode, NMS - is one captured hipGraph replayed on
-static input buffers, as `DistillEngine.capture` / `replay` do for the training step; a new shape captures anew."""
+static input buffers, as `DistillEngine.capture` / `replay` do for the training step; a new shape captures anew.
+
+`detect_stream` slides that chain over one long recording that stays on the device: the front end reads the overlapping windows straight
+out of it (`mmd_melspec_windows`), a device-side record collects every group's rows (`mmd_det_record_append`, csrc/stream.hip), and the
+host synchronises and copies once, at the end."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -16,7 +20,8 @@ import numpy as np
 import torch
 
 from .arch import NetSpec
-from .audio import MelFrontEnd
+from . import _lib
+from .audio import MelFrontEnd, stream_window_starts
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -43,6 +48,9 @@ class AudioDetector:
         self._graphs: Dict[tuple, dict] = {}      # ("wave", B, N) / ("spec", B, S) -> static input, front-end buffers, graph, outputs
         self.graph_replays = 0                    # calls served by a captured graph
         self.use_graph = True                     # False: every call runs eagerly (timing the graph against the plain launch sequence)
+        self._stream: Optional[dict] = None       # detect_stream's buffers and graph: ONE recording at a time (the graph bakes its address in)
+        self.stream_captures = 0                  # graphs detect_stream captured
+        self.stream_replays = 0                   # groups of windows detect_stream served by a captured graph
         self.last_cls: Optional[torch.Tensor] = None   # head outputs of the last call (views of the net's arena: valid until the next call)
         self.last_reg: Optional[torch.Tensor] = None
 
@@ -76,6 +84,11 @@ class AudioDetector:
             audio = self.front.resize_into(g["mel"], S, g["audio"])
         else:
             audio = g["x"]
+        self._tail(audio, g)
+
+    def _tail(self, audio: torch.Tensor, g: dict):
+        """forward -> decode -> NMS of a ready student input [B, 8, S, S]"""
+        S = self.S
         B = audio.shape[0]
         self.ws.reset()
         self.net.begin_step()
@@ -136,6 +149,110 @@ class AudioDetector:
             raise ValueError("detect takes float32 [B, %d, N] waveforms" % self.net.spec.in_channels)
         self.front.n_frames(wave.shape[2])        # raises on a waveform too short for the reflect padding
         return self._detect("wave", wave)
+
+    # ------------------------------------------------------------------ streaming
+    STREAM_ROWS_PER_WINDOW = 256      # default record size per window when cand_cap = 0 (unlimited rows per image)
+
+    def _stream_chain(self, g: dict):
+        """One group of windows: front end on the windows the control row names -> forward -> decode -> NMS -> append to the record."""
+        self.front.melspec_windows_into(g["wave"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
+        audio = self.front.resize_into(g["mel"], self.S, g["audio"])
+        self._tail(audio, g)
+        B = audio.shape[0]
+        _lib.call("mmd_det_record_append", g["rows"], g["cnt"], B, g["rows"].shape[1], g["ctl"], g["rec_rows"], g["rec_win"],
+                  g["rec_cap"], g["rec_state"][0:1], g["rec_state"][1:2])
+
+    @torch.no_grad()
+    def detect_stream(self, wave: torch.Tensor, win_len: int, hop: int, batch: int = 8, rec_cap: Optional[int] = None):
+        """Slides the detector over one recording: wave float32 [8, n_total] on the device -> (rows float32 [R, 6], window int32 [R]),
+        numpy arrays: the rows `detect` gives each window, in window order, and the index of each row's window.
+
+        Window w is wave[:, w * hop : w * hop + win_len] for w = 0 .. W-1, W = 1 + (n_total - win_len) // hop
+        (`audio.stream_window_starts`); a tail shorter than a full window is DROPPED.  hop is any positive number of samples.  The whole
+        recording is resident on the device (8 channels of float32 at 44.1 kHz: 1.4 MB per second); recordings that do not fit are not
+        supported.
+
+        The windows run in groups of `batch`; the last, shorter group repeats its last window up to `batch` and only its real windows
+        are recorded, so one shape - and one captured graph - serves the recording.  Per group the host queues a device-to-device copy
+        of the group's row of a control table (the window starts, the number of real windows, the first window's index; uploaded once
+        per call) and the chain front end -> resize -> forward -> decode -> NMS -> record append; nothing waits for the host until the
+        last group is queued.  A group's rows have the bits `detect` gives the stack of that group's windows.
+
+        rec_cap: rows the device record holds.  Default: W * cand_cap; with cand_cap = 0 (unlimited rows per image) W *
+        STREAM_ROWS_PER_WINDOW (256).  A recording with more rows raises RuntimeError naming the rows needed: pass that as rec_cap.
+
+        The graph bakes in the recording's address: it is kept for (win_len, batch, image size, wave.data_ptr(), n_total) and rec_cap,
+        and captured again when any of them changes; the detector holds the buffers of one recording at a time."""
+        C = self.net.spec.in_channels
+        if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[0] != C or not wave.is_cuda or not wave.is_contiguous():
+            raise ValueError("detect_stream takes one contiguous float32 [%d, n_total] recording on the device" % C)
+        win_len, hop, batch, n_total = int(win_len), int(hop), int(batch), int(wave.shape[1])
+        if batch < 1 or batch > 1024:
+            raise ValueError("detect_stream: batch = %d (1 .. 1024)" % batch)
+        starts = stream_window_starts(n_total, win_len, hop)
+        W = len(starts)
+        if rec_cap is None:
+            rec_cap = W * (self.cand_cap if self.cand_cap > 0 else self.STREAM_ROWS_PER_WINDOW)
+        rec_cap = int(rec_cap)
+        if rec_cap < 1 or rec_cap > 0x7fffffff:
+            raise ValueError("detect_stream: rec_cap = %d" % rec_cap)
+        # control table, one row per group: int64 starts[batch], then {n_valid, first_window} as two int32 in the last word
+        G = (W + batch - 1) // batch
+        table = np.empty((G, batch + 1), np.int64)
+        tail = table.view(np.int32).reshape(G, 2 * (batch + 1))[:, 2 * batch:]
+        for gi in range(G):
+            real = starts[gi * batch:(gi + 1) * batch]
+            table[gi, :batch] = real + [real[-1]] * (batch - len(real))
+            tail[gi] = (len(real), gi * batch)
+        table = torch.from_numpy(table).to(self.device)
+
+        key = (win_len, batch, self.S, wave.data_ptr(), n_total, rec_cap)
+        arenas = (self.ws, self.net.arena, self.net.zarena)
+        g = self._stream
+        if g is None or g["key"] != key:
+            self._stream = g = None               # the old recording's buffers go before the new ones come
+            for a in arenas:
+                a.frozen = False                  # chunks are only ever appended: the graphs of `_detect` stay valid
+            cur = torch.zeros(batch + 1, dtype=torch.int64, device=self.device)
+            g = {"key": key, "wave": wave, "win_len": win_len, "rec_cap": rec_cap, "cur": cur, "starts": cur[:batch],
+                 "ctl": cur[batch:].view(torch.int32),
+                 "mel": torch.empty(batch, self.front.n_mels, self.front.n_frames(win_len), C, device=self.device),
+                 "max_ws": torch.empty(batch * C, device=self.device),
+                 "audio": torch.empty(batch, C, self.S, self.S, device=self.device),
+                 "rec_rows": torch.empty(rec_cap, 6, device=self.device),
+                 "rec_win": torch.empty(rec_cap, dtype=torch.int32, device=self.device),
+                 "rec_state": torch.zeros(2, dtype=torch.int32, device=self.device)}       # {rec_count, overflow flag}
+            self._stream = g
+        if self.use_graph and "graph" not in g:
+            # a warm-up group sizes the arenas (what it appends is dropped: the record's state is zeroed below), then the capture
+            g["cur"].copy_(table[0], non_blocking=True)
+            self._stream_chain(g)
+            torch.cuda.synchronize()
+            for a in arenas:
+                a.frozen = True
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self._stream_chain(g)
+            torch.cuda.synchronize()
+            g["graph"] = graph
+            self.stream_captures += 1
+        g["rec_state"].zero_()
+        for gi in range(G):
+            g["cur"].copy_(table[gi], non_blocking=True)
+            if self.use_graph:
+                g["graph"].replay()
+                self.stream_replays += 1
+            else:
+                self._stream_chain(g)
+        torch.cuda.synchronize()
+        for a in arenas:
+            a.frozen = True
+        self.last_cls, self.last_reg = g["cls"], g["reg"]
+        n, over = g["rec_state"].cpu().tolist()
+        self.check_overflow()
+        if over or n > rec_cap:
+            raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, rec_cap))
+        return g["rec_rows"][:n].cpu().numpy(), g["rec_win"][:n].cpu().numpy()
 
     def check_overflow(self):
         if int(self.overflow.item()):
