@@ -2,7 +2,8 @@
 """Audio-only detection with the trained student: a checkpoint plus microphone waveforms in, boxes out.
 
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
-                     [--window_s SECONDS [--hop_s SECONDS] [--batch N]]
+                     [--window_s SECONDS [--hop_s SECONDS] [--batch N]
+                      [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -15,6 +16,11 @@ With --window_s the input is ONE recording (a `.wav`, or a `.npy` of shape [8, N
 (`AudioDetector.detect_stream`): windows of round(window_s * 44100) samples every round(hop_s * 44100) samples (hop_s defaults to
 window_s), --batch windows per launch sequence; a tail shorter than a window is dropped.  The CSV then has the columns
 window,t_start_s,x1,y1,x2,y2,score,label with t_start_s = window * hop / 44100.
+
+With --track (only with --window_s) the boxes of consecutive windows are linked into tracks on the device
+(`AudioDetector.track_stream`: greedy IoU association with a constant-velocity model) and the CSV gains a last column `track`: the id of
+the row's track - ids start at 0 and rise in order of birth - or -1.  --track_iou: smallest IoU of a pairing (0.3); --track_beta: velocity
+gain (0.5); --track_max_age: windows a track survives without a box (2); --track_max: live tracks at a time (64, at most 256).
 """
 import argparse
 import csv
@@ -37,6 +43,7 @@ from mm_distillnet_amd.detector import AudioDetector  # noqa: E402
 CHANNELS, SAMPLE_RATE = 8, 44100
 COLUMNS = ("clip", "x1", "y1", "x2", "y2", "score", "label")
 STREAM_COLUMNS = ("window", "t_start_s", "x1", "y1", "x2", "y2", "score", "label")
+TRACK_COLUMNS = STREAM_COLUMNS + ("track",)
 
 
 def read_npy(path: str) -> np.ndarray:
@@ -95,6 +102,20 @@ def write_stream_csv(path: str, rows, window, hop: int) -> int:
     return len(rows)
 
 
+def write_track_csv(path: str, rows, window, track, hop: int) -> int:
+    """rows [R, 6] / window [R] / track [R] of `AudioDetector.track_stream` at a hop of `hop` samples"""
+    rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
+    track = np.asarray(track).reshape(-1)
+    if len(track) != len(rows) or len(window) != len(rows):
+        raise ValueError("write_track_csv: %d rows, %d windows, %d track ids" % (len(rows), len(window), len(track)))
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(TRACK_COLUMNS)
+        for w, r, t in zip(window.tolist(), rows, track.tolist()):
+            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + [t])
+    return len(rows)
+
+
 def stream_sizes(window_s: float, hop_s, n_total: int):
     """-> (win_len, hop, number of windows) in samples; raises ValueError as `stream_window_starts` does"""
     from mm_distillnet_amd.audio import stream_window_starts
@@ -113,7 +134,18 @@ def main(argv=None):
     ap.add_argument("--window_s", type=float, default=None, help="slide a window of this many seconds over ONE recording")
     ap.add_argument("--hop_s", type=float, default=None, help="seconds between window starts (default: --window_s)")
     ap.add_argument("--batch", type=int, default=8, help="windows per launch sequence (with --window_s)")
+    ap.add_argument("--track", action="store_true", help="link the boxes of consecutive windows into tracks (with --window_s)")
+    ap.add_argument("--track_iou", type=float, default=0.3, help="smallest IoU at which a track and a box are paired")
+    ap.add_argument("--track_beta", type=float, default=0.5, help="velocity gain of the constant-velocity model")
+    ap.add_argument("--track_max_age", type=int, default=2, help="windows a track survives without a box")
+    ap.add_argument("--track_max", type=int, default=64, help="live tracks at a time (1 .. 256)")
     a = ap.parse_args(argv)
+    track = None
+    if a.track:
+        if a.window_s is None:
+            raise ValueError("--track links the boxes of consecutive windows: it needs --window_s")
+        from mm_distillnet_amd.tracker import TrackConfig
+        track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     waves = read_input(a.input)
     if a.window_s is not None:
@@ -127,6 +159,11 @@ def main(argv=None):
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
+    if track is not None:
+        rows, window, ids = det.track_stream(torch.from_numpy(waves[0]).to(dev), win_len, hop, batch=a.batch, track=track)
+        n = write_track_csv(a.output, rows, window, ids, hop)
+        print("%d windows, %d boxes, %d tracks -> %s" % (n_win, n, len(np.unique(ids[ids >= 0])), a.output))
+        return rows, window, ids
     if a.window_s is not None:
         rows, window = det.detect_stream(torch.from_numpy(waves[0]).to(dev), win_len, hop, batch=a.batch)
         n = write_stream_csv(a.output, rows, window, hop)

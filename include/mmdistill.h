@@ -602,6 +602,26 @@ int mmd_melspec_windows(const float* wav, int channels, long long n_total, const
 // rec_cap < 1.
 int mmd_det_record_append(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, float* rec_rows, int* rec_win, int rec_cap, int* rec_count, int* rec_overflow, hipStream_t stream);
 
+// ---- streaming tracking (csrc/track.hip, AudioDetector.track_stream): links the rows of a group of windows to the tracks of the
+// windows before - a greedy IoU tracker with a constant-velocity alpha-beta model, alpha = 1 (the rule: DESIGN.md, streaming tracking;
+// tests/track_ref.py restates it in numpy float32 and gives the same bits).  rows / cnt / B / cap_img / ctl as mmd_det_record_append.
+// The launch MUST PRECEDE the mmd_det_record_append of the same group on the same stream: it reads the *rec_count the append is
+// about to advance (never writes it), does the same clamped exclusive scan of cnt[0 .. n_valid-1] and writes rec_track[offset + j]
+// (int32: the row's track id, -1 = none) for every row the append will write at rec_rows[offset + j]; rows behind rec_cap are not
+// written.  Windows run in order first_window, first_window + 1, ..; a window without rows ages the tracks.  Counts behind n_valid,
+// negative and huge counts are clamped or ignored as the append does; nothing behind cnt[i] rows of image i is read.
+// State, caller-owned: trk_slots int32 [max_tracks, 16], one slot per row, words 0 live (0 = free), 1 id, 2..5 x1 y1 x2 y2 (float bits),
+// 6 7 vx vy (pixels per window), 8 label (float bits), 9 score, 10 hits, 11 misses, 12 last_window, 13..15 unused (never read or
+// written); a freed slot's words 0..12 are zeroed.  trk_glob int32 [2] = {next_id, overflow}.  A ZERO FILL of both RESETS the tracker
+// (ids start at 0 again); between the groups of one recording they are left alone.  rec_track and the record arrays need no zeroing.
+// Overflow: at most 256 detections of a window take part - the first 256 in NMS output order; later rows get -1 - and an unmatched
+// detection that finds no free slot among max_tracks gets -1; either sets trk_glob[1] = 1 (sticky: only a zero fill clears it).
+// max_tracks 1 .. 256; a track is freed once it was missed more than max_age windows in a row; pairs need equal labels and
+// iou >= iou_min; an unmatched detection starts a track when score >= birth_score (comparisons are false for NaN).
+// One block of 256 threads, no atomics: two runs give the same bits.  -22 before any launch on null pointers, B < 1, B > 1024,
+// cap_img < 1, rec_cap < 1, max_tracks outside 1 .. 256, max_age < 0.
+int mmd_track_update(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, hipStream_t stream);
+
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction
 // (src/optimization/train_methods.py:944-961): student gradients only, sum (the 1/N average rides in the optimizer pass), plus the

@@ -11,7 +11,8 @@ static input buffers, as `DistillEngine.capture` / `replay` do for the training 
 
 `detect_stream` slides that chain over one long recording that stays on the device: the front end reads the overlapping windows straight
 out of it (`mmd_melspec_windows`), a device-side record collects every group's rows (`mmd_det_record_append`, csrc/stream.hip), and the
-host synchronises and copies once, at the end."""
+host synchronises and copies once, at the end.  `track_stream` is the same stream with a tracker (`mmd_track_update`, csrc/track.hip) in
+front of every group's append: each row of the record also gets the id of its track."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -25,6 +26,8 @@ from .audio import MelFrontEnd, stream_window_starts
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
+from . import tracker as _tracker
+from .tracker import TrackConfig
 
 
 class AudioDetector:
@@ -154,11 +157,14 @@ class AudioDetector:
     STREAM_ROWS_PER_WINDOW = 256      # default record size per window when cand_cap = 0 (unlimited rows per image)
 
     def _stream_chain(self, g: dict):
-        """One group of windows: front end on the windows the control row names -> forward -> decode -> NMS -> append to the record."""
+        """One group of windows: front end on the windows the control row names -> forward -> decode -> NMS [-> track update] -> append
+        to the record.  The track update reads the record's count before the append advances it."""
         self.front.melspec_windows_into(g["wave"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
         audio = self.front.resize_into(g["mel"], self.S, g["audio"])
         self._tail(audio, g)
         B = audio.shape[0]
+        if g["track"] is not None:
+            _tracker.update(g["rows"], g["cnt"], g["ctl"], g["rec_state"][0:1], g["rec_cap"], g["rec_track"], g["trk_state"], g["track"])
         _lib.call("mmd_det_record_append", g["rows"], g["cnt"], B, g["rows"].shape[1], g["ctl"], g["rec_rows"], g["rec_win"],
                   g["rec_cap"], g["rec_state"][0:1], g["rec_state"][1:2])
 
@@ -183,19 +189,43 @@ class AudioDetector:
 
         The graph bakes in the recording's address: it is kept for (win_len, batch, image size, wave.data_ptr(), n_total) and rec_cap,
         and captured again when any of them changes; the detector holds the buffers of one recording at a time."""
+        rows, window, _ = self._run_stream("detect_stream", wave, win_len, hop, batch, rec_cap, None)
+        return rows, window
+
+    @torch.no_grad()
+    def track_stream(self, wave: torch.Tensor, win_len: int, hop: int, batch: int = 8, rec_cap: Optional[int] = None,
+                     track: TrackConfig = TrackConfig()):
+        """`detect_stream` with a tracker on the device: -> (rows float32 [R, 6], window int32 [R], track int32 [R]).  rows and window
+        have exactly the bits `detect_stream` gives; track[i] is the id of the track row i belongs to - ids start at 0 for every call,
+        rise in order of birth and are never reused - or -1 (a row that neither continued nor started a track).
+
+        The rule (`tracker.TrackConfig`, DESIGN.md streaming tracking): per window every live track is moved by its velocity, tracks and
+        boxes of equal label are paired greedily by IoU >= iou_min, a paired track takes the box and corrects its velocity by beta of
+        the centre's residual, an unpaired track is kept for max_age windows, an unpaired box of score >= birth_score starts a track.
+
+        The chain is detect_stream's with `mmd_track_update` between a group's NMS and its record append, in a captured graph of its
+        own: the stream key carries the tracking parameters, so `detect_stream` and `track_stream` never replay each other's graph.
+        The tracker's state is zeroed with the record's before the first group; still one synchronisation and one copy at the end.
+        More than max_tracks live tracks, or more than 256 boxes in one window, raise RuntimeError."""
+        if not isinstance(track, TrackConfig):
+            raise ValueError("track_stream: track must be a TrackConfig")
+        return self._run_stream("track_stream", wave, win_len, hop, batch, rec_cap, track)
+
+    def _run_stream(self, who: str, wave: torch.Tensor, win_len: int, hop: int, batch: int, rec_cap: Optional[int],
+                    track: Optional[TrackConfig]):
         C = self.net.spec.in_channels
         if wave.dim() != 2 or wave.dtype != torch.float32 or wave.shape[0] != C or not wave.is_cuda or not wave.is_contiguous():
-            raise ValueError("detect_stream takes one contiguous float32 [%d, n_total] recording on the device" % C)
+            raise ValueError("%s takes one contiguous float32 [%d, n_total] recording on the device" % (who, C))
         win_len, hop, batch, n_total = int(win_len), int(hop), int(batch), int(wave.shape[1])
         if batch < 1 or batch > 1024:
-            raise ValueError("detect_stream: batch = %d (1 .. 1024)" % batch)
+            raise ValueError("%s: batch = %d (1 .. 1024)" % (who, batch))
         starts = stream_window_starts(n_total, win_len, hop)
         W = len(starts)
         if rec_cap is None:
             rec_cap = W * (self.cand_cap if self.cand_cap > 0 else self.STREAM_ROWS_PER_WINDOW)
         rec_cap = int(rec_cap)
         if rec_cap < 1 or rec_cap > 0x7fffffff:
-            raise ValueError("detect_stream: rec_cap = %d" % rec_cap)
+            raise ValueError("%s: rec_cap = %d" % (who, rec_cap))
         # control table, one row per group: int64 starts[batch], then {n_valid, first_window} as two int32 in the last word
         G = (W + batch - 1) // batch
         table = np.empty((G, batch + 1), np.int64)
@@ -206,7 +236,7 @@ class AudioDetector:
             tail[gi] = (len(real), gi * batch)
         table = torch.from_numpy(table).to(self.device)
 
-        key = (win_len, batch, self.S, wave.data_ptr(), n_total, rec_cap)
+        key = (win_len, batch, self.S, wave.data_ptr(), n_total, rec_cap, None if track is None else track.key())
         arenas = (self.ws, self.net.arena, self.net.zarena)
         g = self._stream
         if g is None or g["key"] != key:
@@ -214,7 +244,7 @@ class AudioDetector:
             for a in arenas:
                 a.frozen = False                  # chunks are only ever appended: the graphs of `_detect` stay valid
             cur = torch.zeros(batch + 1, dtype=torch.int64, device=self.device)
-            g = {"key": key, "wave": wave, "win_len": win_len, "rec_cap": rec_cap, "cur": cur, "starts": cur[:batch],
+            g = {"key": key, "track": track, "wave": wave, "win_len": win_len, "rec_cap": rec_cap, "cur": cur, "starts": cur[:batch],
                  "ctl": cur[batch:].view(torch.int32),
                  "mel": torch.empty(batch, self.front.n_mels, self.front.n_frames(win_len), C, device=self.device),
                  "max_ws": torch.empty(batch * C, device=self.device),
@@ -222,6 +252,9 @@ class AudioDetector:
                  "rec_rows": torch.empty(rec_cap, 6, device=self.device),
                  "rec_win": torch.empty(rec_cap, dtype=torch.int32, device=self.device),
                  "rec_state": torch.zeros(2, dtype=torch.int32, device=self.device)}       # {rec_count, overflow flag}
+            if track is not None:
+                g["rec_track"] = torch.empty(rec_cap, dtype=torch.int32, device=self.device)
+                g["trk_state"] = _tracker.new_state(self.device, track)
             self._stream = g
         if self.use_graph and "graph" not in g:
             # a warm-up group sizes the arenas (what it appends is dropped: the record's state is zeroed below), then the capture
@@ -237,6 +270,9 @@ class AudioDetector:
             g["graph"] = graph
             self.stream_captures += 1
         g["rec_state"].zero_()
+        if track is not None:
+            for t in g["trk_state"]:
+                t.zero_()
         for gi in range(G):
             g["cur"].copy_(table[gi], non_blocking=True)
             if self.use_graph:
@@ -252,7 +288,12 @@ class AudioDetector:
         self.check_overflow()
         if over or n > rec_cap:
             raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, rec_cap))
-        return g["rec_rows"][:n].cpu().numpy(), g["rec_win"][:n].cpu().numpy()
+        rows, window = g["rec_rows"][:n].cpu().numpy(), g["rec_win"][:n].cpu().numpy()
+        if track is None:
+            return rows, window, None
+        if int(g["trk_state"][1][1].item()):
+            raise RuntimeError(_tracker.overflow_message(track, window))
+        return rows, window, g["rec_track"][:n].cpu().numpy()
 
     def check_overflow(self):
         if int(self.overflow.item()):
