@@ -4,6 +4,7 @@
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
+                     [--resample | --sample_rate R]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -21,6 +22,12 @@ With --track (only with --window_s) the boxes of consecutive windows are linked 
 (`AudioDetector.track_stream`: greedy IoU association with a constant-velocity model) and the CSV gains a last column `track`: the id of
 the row's track - ids start at 0 and rise in order of birth - or -1.  --track_iou: smallest IoU of a pairing (0.3); --track_beta: velocity
 gain (0.5); --track_max_age: windows a track survives without a box (2); --track_max: live tracks at a time (64, at most 256).
+
+With --resample a `.wav` may have any sample rate and 16-, 24- or 32-bit PCM samples (8 channels): its frames go to the device as they
+are in the file, are decoded there and resampled to 44.1 kHz (`mm_distillnet_amd.audio.Resampler`: what `librosa.load(path, sr=44100)`
+does upstream, by this project's own windowed-sinc rule).  With --sample_rate R a `.npy` is taken to be at R Hz and resampled when
+R != 44100.  Everything behind that - the clip, --window_s and --track paths - runs unchanged on the 44.1 kHz waveforms; window and hop
+sizes and the CSV's times stay in seconds of the recording.  Without these two flags every input is read as described above.
 """
 import argparse
 import csv
@@ -77,6 +84,45 @@ def read_input(path: str) -> np.ndarray:
     if ext == ".wav":
         return read_wav(path)
     raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+
+
+def read_recording(path: str):
+    """A PCM `.wav` of 8 channels at ANY rate, 16-, 24- or 32-bit -> (its frames as a uint8 array, just as they are in the file:
+    interleaved little-endian signed samples; frames; channels; bytes per sample; rate in Hz).  Nothing is decoded on the host:
+    `Resampler.pcm_to_float` and `Resampler.resample` take it from there (--resample)."""
+    with wave.open(path, "rb") as w:
+        width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
+        if w.getcomptype() != "NONE" or width not in (2, 3, 4):
+            raise ValueError(f"{path}: only 16-, 24- or 32-bit PCM is supported, found {8 * width}-bit {w.getcomptype()}")
+        if channels != CHANNELS:
+            raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
+        if rate < 1:
+            raise ValueError(f"{path}: sample rate {rate} Hz")
+        raw = np.frombuffer(w.readframes(w.getnframes()), dtype=np.uint8)
+    frames = raw.size // (channels * width)
+    if frames < 1:
+        raise ValueError(f"{path}: no frames")
+    return raw[:frames * channels * width].copy(), frames, channels, width, rate
+
+
+def load_resampled(a, dev):
+    """--resample / --sample_rate: -> float32 DEVICE waveforms [B, 8, N] at 44.1 kHz"""
+    from mm_distillnet_amd.audio import Resampler
+    ext = os.path.splitext(a.input)[1].lower()
+    if a.resample:
+        if ext != ".wav" or a.sample_rate is not None:
+            raise ValueError(f"{a.input}: --resample reads a .wav, whose header holds the rate (for a .npy give --sample_rate R alone)")
+        raw, frames, channels, width, rate = read_recording(a.input)
+        rs = Resampler(dev)
+        wav = rs.pcm_to_float(torch.from_numpy(raw).to(dev), frames, channels, width)[None]
+    else:
+        if ext != ".npy":
+            raise ValueError(f"{a.input}: --sample_rate R says at which rate a .npy was recorded (a .wav holds its rate: --resample)")
+        if a.sample_rate < 1:
+            raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
+        rs = Resampler(dev)
+        wav, rate = torch.from_numpy(read_npy(a.input)).to(dev), a.sample_rate
+    return rs.resample(wav, rate, SAMPLE_RATE)
 
 
 def write_csv(path: str, rows_per_clip) -> int:
@@ -139,6 +185,8 @@ def main(argv=None):
     ap.add_argument("--track_beta", type=float, default=0.5, help="velocity gain of the constant-velocity model")
     ap.add_argument("--track_max_age", type=int, default=2, help="windows a track survives without a box")
     ap.add_argument("--track_max", type=int, default=64, help="live tracks at a time (1 .. 256)")
+    ap.add_argument("--resample", action="store_true", help="a .wav of any rate, 16/24/32-bit PCM: decode and resample to 44.1 kHz on the device")
+    ap.add_argument("--sample_rate", type=int, default=None, help="the rate in Hz of a .npy input; resampled to 44.1 kHz on the device")
     a = ap.parse_args(argv)
     track = None
     if a.track:
@@ -147,29 +195,36 @@ def main(argv=None):
         from mm_distillnet_amd.tracker import TrackConfig
         track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
-    waves = read_input(a.input)
+    dev = "cuda:0"
+    resampled = a.resample or a.sample_rate is not None
+    if resampled:                             # the waveforms are made on the device: it is needed before the sizes are known
+        torch.cuda.set_device(0)
+        waves = load_resampled(a, dev)
+    else:
+        waves = read_input(a.input)
     if a.window_s is not None:
         if waves.shape[0] != 1:
             raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
                              f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
         win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, waves.shape[2])
     torch.cuda.set_device(0)
-    dev = "cuda:0"
     sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
+    if not resampled:
+        waves = torch.from_numpy(waves).to(dev)
     if track is not None:
-        rows, window, ids = det.track_stream(torch.from_numpy(waves[0]).to(dev), win_len, hop, batch=a.batch, track=track)
+        rows, window, ids = det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
         n = write_track_csv(a.output, rows, window, ids, hop)
         print("%d windows, %d boxes, %d tracks -> %s" % (n_win, n, len(np.unique(ids[ids >= 0])), a.output))
         return rows, window, ids
     if a.window_s is not None:
-        rows, window = det.detect_stream(torch.from_numpy(waves[0]).to(dev), win_len, hop, batch=a.batch)
+        rows, window = det.detect_stream(waves[0], win_len, hop, batch=a.batch)
         n = write_stream_csv(a.output, rows, window, hop)
         print("%d windows, %d boxes -> %s" % (n_win, n, a.output))
         return rows, window
-    rows = det.detect(torch.from_numpy(waves).to(dev))
+    rows = det.detect(waves)
     det.check_overflow()
     n = write_csv(a.output, rows)
     print("%d clips, %d boxes -> %s" % (len(rows), n, a.output))

@@ -589,6 +589,34 @@ int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_
 // channels < 1, win_len <= 512 (too short for the padding), win_len > n_total, a bad band_stride or db outside {0, 1}.
 int mmd_melspec_windows(const float* wav, int channels, long long n_total, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
 
+// ---- sample-rate conversion and PCM decoding (csrc/resample.hip): what librosa.load(path, sr=44100) does in front of the mel
+// spectrogram upstream (mp3_to_pkl.py:31; merge_audios, src/datasets/MultimodalDetection.py:335-336).
+// x[rows, n_in] at sr_in -> y[rows, n_out] at sr_out, rows = batch x channels, with L / M = sr_out / sr_in in lowest terms and
+// n_out = ceil(n_in * L / M):  y[t] = sum_{j < taps} B[p][j] * x[n + j - taps / 2 + 1],  n = (t * M) // L,  p = (t * M) % L,  where
+// B[p][j] = h(p / L - (j - taps / 2 + 1)) is the float32 windowed-sinc bank of mm_distillnet_amd.audio.resample_bank (after the published
+// design of resampy's kaiser_best, as an exact polyphase filter; the rule is the project's own, pinned to tests/resample_ref.py: parity
+// with resampy / librosa themselves is UNPINNED).  x is ZERO-EXTENDED at both ends: samples outside 0 .. n_in - 1 count as 0, there is
+// no reflect padding, so the first and last taps / 2 input samples' worth of output fade in and out.
+// Layout of the arguments: bank[taps, L] TRANSPOSED and in OUTPUT-phase order - bank[j * L + r] = B[(r * M) % L][j] for r = t % L - so
+// that neighbouring outputs read neighbouring addresses for a fixed tap; phase_off[L], phase_off[r] = (r * M) // L.  Both are DEVICE
+// tables whose contents cannot be checked on the host: a wrong table is the CALLER'S ERROR (the kernel clamps what it takes from
+// phase_off into the input span it staged, so such a call gives wrong samples but reads nothing outside x's row and writes nothing
+// outside y's).  fp32 accumulation in tap order; one launch, plain stores, no atomics, no allocation, no host synchronisation: y needs
+// no zeroing, elements behind n_out of a larger buffer are not touched, and two calls give the same bits.  Outputs are indexed as
+// (period, phase), so no product t * M is formed.  Caps: L, M in 1 .. 1024, taps even in 2 .. 4096, rows <= 65535, n_in <= 2^50.
+// -22 before any launch on null pointers, rows < 1, n_in < 1, L or M outside 1 .. 1024, taps odd or outside 2 .. 4096,
+// n_out != ceil(n_in * L / M), or a size above the caps.
+int mmd_resample_poly(const float* x, int rows, long long n_in, const float* bank, const int* phase_off, int L, int M, int taps, float* y, long long n_out, hipStream_t stream);
+
+// A PCM WAV's frames as read from the file -> the waveforms the front end takes (detect.py --resample; upstream gets floats from
+// librosa.load, mp3_to_pkl.py:31): pcm = interleaved little-endian SIGNED samples [frames, channels] of width 2, 3 or 4 bytes ->
+// out[channels, frames] float32, a de-interleaving transpose staged through LDS (word reads, coalesced float stores; pcm needs no
+// alignment).  16-bit: i / 2^15; 24-bit: sign-extended, i / 2^23; 32-bit: (float)i rounded to nearest, then * 2^-31 - each equal bit for
+// bit to numpy.float32(i) / numpy.float32(2^k).  One launch, no allocation, no host synchronisation; out needs no zeroing and two calls
+// give the same bits.  Caps: channels * width <= 16384.  -22 before any launch on null pointers, frames < 1, channels < 1, another
+// width, or channels above the cap.
+int mmd_pcm_to_float(const unsigned char* pcm, long long frames, int channels, int width, float* out, hipStream_t stream);
+
 // ---- device-side detection record (csrc/stream.hip): the rows mmd_nms_teacher leaves for a group of windows, appended behind every
 // group with one host copy at the end of the recording (the shape of mmd_eval_match's record).
 // rows[B, cap_img, 6] / cnt[B]: decode / NMS output (counts are clamped to 0 .. cap_img).  ctl[2] (DEVICE) = {n_valid, first_window}:

@@ -6,8 +6,14 @@ each channel, then resizes with cv2.INTER_CUBIC; `Audio2Spectogram` (src/dataset
 one recording.  The student's stored input is the dB map `librosa.power_to_db(S, ref=np.max)` of each microphone's spectrogram
 (mp3_to_pkl.py:31-41): `db=True`.  Here the host only builds the Slaney filter bank; the spectrogram and the dB conversion are
 csrc/melspec.hip (`mmd_melspec_batch`, `mmd_power_to_db`), the resize `mmd_resize_cubic_batch`.  librosa's and cv2's arithmetic is
-restated, parity with the libraries themselves is unpinned."""
+restated, parity with the libraries themselves is unpinned.
+
+Upstream's `librosa.load(path, sr=44100)` (mp3_to_pkl.py:31, merge_audios :335-336) also resamples whatever rate the file has; here that
+first link is `Resampler` (csrc/resample.hip: `mmd_resample_poly`, and `mmd_pcm_to_float` for a WAV's raw frames).  The rule is the
+project's own, pinned to tests/resample_ref.py; parity with resampy / librosa is unpinned."""
 from __future__ import annotations
+
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -139,3 +145,97 @@ class MelFrontEnd:
         mel = self.melspec(wav_a, wav_b, db)
         B, M, T, C = mel.shape
         return self.resize_into(mel, S, torch.empty(B, C, S, S, device=self.device))
+
+
+# ---- resampling (csrc/resample.hip): a windowed-sinc interpolator after the published design of resampy's `kaiser_best` filter, as an
+# exact rational polyphase filter
+RS_ZEROS, RS_ROLLOFF, RS_BETA = 64, 0.9475937167399596, 14.769656459379492
+RS_MAX_FACTOR = 1024                                 # cap of L and M in mmd_resample_poly
+RS_MAX_TAPS = 4096                                   # and of the taps per output: 2 * ceil(64 * max(1, M / L))
+
+
+def resample_len(n_in: int, sr_in: int, sr_out: int = 44100) -> int:
+    """ceil(n_in * sr_out / sr_in) in integers: the samples `Resampler.resample` returns for n_in"""
+    f = Fraction(int(sr_out), int(sr_in))
+    return -((-int(n_in) * f.numerator) // f.denominator)
+
+
+def resample_bank(sr_in: int, sr_out: int = 44100):
+    """-> (L, M, half, bank float32 [L, 2 * half], phase_off int32 [L]) for sr_in -> sr_out.
+
+    L / M = sr_out / sr_in in lowest terms, scale = min(1, L / M), half = ceil(64 / scale).  bank[p][j] = h(p / L - k) at k = j - half + 1
+    with h(tau) = scale * rolloff * sinc(scale * rolloff * tau) * kaiser(tau * scale / 64), computed in float64 (the argument as the one
+    quotient (p - k L) / L) and rounded once: output t is sum_j bank[(t M) % L][j] * x[(t M) // L + j - half + 1].  phase_off[r] =
+    (r * M) // L is the input offset of output phase r = t % L inside its period.  Raises ValueError, naming the reduced ratio, for what
+    `mmd_resample_poly` does not take: L or M above 1024, or more than 4096 taps (M / L above 32)."""
+    if int(sr_in) < 1 or int(sr_out) < 1:
+        raise ValueError(f"sample rates must be positive, found {sr_in} -> {sr_out}")
+    f = Fraction(int(sr_out), int(sr_in))
+    L, M = f.numerator, f.denominator
+    if L > RS_MAX_FACTOR or M > RS_MAX_FACTOR:
+        raise ValueError(f"{sr_in} Hz -> {sr_out} Hz reduces to the ratio {L} / {M}: factors above {RS_MAX_FACTOR} are not supported")
+    scale = 1.0 if L >= M else L / M
+    half = RS_ZEROS if L >= M else -((-RS_ZEROS * M) // L)
+    if 2 * half > RS_MAX_TAPS:
+        raise ValueError(f"{sr_in} Hz -> {sr_out} Hz reduces to the ratio {L} / {M}: its filter has {2 * half} taps, "
+                         f"more than {RS_MAX_TAPS} (a reduction by more than {RS_MAX_TAPS // (2 * RS_ZEROS)} is not supported)")
+    p = np.arange(L, dtype=np.int64)[:, None]
+    k = np.arange(-half + 1, half + 1, dtype=np.int64)[None, :]
+    tau = (p - k * L).astype(np.float64) / L
+    u = tau * scale / RS_ZEROS
+    inside = np.abs(u) < 1.0
+    window = np.where(inside, np.i0(RS_BETA * np.sqrt(np.where(inside, 1.0 - u * u, 0.0))) / np.i0(RS_BETA), 0.0)
+    bank = (scale * RS_ROLLOFF * np.sinc(scale * RS_ROLLOFF * tau) * window).astype(np.float32)
+    phase_off = ((np.arange(L, dtype=np.int64) * M) // L).astype(np.int32)
+    return L, M, half, bank, phase_off
+
+
+class Resampler:
+    """Sample-rate conversion and PCM decoding on `device`.  The filter banks are built on the host once per (sr_in, sr_out) and kept
+    on the device; every call runs on the current stream and allocates only its result."""
+
+    def __init__(self, device):
+        from . import _lib
+        self.call = _lib.call
+        self.device = torch.device(device)
+        self._banks = {}
+
+    def _on_device(self, t: torch.Tensor, what: str):
+        if not t.is_cuda or (self.device.index is not None and t.device.index != self.device.index):
+            raise ValueError(f"{what}: the tensor is on {t.device}, this Resampler on {self.device}")
+
+    def _bank(self, sr_in: int, sr_out: int):
+        key = (int(sr_in), int(sr_out))
+        if key not in self._banks:
+            L, M, half, bank, phase_off = resample_bank(*key)
+            # the kernel's layout: [taps, L] with the columns in OUTPUT-phase order r = t % L (filter phase (r M) % L), so that the lanes
+            # of a wave - neighbouring outputs - read neighbouring addresses for a fixed tap
+            by_out_phase = bank[(np.arange(L, dtype=np.int64) * M) % L]
+            self._banks[key] = (L, M, 2 * half, torch.from_numpy(np.ascontiguousarray(by_out_phase.T)).to(self.device),
+                                torch.from_numpy(phase_off).to(self.device))
+        return self._banks[key]
+
+    def resample(self, wav: torch.Tensor, sr_in: int, sr_out: int = 44100) -> torch.Tensor:
+        """contiguous float32 device waveforms [..., N] at sr_in -> [..., ceil(N * sr_out / sr_in)] at sr_out (`mmd_resample_poly`, one
+        launch).  sr_in == sr_out returns `wav` itself: no bank, no launch."""
+        if int(sr_in) == int(sr_out):
+            return wav
+        if wav.dtype != torch.float32 or wav.dim() < 1 or wav.shape[-1] < 1 or not wav.is_contiguous():
+            raise ValueError("resample takes contiguous float32 [..., N] waveforms")
+        self._on_device(wav, "resample")
+        L, M, taps, bank, phase_off = self._bank(sr_in, sr_out)
+        n_in = wav.shape[-1]
+        n_out = -((-n_in * L) // M)
+        out = torch.empty(*wav.shape[:-1], n_out, device=self.device)
+        self.call("mmd_resample_poly", wav, wav.numel() // n_in, n_in, bank, phase_off, L, M, taps, out, n_out)
+        return out
+
+    def pcm_to_float(self, raw: torch.Tensor, frames: int, channels: int, width: int) -> torch.Tensor:
+        """interleaved little-endian signed PCM, raw uint8 [frames * channels * width] on the device (a WAV's frames as read) ->
+        float32 [channels, frames] in [-1, 1) (`mmd_pcm_to_float`): 16-bit / 2^15, 24-bit / 2^23, 32-bit rounded to float32 then / 2^31."""
+        if raw.dtype != torch.uint8 or raw.numel() != int(frames) * int(channels) * int(width) or not raw.is_contiguous():
+            raise ValueError(f"pcm_to_float takes {frames} * {channels} * {width} contiguous uint8 bytes, found {raw.numel()} of {raw.dtype}")
+        self._on_device(raw, "pcm_to_float")
+        out = torch.empty(int(channels), int(frames), device=self.device)
+        self.call("mmd_pcm_to_float", raw, int(frames), int(channels), int(width), out)
+        return out

@@ -1,0 +1,196 @@
+// Sample-rate conversion and PCM decoding: the first link of the waveform chain that melspec.hip restates.
+//
+//   Both of upstream's audio entry points call librosa.load(path, sr=44100) (mp3_to_pkl.py:31; MultimodalDetection.merge_audios,
+//   src/datasets/MultimodalDetection.py:335-336), so upstream resamples whatever rate a file has (librosa 0.7.2 hands that to resampy's
+//   `kaiser_best`) before the mel spectrogram.
+//
+// Neither library is part of the reference tree or installed with this project.  The rule below is the project's OWN: a band-limited
+// windowed-sinc interpolator after the published design of `kaiser_best` (Z = 64 zero crossings, rolloff = 0.9475937167399596, Kaiser
+// beta = 14.769656459379492), evaluated as an EXACT rational polyphase filter - resampy's linearly interpolated table is not used.  It is
+// pinned to tests/resample_ref.py; parity with resampy / librosa themselves is UNPINNED.
+//
+//   L / M = sr_out / sr_in in lowest terms, scale = min(1, L / M), half = ceil(Z / scale), taps = 2 * half
+//   h(tau) = scale * rolloff * sinc(scale * rolloff * tau) * w(tau * scale / Z)        tau in input samples, sinc(x) = sin(pi x) / (pi x)
+//   w(u)   = I0(beta * sqrt(1 - u^2)) / I0(beta) for |u| < 1, else 0
+//   n_out  = ceil(n_in * L / M)
+//   y[t]   = sum_{k = -half+1 .. half} h(p / L - k) * x[n + k],   n = (t * M) // L,  p = (t * M) % L,   x = 0 outside 0 .. n_in - 1
+//
+// The host (mm_distillnet_amd.audio.resample_bank) evaluates h in float64 and rounds it once to float32; the kernel multiplies those
+// values and accumulates in fp32 in tap order.
+//
+// Indexing.  t * M passes 2^31 within 77 s of 192 kHz audio (M = 640), and a 64-bit division per output is dear, so outputs are addressed
+// as (period q, output phase r): t = q * L + r, 0 <= r < L.  Then n = q * M + phase_off[r] with phase_off[r] = (r * M) // L < M, and the
+// filter phase is p = (r * M) % L - both depend on r alone.  Only q * M, q * L and the row offsets are 64-bit; nothing is divided.
+//
+// Bank layout (the `bank` argument): [taps, L], bank[j * L + r] = h(p(r) / L - k) at k = j - half + 1 - TRANSPOSED and with the columns in
+// OUTPUT-phase order r, not filter-phase order p.  The lanes of a wave hold neighbouring r, so for a fixed tap they read neighbouring
+// addresses; with the natural [L, taps] layout they would read `taps` floats apart.  The bank is 80 KB (48 k -> 44.1 k) to 320 KB
+// (192 k -> 44.1 k) and every block walks all of it: it lives in L2.
+//
+// Shape.  A block owns ONE row, a tile of PH <= 64 consecutive output phases (L split into cdiv(L, 64) equal tiles: 3 x 49 for L = 147)
+// and QB consecutive periods.  Thread (ph, pq) = (tid % PH, tid / PH) accumulates RS_QT = 4 outputs of its phase, periods pq, pq + PS,
+// pq + 2 PS, pq + 3 PS with PS = 256 / PH: one bank value from L2 feeds four multiply-adds, and the threads of a wave write outputs that
+// are consecutive in t within a period (consecutive across periods too when PH == L).  The tile's input span,
+// (QB - 1) * M + (phase_off[last] - phase_off[first]) + taps samples (13 KB for 48 k -> 44.1 k with QB = 20; for 192 k QB shrinks from 20 to
+// 19 and the span fills the 48 KB cap, three blocks per CU), is staged into LDS once with coalesced loads, zeros where the index leaves
+// 0 .. n_in - 1: the tap loop has no bounds test.
+// LDS reads are ds_read_b32 at (period offset + phase offset + j): within a 32-lane half the phase offsets rise by M / L per lane, so
+// lanes land on distinct banks for M / L near 1, share an address (broadcast) for upsampling, and collide about M / L ways when
+// downsampling from 96 k or 192 k - four LDS reads per global load either way.  Plain stores, no atomics, fixed summation order: y
+// needs no zeroing and two launches give the same bits.
+#include "common.h"
+
+#define RS_THREADS 256
+#define RS_QT 4                                      // periods per thread
+#define RS_PHMAX 64                                  // phases per block at most
+#define RS_LDS_FLOATS 12288                          // staged input span at most (48 KB)
+#define RS_FMAX 1024                                 // L, M at most
+#define RS_TAPS_MAX 4096
+#define RS_ROWS_MAX 65535                            // rows ride in gridDim.z
+
+struct RsPlan { int PH, PS, QB, dbound, span; };
+
+// dbound: phase_off[b] - phase_off[a] = floor(b M / L) - floor(a M / L) <= floor((b - a) M / L) + 1 for the PH phases of a tile
+static inline RsPlan rs_plan(int L, int M, int taps, long long n_periods) {
+  RsPlan p;
+  const int ntile = cdiv(L, RS_PHMAX);
+  p.PH = cdiv(L, ntile);
+  p.PS = RS_THREADS / p.PH;
+  p.dbound = (int)(((long long)(p.PH - 1) * M) / L) + 1;
+  long long qb = (RS_LDS_FLOATS - taps - p.dbound) / M + 1;          // >= 1: taps + dbound <= 4096 + 1024 < RS_LDS_FLOATS
+  if (qb > (long long)p.PS * RS_QT) qb = (long long)p.PS * RS_QT;
+  if (qb > n_periods) qb = n_periods;
+  p.QB = (int)qb;
+  p.span = (p.QB - 1) * M + p.dbound + taps;
+  return p;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const float* __restrict__ x, long long n_in, const float* __restrict__ bank,
+                                                                   const int* __restrict__ phase_off, int L, int M, int taps,
+                                                                   float* __restrict__ y, long long n_out, RsPlan pl) {
+  extern __shared__ float s_x[];                     // pl.span floats
+  const int tid = threadIdx.x;
+  const int r0 = blockIdx.y * pl.PH;                 // < L: gridDim.y = cdiv(L, PH)
+  const long long q0 = (long long)blockIdx.x * pl.QB;
+  x += (size_t)blockIdx.z * (size_t)n_in;
+  y += (size_t)blockIdx.z * (size_t)n_out;
+
+  // ---- stage the tile's input span; s_x[i] = x[g0 + i], zero outside the row
+  const int off0 = phase_off[r0];
+  const long long g0 = q0 * M + off0 - (taps >> 1) + 1;
+  for (int i = tid; i < pl.span; i += RS_THREADS) {
+    const long long g = g0 + i;
+    s_x[i] = (g >= 0 && g < n_in) ? x[g] : 0.f;
+  }
+  __syncthreads();
+
+  // ---- thread (ph, pq): phase r0 + ph, periods q0 + pq + i * PS.  The table is the caller's: its differences are clamped into the
+  //      staged span (a bad table gives wrong samples, never a read outside the tile), idle threads read the tile's first taps.
+  const int ph = tid % pl.PH, pq = tid / pl.PH;
+  const int r = min(r0 + ph, L - 1);
+  const bool lane_ok = r0 + ph < L && pq < pl.PS;
+  const int d = min(max(phase_off[r] - off0, 0), pl.dbound);
+  int base[RS_QT];
+  float acc[RS_QT];
+#pragma unroll
+  for (int i = 0; i < RS_QT; ++i) {
+    const int qi = pq + i * pl.PS;
+    base[i] = (lane_ok && qi < pl.QB) ? qi * M + d : 0;
+    acc[i] = 0.f;
+  }
+  const float* b = bank + r;
+#pragma unroll 4
+  for (int j = 0; j < taps; ++j) {
+    const float w = b[(size_t)j * L];
+#pragma unroll
+    for (int i = 0; i < RS_QT; ++i) acc[i] = fmaf(w, s_x[base[i] + j], acc[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < RS_QT; ++i) {
+    const int qi = pq + i * pl.PS;
+    const long long t = (q0 + qi) * L + r0 + ph;
+    if (lane_ok && qi < pl.QB && t < n_out) y[t] = acc[i];
+  }
+}
+
+extern "C" int mmd_resample_poly(const float* x, int rows, long long n_in, const float* bank, const int* phase_off, int L, int M, int taps,
+                                 float* y, long long n_out, hipStream_t stream) {
+  if (!x || !bank || !phase_off || !y || rows < 1 || rows > RS_ROWS_MAX || n_in < 1 || n_in > (1ll << 50)) return MMD_EINVAL;
+  if (L < 1 || L > RS_FMAX || M < 1 || M > RS_FMAX || (taps & 1) || taps < 2 || taps > RS_TAPS_MAX) return MMD_EINVAL;
+  if (n_out != (n_in * L + M - 1) / M) return MMD_EINVAL;
+  const long long n_periods = (n_out + L - 1) / L;
+  const RsPlan pl = rs_plan(L, M, taps, n_periods);
+  const long long blocks = (n_periods + pl.QB - 1) / pl.QB;
+  if (blocks > 0x7fffffffll) return MMD_EINVAL;
+  const dim3 grid((unsigned)blocks, cdiv(L, pl.PH), rows);
+  hipLaunchKernelGGL(resample_poly_kernel, grid, dim3(RS_THREADS), sizeof(float) * (size_t)pl.span, stream, x, n_in, bank, phase_off, L, M,
+                     taps, y, n_out, pl);
+  return mmd_check_launch();
+}
+
+// ---- interleaved little-endian signed PCM [frames, channels] of 2, 3 or 4 bytes -> float [channels, frames]: a transpose.
+// A block owns F consecutive frames (F * channels * width <= 16 KB).  It copies their bytes to LDS as aligned 32-bit words, lane i word i
+// (a word that straddles the tile's first or last byte is put together from byte loads, so nothing outside the tile is read, whatever
+// the buffer's alignment), then thread idx = c * F + f decodes sample (f, c) from LDS bytes and stores out[c, f0 + f]: the lanes of a
+// wave write consecutive floats.  In LDS they read channels * width bytes apart (16 bytes for eight 16-bit channels: every fourth bank,
+// 4 lanes of a 32-lane half on each); one pad word behind every 32 spreads such power-of-two strides over all banks.
+#define PCM_THREADS 256
+#define PCM_TILE_BYTES 16384
+#define PCM_FMAX 2048
+#define PCM_LDS_WORDS ((PCM_TILE_BYTES + 4) / 4 + (PCM_TILE_BYTES + 4) / 128 + 2)
+
+__device__ __forceinline__ int pcm_lds(int byte) { return (((byte >> 2) + (byte >> 7)) << 2) | (byte & 3); }
+
+__global__ __launch_bounds__(PCM_THREADS) void pcm_to_float_kernel(const unsigned char* __restrict__ pcm, long long frames, int channels,
+                                                                   int width, int F, float* __restrict__ out) {
+  __shared__ unsigned int s_w[PCM_LDS_WORDS];
+  const unsigned char* s_b = reinterpret_cast<const unsigned char*>(s_w);
+  const int tid = threadIdx.x;
+  const long long f0 = (long long)blockIdx.x * F;
+  const int nf = (int)(frames - f0 < F ? frames - f0 : F);
+  const int fb = channels * width;
+  const unsigned char* src = pcm + (size_t)f0 * fb;
+  const int nbytes = nf * fb;                                        // <= PCM_TILE_BYTES
+  const int lead = (int)(reinterpret_cast<uintptr_t>(src) & 3);      // LDS byte `lead + o` = src[o]
+  const int nwords = (lead + nbytes + 3) >> 2;
+  for (int i = tid; i < nwords; i += PCM_THREADS) {
+    const int lo = 4 * i - lead;
+    unsigned int v = 0;
+    if (lo >= 0 && lo + 4 <= nbytes) {
+      v = *reinterpret_cast<const unsigned int*>(src + lo);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (lo + k >= 0 && lo + k < nbytes) v |= (unsigned int)src[lo + k] << (8 * k);
+    }
+    s_w[i + (i >> 5)] = v;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < channels * nf; idx += PCM_THREADS) {
+    const int c = idx / nf, f = idx - c * nf;
+    const int at = lead + (f * channels + c) * width;
+    const unsigned int b0 = s_b[pcm_lds(at)], b1 = s_b[pcm_lds(at + 1)];
+    float v;
+    if (width == 2) {
+      v = (float)(short)(b0 | (b1 << 8)) * (1.f / 32768.f);
+    } else if (width == 3) {
+      const unsigned int b2 = s_b[pcm_lds(at + 2)];
+      v = (float)((int)((b0 | (b1 << 8) | (b2 << 16)) << 8) >> 8) * (1.f / 8388608.f);
+    } else {
+      const unsigned int b2 = s_b[pcm_lds(at + 2)], b3 = s_b[pcm_lds(at + 3)];
+      v = (float)(int)(b0 | (b1 << 8) | (b2 << 16) | (b3 << 24)) * (1.f / 2147483648.f);      // (float)i rounds to nearest; 2^-31 is exact
+    }
+    out[(size_t)c * (size_t)frames + (size_t)(f0 + f)] = v;
+  }
+}
+
+extern "C" int mmd_pcm_to_float(const unsigned char* pcm, long long frames, int channels, int width, float* out, hipStream_t stream) {
+  if (!pcm || !out || frames < 1 || channels < 1 || (width != 2 && width != 3 && width != 4)) return MMD_EINVAL;
+  if (channels > PCM_TILE_BYTES / width || frames > (1ll << 50)) return MMD_EINVAL;
+  int F = PCM_TILE_BYTES / (channels * width);
+  F = F > PCM_FMAX ? PCM_FMAX : F;
+  const long long blocks = (frames + F - 1) / F;
+  if (blocks > 0x7fffffffll) return MMD_EINVAL;
+  hipLaunchKernelGGL(pcm_to_float_kernel, dim3((unsigned)blocks), dim3(PCM_THREADS), 0, stream, pcm, frames, channels, width, F, out);
+  return mmd_check_launch();
+}
