@@ -4,7 +4,7 @@
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
-                     [--resample | --sample_rate R]
+                     [--resample | --sample_rate R] [--chunk_s SECONDS]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -28,6 +28,12 @@ are in the file, are decoded there and resampled to 44.1 kHz (`mm_distillnet_amd
 does upstream, by this project's own windowed-sinc rule).  With --sample_rate R a `.npy` is taken to be at R Hz and resampled when
 R != 44100.  Everything behind that - the clip, --window_s and --track paths - runs unchanged on the 44.1 kHz waveforms; window and hop
 sizes and the CSV's times stay in seconds of the recording.  Without these two flags every input is read as described above.
+
+With --chunk_s X (only with --window_s) the recording is never whole in host or device memory: it is read X seconds at a time - a
+`.wav` with `wave.readframes`, its frames decoded on the device; a `.npy` through a memory map - and fed to a live session
+(`AudioDetector.open_stream`), which keeps a bounded ring of samples on the device and runs each group of --batch windows as soon as
+its last sample has arrived.  The CSV is byte for byte the one the same command writes without --chunk_s, with or without --track.
+--chunk_s does not go with --resample / --sample_rate (the resampler's filter history is not carried across chunks).
 """
 import argparse
 import csv
@@ -170,6 +176,65 @@ def stream_sizes(window_s: float, hop_s, n_total: int):
     return win_len, hop, len(stream_window_starts(n_total, win_len, hop))
 
 
+def check_chunk_flags(a):
+    """--chunk_s: what can be refused from the flags alone, before any device work"""
+    if a.chunk_s is None:
+        return
+    if a.window_s is None:
+        raise ValueError("--chunk_s feeds a live session that slides a window over the recording: it needs --window_s")
+    if a.resample or a.sample_rate is not None:
+        raise ValueError("--chunk_s does not go with --resample / --sample_rate: resampling needs the whole recording "
+                         "(the filter's history is not carried across chunks)")
+    if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
+        raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
+    if os.path.splitext(a.input)[1].lower() not in (".npy", ".wav"):
+        raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+
+
+def open_chunked(path: str, chunk: int):
+    """-> (n_total, chunks): the recording's length in samples and an iterator over it `chunk` samples at a time - (raw frames, 2) of a
+    16-bit `.wav` (for `LiveSession.push_pcm`), (float32 [8, n], None) of a `.npy` (for `push`).  The checks are `read_wav`'s and
+    `read_npy`'s; only one chunk is in host memory at a time."""
+    if os.path.splitext(path)[1].lower() == ".wav":
+        w = wave.open(path, "rb")
+        try:
+            if w.getframerate() != SAMPLE_RATE:
+                raise ValueError(f"{path}: sample rate {w.getframerate()} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
+            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
+                raise ValueError(f"{path}: only 16-bit PCM is supported, found {8 * w.getsampwidth()}-bit {w.getcomptype()}")
+            if w.getnchannels() != CHANNELS:
+                raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {w.getnchannels()}")
+        except ValueError:
+            w.close()
+            raise
+
+        def frames():
+            with w:
+                while True:
+                    raw = w.readframes(chunk)
+                    if len(raw) < 2 * CHANNELS:
+                        return
+                    yield raw[:len(raw) - len(raw) % (2 * CHANNELS)], 2
+        return w.getnframes(), frames()
+    m = np.load(path, mmap_mode="r", allow_pickle=False)
+    if m.dtype != np.float32:
+        raise ValueError(f"{path}: waveforms must be float32, found {m.dtype}")
+    if m.ndim == 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.ndim != 2 or m.shape[0] != CHANNELS:
+        raise ValueError(f"{path}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), found shape {m.shape}")
+    return m.shape[1], ((np.ascontiguousarray(m[:, i:i + chunk]), None) for i in range(0, m.shape[1], chunk))
+
+
+def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track):
+    """Feeds the chunks of `open_chunked` to a live session -> what `detect_stream` / `track_stream` return for the whole recording"""
+    session = det.open_stream(win_len, hop, batch=batch, track=track)
+    parts = [session.push(c) if width is None else session.push_pcm(c, width) for c, width in chunks]
+    parts.append(session.flush())
+    session.close()
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_file", required=True)
@@ -187,7 +252,9 @@ def main(argv=None):
     ap.add_argument("--track_max", type=int, default=64, help="live tracks at a time (1 .. 256)")
     ap.add_argument("--resample", action="store_true", help="a .wav of any rate, 16/24/32-bit PCM: decode and resample to 44.1 kHz on the device")
     ap.add_argument("--sample_rate", type=int, default=None, help="the rate in Hz of a .npy input; resampled to 44.1 kHz on the device")
+    ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
     a = ap.parse_args(argv)
+    check_chunk_flags(a)
     track = None
     if a.track:
         if a.window_s is None:
@@ -197,12 +264,15 @@ def main(argv=None):
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     dev = "cuda:0"
     resampled = a.resample or a.sample_rate is not None
-    if resampled:                             # the waveforms are made on the device: it is needed before the sizes are known
+    if a.chunk_s is not None:
+        n_total, chunks = open_chunked(a.input, int(round(a.chunk_s * SAMPLE_RATE)))
+        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, n_total)
+    elif resampled:                           # the waveforms are made on the device: it is needed before the sizes are known
         torch.cuda.set_device(0)
         waves = load_resampled(a, dev)
     else:
         waves = read_input(a.input)
-    if a.window_s is not None:
+    if a.window_s is not None and a.chunk_s is None:
         if waves.shape[0] != 1:
             raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
                              f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
@@ -212,15 +282,17 @@ def main(argv=None):
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
-    if not resampled:
+    if a.chunk_s is not None:
+        streamed = run_chunked(det, chunks, win_len, hop, a.batch, track)
+    elif not resampled:
         waves = torch.from_numpy(waves).to(dev)
     if track is not None:
-        rows, window, ids = det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
+        rows, window, ids = streamed if a.chunk_s is not None else det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
         n = write_track_csv(a.output, rows, window, ids, hop)
         print("%d windows, %d boxes, %d tracks -> %s" % (n_win, n, len(np.unique(ids[ids >= 0])), a.output))
         return rows, window, ids
     if a.window_s is not None:
-        rows, window = det.detect_stream(waves[0], win_len, hop, batch=a.batch)
+        rows, window = streamed if a.chunk_s is not None else det.detect_stream(waves[0], win_len, hop, batch=a.batch)
         n = write_stream_csv(a.output, rows, window, hop)
         print("%d windows, %d boxes -> %s" % (n_win, n, a.output))
         return rows, window

@@ -589,6 +589,19 @@ int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_
 // channels < 1, win_len <= 512 (too short for the padding), win_len > n_total, a bad band_stride or db outside {0, 1}.
 int mmd_melspec_windows(const float* wav, int channels, long long n_total, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
 
+// mmd_melspec_windows with the recording in a RING (live streaming detection, AudioDetector.open_stream; the melspectrogram call is
+// merge_audios', src/datasets/MultimodalDetection.py:329-353, the dB map mp3_to_pkl.py:31-41's): ring[channels, cap], absolute sample p
+// of channel c at ring[c * cap + p % cap]; win_start[batch] (DEVICE int64) are ABSOLUTE positions counted from the session's start.
+// Window b is samples win_start[b] .. win_start[b] + win_len - 1, read modulo cap; the reflect padding stays in window coordinates, so
+// for db = 0 and db = 1 the output is bit for bit what mmd_melspec_windows gives for that window of the linear recording (one kernel
+// body, one more mode: only the staging load's address differs - the start is reduced modulo cap once per block and every load wraps
+// with one compare and one subtract).  Nothing but the window's win_len slots per channel is read.  A negative start is the CALLER'S
+// ERROR (the kernel clamps it to 0: the wrong window, but no read leaves the ring); that the window's samples are still resident is
+// the caller's schedule.  Launch sequence, max_ws[batch * channels] and out as mmd_melspec_windows: they need no zeroing, two calls
+// give the same bits, no allocation, no host synchronisation.  -22 before any launch on the refusals of mmd_melspec_windows, and on
+// win_len > cap.
+int mmd_melspec_windows_ring(const float* ring, int channels, long long cap, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
+
 // ---- sample-rate conversion and PCM decoding (csrc/resample.hip): what librosa.load(path, sr=44100) does in front of the mel
 // spectrogram upstream (mp3_to_pkl.py:31; merge_audios, src/datasets/MultimodalDetection.py:335-336).
 // x[rows, n_in] at sr_in -> y[rows, n_out] at sr_out, rows = batch x channels, with L / M = sr_out / sr_in in lowest terms and
@@ -616,6 +629,26 @@ int mmd_resample_poly(const float* x, int rows, long long n_in, const float* ban
 // give the same bits.  Caps: channels * width <= 16384.  -22 before any launch on null pointers, frames < 1, channels < 1, another
 // width, or channels above the cap.
 int mmd_pcm_to_float(const unsigned char* pcm, long long frames, int channels, int width, float* out, hipStream_t stream);
+
+// ---- the device sample ring of live streaming detection (csrc/live.hip, AudioDetector.open_stream): chunks go in as they arrive,
+// mmd_melspec_windows_ring reads windows back out.  ring[channels, cap] float32 at a fixed address; absolute sample p (int64, counted
+// from the session's start) of channel c lives at ring[c * cap + p % cap].
+// ring[c, (pos + i) % cap] = src[c * src_stride + i] for i < n: n samples per channel from float rows src_stride apart (src_stride > n:
+// a column slice of a larger tensor).  pos is reduced modulo cap on the host and n <= cap, so a position wraps at most once: one
+// compare and one subtract per store, lanes store consecutive floats (two contiguous runs where the chunk crosses the ring's end).
+// One launch, plain vector stores, no atomics, no allocation, no host synchronisation; nothing outside those n positions per channel
+// is touched, two calls give the same bits.  Which older sample a store overwrites is the caller's schedule
+// (mm_distillnet_amd.audio.live_schedule).  Caps: channels <= 65535, cap and pos <= 2^50.  -22 before any launch on null pointers,
+// channels < 1, n < 1, n > cap, pos < 0, src_stride < n, or a size above the caps.
+int mmd_ring_push(const float* src, long long src_stride, int channels, long long n, float* ring, long long cap, long long pos, hipStream_t stream);
+
+// The same for a PCM WAV's frames as read from the file: pcm = interleaved little-endian SIGNED samples [frames, channels] of width
+// 2, 3 or 4 bytes (no alignment needed), decoded exactly as mmd_pcm_to_float decodes them - one tile body, the floats are bit for bit
+// the same - de-interleaved through LDS and stored at ring[c, (pos + f) % cap] for f < frames.  One launch, no atomics, no allocation,
+// no host synchronisation; nothing outside those positions is touched.  Caps as mmd_pcm_to_float (channels * width <= 16384) and as
+// mmd_ring_push.  -22 before any launch on null pointers, frames < 1, channels < 1, another width, channels above the cap,
+// frames > cap, pos < 0, or cap / pos above 2^50.
+int mmd_ring_push_pcm(const unsigned char* pcm, long long frames, int channels, int width, float* ring, long long cap, long long pos, hipStream_t stream);
 
 // ---- device-side detection record (csrc/stream.hip): the rows mmd_nms_teacher leaves for a group of windows, appended behind every
 // group with one host copy at the end of the recording (the shape of mmd_eval_match's record).

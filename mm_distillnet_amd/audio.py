@@ -75,6 +75,41 @@ def stream_window_starts(n_total: int, win_len: int, hop: int) -> list:
     return [w * hop for w in range(1 + (n_total - win_len) // hop)]
 
 
+def live_group_span(win_len: int, hop: int, batch: int) -> int:
+    """Samples from the first sample of a group of `batch` consecutive windows to its last: (batch - 1) * hop + win_len"""
+    return (int(batch) - 1) * int(hop) + int(win_len)
+
+
+def live_schedule(written: int, group: int, n: int, win_len: int, hop: int, batch: int, cap: int):
+    """What one push of n samples does to a live session's ring (`AudioDetector.open_stream`), as a list of steps in order:
+    ("write", lo, hi) - absolute samples lo .. hi-1 go into the ring (hi - lo <= cap) - and ("run", g) - group g, windows g * batch ..
+    g * batch + batch - 1, runs.  written: samples pushed so far; group: the next group to run.  -> (steps, written + n, next group).
+
+    Group g covers the samples S_g = g * batch * hop .. S_g + span - 1, span = `live_group_span`.  The rule: a group runs as soon as its
+    last sample is in, and a write never goes past S_g + cap for the next group g to run - the slot of sample p is that of p - cap, so
+    nothing at or behind S_g, which a pending window may still need, is overwritten (cap >= span lets every group complete).  Samples
+    in front of S_g are no window's any more (hop > win_len leaves such gaps between groups): they are skipped, not written.  The
+    groups and their order depend on the total pushed alone, never on how it was cut into chunks."""
+    written, group, n, hop, batch, cap = int(written), int(group), int(n), int(hop), int(batch), int(cap)
+    span = live_group_span(win_len, hop, batch)
+    if cap < span:
+        raise ValueError(f"a ring of {cap} samples is shorter than one group of {batch} windows ({span} samples)")
+    steps, end = [], written + n
+    while True:
+        start = group * batch * hop
+        while start + span <= written:
+            steps.append(("run", group))
+            group += 1
+            start += batch * hop
+        if written == end:
+            return steps, written, group
+        hi = min(end, start + cap)              # > written: the group at `start` has not run, so written < start + span <= start + cap
+        lo = max(written, start)
+        if lo < hi:
+            steps.append(("write", lo, hi))
+        written = hi
+
+
 class MelFrontEnd:
     """Holds the band-form filter bank on `device`; every call runs on the current stream and allocates only its result."""
 
@@ -113,6 +148,15 @@ class MelFrontEnd:
         C, n_total = wav.shape
         self.call("mmd_melspec_windows", wav, C, n_total, win_start, win_start.shape[0], int(win_len), self.start, self.length, self.band,
                   self.stride, 1 if db else 0, max_ws, out)
+        return out
+
+    def melspec_windows_ring_into(self, ring, win_start, win_len: int, db: bool, max_ws, out):
+        """`melspec_windows_into` for a ring of samples (`mmd_melspec_windows_ring`): ring [C, cap] holds absolute sample p at slot
+        p % cap, win_start int64 [B] on the device are absolute positions.  The bits are those of `melspec_windows_into` on the linear
+        recording."""
+        C, cap = ring.shape
+        self.call("mmd_melspec_windows_ring", ring, C, cap, win_start, win_start.shape[0], int(win_len), self.start, self.length,
+                  self.band, self.stride, 1 if db else 0, max_ws, out)
         return out
 
     def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None, db: bool = False) -> torch.Tensor:

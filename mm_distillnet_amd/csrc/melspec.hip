@@ -86,11 +86,18 @@ __device__ __forceinline__ void mel_dft16(float2 v[16]) {
 __device__ __forceinline__ int mel_pad(int i) { return i + (i >> 4); }
 
 // blockIdx.z = the sample of a batch ([B, C, N] waveforms -> [B, 80, T, C]); TRACK: also the block's maximum into mx_ws[sample * C + c]
-// WIN (mmd_melspec_windows): sample b is the window wav_a[:, win_start[b] : win_start[b] + N] of ONE recording wav_a[C, n_total]; only
+// WIN = MEL_WIN_LINEAR (mmd_melspec_windows): sample b is the window wav_a[:, win_start[b] : win_start[b] + N] of ONE recording wav_a[C, n_total]; only
 // the base pointer differs - every index below stays in window coordinates 0 .. N-1, so the reflection sees the window's own two ends
 // and the bits are those of the materialised [B, C, N] stack.  The start is clamped into [0, n_total - N]: a bad table reads the wrong
 // window, never outside the recording.
-template <bool MIX, bool TRACK, bool WIN>
+// WIN = MEL_WIN_RING (mmd_melspec_windows_ring): the recording is a ring wav_a[C, n_total] of n_total = cap slots per channel and
+// win_start[b] an ABSOLUTE sample position: window sample s lives at slot (win_start[b] + s) % cap.  The start is reduced modulo cap
+// once per block; s <= N - 1 < cap, so a slot wraps at most once: one compare and one subtract at the staging load, which is the only
+// line that differs.  A negative start is clamped to 0; every slot read is inside the channel's row.
+#define MEL_WIN_NONE 0
+#define MEL_WIN_LINEAR 1
+#define MEL_WIN_RING 2
+template <bool MIX, bool TRACK, int WIN>
 __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restrict__ wav_a, const float* __restrict__ wav_b, long long N,
                                                             int T, int C, const int* __restrict__ band_start,
                                                             const int* __restrict__ band_len, const float* __restrict__ band_w,
@@ -103,7 +110,12 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
   const int c = blockIdx.y, f0 = blockIdx.x * MEL_FPB;
   const size_t smp = blockIdx.z;
   const float* pa;
-  if (WIN) {
+  long long r0 = 0;                                  // MEL_WIN_RING: the window's first slot
+  if (WIN == MEL_WIN_RING) {
+    const long long w0 = win_start[smp];
+    r0 = w0 < 0 ? 0 : w0 % n_total;
+    pa = wav_a + (size_t)c * (size_t)n_total;
+  } else if (WIN == MEL_WIN_LINEAR) {
     long long w0 = win_start[smp];
     w0 = w0 < 0 ? 0 : (w0 > n_total - N ? n_total - N : w0);
     pa = wav_a + (size_t)c * (size_t)n_total + (size_t)w0;
@@ -123,6 +135,10 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
     s = s < 0 ? -s : s;
     s = s >= N ? 2 * (N - 1) - s : s;
     s = s < 0 ? 0 : (s > N - 1 ? N - 1 : s);
+    if (WIN == MEL_WIN_RING) {
+      s += r0;
+      s = s >= n_total ? s - n_total : s;
+    }
     float v = pa[s];
     if (MIX) v = (v + pb[s]) * 0.5f;
     s_x[i] = v;
@@ -298,10 +314,10 @@ extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int cha
   const dim3 grid(cdiv(T, MEL_FPB), channels), block(256);
   unsigned int* none = nullptr;
   if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<true, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
   else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
   return mmd_check_launch();
 }
@@ -332,16 +348,16 @@ extern "C" int mmd_melspec_batch(const float* wav_a, const float* wav_b, int bat
   unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
   if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
   if (wav_b && db)
-    hipLaunchKernelGGL((melspec_power_kernel<true, true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<true, true, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<true, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, false>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
   if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
   return mmd_check_launch();
@@ -361,11 +377,35 @@ extern "C" int mmd_melspec_windows(const float* wav, int channels, long long n_t
   const float* none = nullptr;
   if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
   if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true, true>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_LINEAR>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, win_start, n_total);
   else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, true>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_LINEAR>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
                        band_len, band_w, band_stride, out, mx, win_start, n_total);
+  if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
+  return mmd_check_launch();
+}
+
+// the ring mode of mmd_melspec_windows: same checks, same launch sequence, cap in n_total's place
+extern "C" int mmd_melspec_windows_ring(const float* ring, int channels, long long cap, const long long* win_start, int batch,
+                                        long long win_len, const int* band_start, const int* band_len, const float* band_w,
+                                        int band_stride, int db, float* max_ws, float* out, hipStream_t stream) {
+  if (!ring || !win_start || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 ||
+      batch > 65535)
+    return MMD_EINVAL;
+  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
+  const int T = mmd_melspec_frames(win_len);
+  if (T < 0 || win_len > cap) return MMD_EINVAL;
+  const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
+  unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
+  const float* none = nullptr;
+  if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
+  if (db)
+    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_RING>), grid, block, 0, stream, ring, none, win_len, T, channels,
+                       band_start, band_len, band_w, band_stride, out, mx, win_start, cap);
+  else
+    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_RING>), grid, block, 0, stream, ring, none, win_len, T, channels,
+                       band_start, band_len, band_w, band_stride, out, mx, win_start, cap);
   if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
   return mmd_check_launch();
 }

@@ -39,6 +39,7 @@
 // downsampling from 96 k or 192 k - four LDS reads per global load either way.  Plain stores, no atomics, fixed summation order: y
 // needs no zeroing and two launches give the same bits.
 #include "common.h"
+#include "pcm_tile.h"
 
 #define RS_THREADS 256
 #define RS_QT 4                                      // periods per thread
@@ -128,67 +129,17 @@ extern "C" int mmd_resample_poly(const float* x, int rows, long long n_in, const
   return mmd_check_launch();
 }
 
-// ---- interleaved little-endian signed PCM [frames, channels] of 2, 3 or 4 bytes -> float [channels, frames]: a transpose.
-// A block owns F consecutive frames (F * channels * width <= 16 KB).  It copies their bytes to LDS as aligned 32-bit words, lane i word i
-// (a word that straddles the tile's first or last byte is put together from byte loads, so nothing outside the tile is read, whatever
-// the buffer's alignment), then thread idx = c * F + f decodes sample (f, c) from LDS bytes and stores out[c, f0 + f]: the lanes of a
-// wave write consecutive floats.  In LDS they read channels * width bytes apart (16 bytes for eight 16-bit channels: every fourth bank,
-// 4 lanes of a 32-lane half on each); one pad word behind every 32 spreads such power-of-two strides over all banks.
-#define PCM_THREADS 256
-#define PCM_TILE_BYTES 16384
-#define PCM_FMAX 2048
-#define PCM_LDS_WORDS ((PCM_TILE_BYTES + 4) / 4 + (PCM_TILE_BYTES + 4) / 128 + 2)
-
-__device__ __forceinline__ int pcm_lds(int byte) { return (((byte >> 2) + (byte >> 7)) << 2) | (byte & 3); }
-
+// ---- interleaved little-endian signed PCM [frames, channels] of 2, 3 or 4 bytes -> float [channels, frames]: a transpose.  The tile
+// body (LDS staging, decoding) is pcm_tile.h's, shared with the ring writer of live.hip; here row c is out[c, :] and nothing wraps.
 __global__ __launch_bounds__(PCM_THREADS) void pcm_to_float_kernel(const unsigned char* __restrict__ pcm, long long frames, int channels,
                                                                    int width, int F, float* __restrict__ out) {
-  __shared__ unsigned int s_w[PCM_LDS_WORDS];
-  const unsigned char* s_b = reinterpret_cast<const unsigned char*>(s_w);
-  const int tid = threadIdx.x;
-  const long long f0 = (long long)blockIdx.x * F;
-  const int nf = (int)(frames - f0 < F ? frames - f0 : F);
-  const int fb = channels * width;
-  const unsigned char* src = pcm + (size_t)f0 * fb;
-  const int nbytes = nf * fb;                                        // <= PCM_TILE_BYTES
-  const int lead = (int)(reinterpret_cast<uintptr_t>(src) & 3);      // LDS byte `lead + o` = src[o]
-  const int nwords = (lead + nbytes + 3) >> 2;
-  for (int i = tid; i < nwords; i += PCM_THREADS) {
-    const int lo = 4 * i - lead;
-    unsigned int v = 0;
-    if (lo >= 0 && lo + 4 <= nbytes) {
-      v = *reinterpret_cast<const unsigned int*>(src + lo);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (lo + k >= 0 && lo + k < nbytes) v |= (unsigned int)src[lo + k] << (8 * k);
-    }
-    s_w[i + (i >> 5)] = v;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < channels * nf; idx += PCM_THREADS) {
-    const int c = idx / nf, f = idx - c * nf;
-    const int at = lead + (f * channels + c) * width;
-    const unsigned int b0 = s_b[pcm_lds(at)], b1 = s_b[pcm_lds(at + 1)];
-    float v;
-    if (width == 2) {
-      v = (float)(short)(b0 | (b1 << 8)) * (1.f / 32768.f);
-    } else if (width == 3) {
-      const unsigned int b2 = s_b[pcm_lds(at + 2)];
-      v = (float)((int)((b0 | (b1 << 8) | (b2 << 16)) << 8) >> 8) * (1.f / 8388608.f);
-    } else {
-      const unsigned int b2 = s_b[pcm_lds(at + 2)], b3 = s_b[pcm_lds(at + 3)];
-      v = (float)(int)(b0 | (b1 << 8) | (b2 << 16) | (b3 << 24)) * (1.f / 2147483648.f);      // (float)i rounds to nearest; 2^-31 is exact
-    }
-    out[(size_t)c * (size_t)frames + (size_t)(f0 + f)] = v;
-  }
+  pcm_tile_to_rows(pcm, frames, channels, width, F, out, frames, 0ll, 0x7fffffffffffffffll);
 }
 
 extern "C" int mmd_pcm_to_float(const unsigned char* pcm, long long frames, int channels, int width, float* out, hipStream_t stream) {
   if (!pcm || !out || frames < 1 || channels < 1 || (width != 2 && width != 3 && width != 4)) return MMD_EINVAL;
   if (channels > PCM_TILE_BYTES / width || frames > (1ll << 50)) return MMD_EINVAL;
-  int F = PCM_TILE_BYTES / (channels * width);
-  F = F > PCM_FMAX ? PCM_FMAX : F;
+  const int F = pcm_tile_frames(channels, width);
   const long long blocks = (frames + F - 1) / F;
   if (blocks > 0x7fffffffll) return MMD_EINVAL;
   hipLaunchKernelGGL(pcm_to_float_kernel, dim3((unsigned)blocks), dim3(PCM_THREADS), 0, stream, pcm, frames, channels, width, F, out);

@@ -12,7 +12,11 @@ static input buffers, as `DistillEngine.capture` / `replay` do for the training 
 `detect_stream` slides that chain over one long recording that stays on the device: the front end reads the overlapping windows straight
 out of it (`mmd_melspec_windows`), a device-side record collects every group's rows (`mmd_det_record_append`, csrc/stream.hip), and the
 host synchronises and copies once, at the end.  `track_stream` is the same stream with a tracker (`mmd_track_update`, csrc/track.hip) in
-front of every group's append: each row of the record also gets the id of its track."""
+front of every group's append: each row of the record also gets the id of its track.
+
+`open_stream` is the same chain for audio that ARRIVES: a `LiveSession` keeps a bounded ring of samples at a fixed device address
+(csrc/live.hip: `mmd_ring_push`, `mmd_ring_push_pcm`), the front end reads the windows out of it across the wrap
+(`mmd_melspec_windows_ring`), and one captured graph serves the whole session and every recording pushed through it."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -22,7 +26,7 @@ import torch
 
 from .arch import NetSpec
 from . import _lib
-from .audio import MelFrontEnd, stream_window_starts
+from .audio import MelFrontEnd, live_group_span, live_schedule, stream_window_starts
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -54,6 +58,9 @@ class AudioDetector:
         self._stream: Optional[dict] = None       # detect_stream's buffers and graph: ONE recording at a time (the graph bakes its address in)
         self.stream_captures = 0                  # graphs detect_stream captured
         self.stream_replays = 0                   # groups of windows detect_stream served by a captured graph
+        self._live: Optional["LiveSession"] = None     # open_stream's session; a stream and a session never coexist
+        self.live_captures = 0                    # graphs open_stream's sessions captured
+        self.live_replays = 0                     # groups of windows a session served by a captured graph
         self.last_cls: Optional[torch.Tensor] = None   # head outputs of the last call (views of the net's arena: valid until the next call)
         self.last_reg: Optional[torch.Tensor] = None
 
@@ -158,8 +165,12 @@ class AudioDetector:
 
     def _stream_chain(self, g: dict):
         """One group of windows: front end on the windows the control row names -> forward -> decode -> NMS [-> track update] -> append
-        to the record.  The track update reads the record's count before the append advances it."""
-        self.front.melspec_windows_into(g["wave"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
+        to the record.  The track update reads the record's count before the append advances it.  A live session's windows come out
+        of its ring (g["ring"]), a stream's out of the recording (g["wave"])."""
+        if g.get("ring") is not None:
+            self.front.melspec_windows_ring_into(g["ring"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
+        else:
+            self.front.melspec_windows_into(g["wave"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
         audio = self.front.resize_into(g["mel"], self.S, g["audio"])
         self._tail(audio, g)
         B = audio.shape[0]
@@ -221,6 +232,8 @@ class AudioDetector:
             raise ValueError("%s: batch = %d (1 .. 1024)" % (who, batch))
         starts = stream_window_starts(n_total, win_len, hop)
         W = len(starts)
+        if self._live is not None:
+            self._live.close()                    # one stream or session at a time
         if rec_cap is None:
             rec_cap = W * (self.cand_cap if self.cand_cap > 0 else self.STREAM_ROWS_PER_WINDOW)
         rec_cap = int(rec_cap)
@@ -295,6 +308,286 @@ class AudioDetector:
             raise RuntimeError(_tracker.overflow_message(track, window))
         return rows, window, g["rec_track"][:n].cpu().numpy()
 
+    def _overflow_message(self) -> str:
+        return "detection capacity exceeded (cand_cap = %d rows per image; 0 = unlimited)" % self.cand_cap
+
     def check_overflow(self):
         if int(self.overflow.item()):
-            raise RuntimeError("detection capacity exceeded (cand_cap = %d rows per image; 0 = unlimited)" % self.cand_cap)
+            raise RuntimeError(self._overflow_message())
+
+    # ------------------------------------------------------------------ live streaming
+    @torch.no_grad()
+    def open_stream(self, win_len: int, hop: int, batch: int = 8, track: Optional[TrackConfig] = None,
+                    ring_len: Optional[int] = None) -> "LiveSession":
+        """Opens a live session: `detect_stream` / `track_stream` (track: a TrackConfig) for audio that arrives in chunks - see
+        `LiveSession`.  win_len, hop, batch as `detect_stream`.  ring_len: samples per channel the session keeps on the device, at
+        least one group's span (batch - 1) * hop + win_len (ValueError below that); default TWICE that span - the least is the span
+        itself, a second one lets a push of up to a span go in as one ring write while the group before it is still pending, and
+        the ring stays small against everything else the detector holds (8 channels x 2 x 1.7 s at 44.1 kHz: 4.8 MB for one-second
+        windows every 0.1 s in groups of 8).  The detector holds one stream or session at a time: opening one closes the session
+        before it and drops `detect_stream`'s buffers, and a later `detect_stream` / `track_stream` closes the session."""
+        if track is not None and not isinstance(track, TrackConfig):
+            raise ValueError("open_stream: track must be a TrackConfig or None")
+        if self._live is not None:
+            self._live.close()
+        self._stream = None
+        self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len)
+        return self._live
+
+
+class LiveSession:
+    """A recording that arrives in chunks (`AudioDetector.open_stream`).  `push` / `push_pcm` write a chunk into a ring of samples on the
+    device and return the results of the windows the chunk COMPLETED - (rows float32 [R, 6], window int32 [R]), with tracking also
+    track int32 [R], in the dtypes and order of `detect_stream` / `track_stream`; window indices count from the start of the recording
+    - or empty arrays; `flush` ends the recording; `reset` starts the next one; `close` releases the buffers.
+
+    Grouping does not depend on chunking.  Windows run in groups of exactly `batch` consecutive windows, in window order; a group
+    runs as soon as its last sample has been pushed; only `flush` runs a shorter group (padded by repeating its last window, the
+    padding not recorded) and drops a tail shorter than a window.  These are the groups `detect_stream` forms over the whole
+    recording, and equal groups give equal bits: for ANY way of cutting a recording into chunks, what the pushes and `flush` return,
+    concatenated, is bit for bit what `detect_stream` / `track_stream` return for the whole recording at the same win_len, hop, batch,
+    tracker settings and detector.  (Nothing more is promised: another batch gives other groups.)  Results therefore come up to
+    `batch` windows late: batch = 1 is the low-latency setting.
+
+    The ring (`audio.live_schedule`) holds absolute sample p at slot p % ring_len.  A push alternates ring writes and group runs, and
+    a write never passes the first sample of the next group to run plus ring_len, so no sample a pending window needs is overwritten
+    whatever the chunk's length - also one longer than the ring.  With hop > win_len the samples between groups are skipped.
+
+    One graph of the chain ring front end -> resize -> forward -> decode -> NMS [-> track update] -> record append is captured when
+    the session opens (`AudioDetector.live_captures`; with use_graph = False the chain runs eagerly); the ring, the control row and the record keep their addresses, so it serves
+    every group of every recording of the session.  The record holds the rows of ONE group (batch x cand_cap, or batch x
+    STREAM_ROWS_PER_WINDOW with cand_cap = 0); a group with more raises the RuntimeError of `detect_stream`.
+
+    Synchronisation: a push that completes no group only queues its ring write and returns.  A push that completes a group waits for
+    the device once, at its end, behind ONE copy of the record (rows, windows, track ids and count are one block of memory) and the
+    two overflow flags into pinned host memory.  A push that completes several groups empties the record that way before each further
+    group.  Host chunks go through two pinned staging buffers used in turn; before a buffer is written again the session waits for
+    the event behind the copy that last read it - two pushes back - never for the detection chain.  The control rows of a push's
+    groups lie in one pinned table that is only rewritten after that push's final wait."""
+
+    def __init__(self, det: AudioDetector, win_len: int, hop: int, batch: int, track: Optional[TrackConfig], ring_len: Optional[int]):
+        C = det.net.spec.in_channels
+        if hop < 1:
+            raise ValueError("open_stream: hop = %d: the windows must advance by at least one sample" % hop)
+        if batch < 1 or batch > 1024:
+            raise ValueError("open_stream: batch = %d (1 .. 1024)" % batch)
+        n_frames = det.front.n_frames(win_len)    # raises on a window too short for the reflect padding
+        span = live_group_span(win_len, hop, batch)
+        cap = 2 * span if ring_len is None else int(ring_len)
+        if cap < span:
+            raise ValueError("open_stream: ring_len = %d is shorter than one group of %d windows (%d samples)" % (cap, batch, span))
+        self.det, self.track, self.C, self.win_len, self.hop, self.batch, self.ring_len = det, track, C, win_len, hop, batch, cap
+        self.written, self.group, self.flushed, self.closed = 0, 0, False, False
+        dev = det.device
+        rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
+        if rec_cap > 0x7fffffff // 8:
+            raise ValueError("open_stream: a record of %d rows" % rec_cap)
+        self.rec_cap = rec_cap
+        # the record as ONE block of int32 words: rows [rec_cap, 6] (float bits), window [rec_cap], track [rec_cap], {count, overflow}
+        blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, device=dev)
+        self._blob, self._h_blob = blob, torch.zeros(8 * rec_cap + 2, dtype=torch.int32, pin_memory=True)
+        self._h_flags = torch.zeros(3, dtype=torch.int32, pin_memory=True)       # detector overflow; tracker {next_id, overflow}
+        cur = torch.zeros(batch + 1, dtype=torch.int64, device=dev)
+        self.g = g = {"track": track, "ring": torch.zeros(C, cap, device=dev), "win_len": win_len, "rec_cap": rec_cap, "cur": cur,
+                      "starts": cur[:batch], "ctl": cur[batch:].view(torch.int32),
+                      "mel": torch.empty(batch, det.front.n_mels, n_frames, C, device=dev),
+                      "max_ws": torch.empty(batch * C, device=dev), "audio": torch.empty(batch, C, det.S, det.S, device=dev),
+                      "rec_rows": blob[:6 * rec_cap].view(torch.float32).view(rec_cap, 6), "rec_win": blob[6 * rec_cap:7 * rec_cap],
+                      "rec_track": blob[7 * rec_cap:8 * rec_cap], "rec_state": blob[8 * rec_cap:]}
+        if track is not None:
+            g["trk_state"] = _tracker.new_state(dev, track)
+        self._h_ctl = torch.zeros(1, batch + 1, dtype=torch.int64, pin_memory=True)
+        self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
+        self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
+        self._pushes = 0
+        # a warm-up group on the zeroed ring sizes the arenas; its control row says 0 real windows: nothing is recorded or tracked
+        arenas = (det.ws, det.net.arena, det.net.zarena)
+        for a in arenas:
+            a.frozen = False                      # chunks are only ever appended: the graphs of `_detect` stay valid
+        det._stream_chain(g)
+        torch.cuda.synchronize()
+        for a in arenas:
+            a.frozen = True
+        self._zero_state()
+        if det.use_graph:
+            self._capture()
+
+    def _capture(self):
+        det, g = self.det, self.g
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            det._stream_chain(g)
+        torch.cuda.synchronize()
+        g["graph"] = graph
+        det.live_captures += 1
+
+    # ---- state
+    def _check_open(self, pushing: bool = False):
+        if self.closed:
+            raise RuntimeError("this live session is closed (the detector holds one stream or session at a time)")
+        if pushing and self.flushed:
+            raise RuntimeError("the recording was flushed: reset() starts the next one")
+
+    def _zero_state(self):
+        self.g["rec_state"].zero_()
+        if self.track is not None:
+            for t in self.g["trk_state"]:
+                t.zero_()
+
+    def reset(self):
+        """Starts a new recording on the same session: position 0, window 0, the tracker zeroed (ids start at 0 again); the graph, the
+        ring and every buffer stay (the ring needs no clearing: no window reads a slot this recording has not written)."""
+        self._check_open()
+        self.written, self.group, self.flushed = 0, 0, False
+        self._zero_state()
+
+    def close(self):
+        """Releases the session's buffers and graph."""
+        if not self.closed:
+            torch.cuda.synchronize()
+            self.closed = True
+            self.g = self._blob = self._h_blob = self._stage = None
+            if self.det._live is self:
+                self.det._live = None
+
+    # ---- one group
+    def _control_rows(self, rows: list) -> torch.Tensor:
+        """rows: (starts [<= batch], first_window) per group -> the pinned table, one row per group as `_run_stream` lays it out: int64
+        starts[batch] (the last window repeated up to batch), then {n_valid, first_window} as two int32 in the last word"""
+        if self._h_ctl.shape[0] < len(rows):
+            self._h_ctl = torch.zeros(len(rows), self.batch + 1, dtype=torch.int64, pin_memory=True)
+        table = self._h_ctl.numpy()
+        tail = table.view(np.int32).reshape(table.shape[0], 2 * (self.batch + 1))[:, 2 * self.batch:]
+        for k, (real, first) in enumerate(rows):
+            table[k, :self.batch] = real + [real[-1]] * (self.batch - len(real))
+            tail[k] = (len(real), first)
+        return self._h_ctl
+
+    def _run_group(self, row: torch.Tensor):
+        det, g = self.det, self.g
+        if det.use_graph and "graph" not in g:
+            self._capture()                       # the session was opened with use_graph = False
+        g["cur"].copy_(row, non_blocking=True)
+        if det.use_graph:
+            g["graph"].replay()
+            det.live_replays += 1
+        else:
+            det._stream_chain(g)
+
+    def _drain(self):
+        """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
+        det, g, R = self.det, self.g, self.rec_cap
+        self._h_blob.copy_(self._blob, non_blocking=True)
+        self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
+        if self.track is not None:
+            self._h_flags[1:3].copy_(g["trk_state"][1], non_blocking=True)
+        g["rec_state"].zero_()
+        torch.cuda.synchronize()
+        det.last_cls, det.last_reg = g["cls"], g["reg"]
+        h = self._h_blob.numpy()
+        n, over = int(h[8 * R]), int(h[8 * R + 1])
+        if int(self._h_flags[0]):
+            raise RuntimeError(det._overflow_message())
+        if over or n > R:
+            raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, R))
+        rows, window = h[:6 * n].view(np.float32).reshape(n, 6).copy(), h[6 * R:6 * R + n].copy()
+        if self.track is None:
+            return rows, window
+        if int(self._h_flags[2]):
+            raise RuntimeError(_tracker.overflow_message(self.track, window))
+        return rows, window, h[7 * R:7 * R + n].copy()
+
+    def _result(self, parts: list):
+        if not parts:
+            parts = [(np.zeros((0, 6), np.float32), np.zeros(0, np.int32)) + ((np.zeros(0, np.int32),) if self.track is not None else ())]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
+
+    @torch.no_grad()
+    def _advance(self, n: int, write):
+        """the schedule of one push of n samples; write(offset into the chunk, samples, absolute position) queues one ring write"""
+        steps, written, group = live_schedule(self.written, self.group, n, self.win_len, self.hop, self.batch, self.ring_len)
+        runs = [s[1] for s in steps if s[0] == "run"]
+        table = self._control_rows([([(gi * self.batch + i) * self.hop for i in range(self.batch)], gi * self.batch) for gi in runs])
+        parts, k = [], 0
+        for st in steps:
+            if st[0] == "write":
+                write(st[1] - self.written, st[2] - st[1], st[1])
+            else:
+                if k:
+                    parts.append(self._drain())   # the record holds one group
+                self._run_group(table[k])
+                k += 1
+        self.written, self.group = written, group
+        if k:
+            parts.append(self._drain())
+        return self._result(parts)
+
+    # ---- chunks
+    def _to_device(self, host: torch.Tensor) -> torch.Tensor:
+        """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
+        k = self._pushes & 1
+        self._pushes += 1
+        nbytes = host.numel() * host.element_size()
+        self._stage_ev[k].synchronize()           # the copy that last read this buffer (two pushes back) is done
+        if self._stage[k] is None or self._stage[k].numel() < nbytes:
+            self._stage[k] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+        pinned = self._stage[k][:nbytes].view(host.dtype).view(host.shape)
+        pinned.copy_(host)
+        dev = pinned.to(self.det.device, non_blocking=True)
+        self._stage_ev[k].record()
+        return dev
+
+    def push(self, chunk):
+        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of every microphone"""
+        self._check_open(pushing=True)
+        if isinstance(chunk, np.ndarray):
+            if chunk.dtype != np.float32:
+                raise ValueError("push takes float32 [%d, n] samples, found %s" % (self.C, chunk.dtype))
+            chunk = torch.from_numpy(chunk if chunk.flags.writeable else chunk.copy())
+        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.dtype != torch.float32 or chunk.shape[0] != self.C or \
+                chunk.shape[1] < 1:
+            raise ValueError("push takes float32 [%d, n] samples, n >= 1" % self.C)
+        if not chunk.is_cuda:
+            chunk = self._to_device(chunk)
+        elif chunk.stride(1) != 1 or chunk.stride(0) < chunk.shape[1]:
+            chunk = chunk.contiguous()
+        ptr, stride, ring = chunk.data_ptr(), chunk.stride(0), self.g["ring"]
+        return self._advance(chunk.shape[1], lambda off, cnt, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt, ring,
+                                                                             self.ring_len, pos))
+
+    def push_pcm(self, raw, width: int):
+        """raw: bytes, a bytearray or a uint8 tensor (host or device) of whole frames of interleaved little-endian signed PCM, 8 channels
+        of `width` = 2, 3 or 4 bytes, as `wave.readframes` returns them; decoded on the device exactly as `Resampler.pcm_to_float`
+        decodes (`mmd_ring_push_pcm`).  Otherwise as `push`."""
+        self._check_open(pushing=True)
+        width = int(width)
+        if width not in (2, 3, 4):
+            raise ValueError("push_pcm: width = %d (2, 3 or 4 bytes per sample)" % width)
+        if isinstance(raw, (bytes, bytearray, memoryview)):
+            raw = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy())
+        if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() != 1:
+            raise ValueError("push_pcm takes bytes, a bytearray or a one-dimensional uint8 tensor")
+        fb = self.C * width
+        if raw.numel() < fb or raw.numel() % fb:
+            raise ValueError("push_pcm: %d bytes are not whole frames of %d x %d bytes" % (raw.numel(), self.C, width))
+        raw = raw.contiguous() if raw.is_cuda else self._to_device(raw)
+        ptr, ring = raw.data_ptr(), self.g["ring"]
+        return self._advance(raw.numel() // fb, lambda off, cnt, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C, width,
+                                                                                ring, self.ring_len, pos))
+
+    @torch.no_grad()
+    def flush(self):
+        """Ends the recording: runs the last, shorter group - the complete windows no full group took, padded by repeating the last one
+        - and returns its results; a tail shorter than a window is dropped, as `detect_stream` drops it.  Afterwards only `reset` or
+        `close`."""
+        self._check_open()
+        if self.flushed:
+            return self._result([])
+        self.flushed = True
+        W = 0 if self.written < self.win_len else 1 + (self.written - self.win_len) // self.hop
+        first = self.group * self.batch
+        if W <= first:
+            return self._result([])
+        table = self._control_rows([([w * self.hop for w in range(first, W)], first)])
+        self._run_group(table[0])
+        return self._result([self._drain()])
