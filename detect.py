@@ -4,7 +4,7 @@
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
-                     [--resample | --sample_rate R] [--chunk_s SECONDS]
+                     [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -33,7 +33,15 @@ With --chunk_s X (only with --window_s) the recording is never whole in host or 
 `.wav` with `wave.readframes`, its frames decoded on the device; a `.npy` through a memory map - and fed to a live session
 (`AudioDetector.open_stream`), which keeps a bounded ring of samples on the device and runs each group of --batch windows as soon as
 its last sample has arrived.  The CSV is byte for byte the one the same command writes without --chunk_s, with or without --track.
---chunk_s does not go with --resample / --sample_rate (the resampler's filter history is not carried across chunks).
+--chunk_s does not go with --resample / --sample_rate: it reads 44.1 kHz input only.
+
+With --live_s X (only with --window_s, not with --chunk_s) a recording of ANY rate is read X seconds - round(X * R) frames - at a time
+at its own rate R and fed to a live session that resamples as the chunks arrive (`AudioDetector.open_stream(sample_rate=R)`: the
+resampler's filter history is carried across chunks in a ring of input samples on the device).  A `.wav`: 8 channels of 16-, 24- or
+32-bit PCM, R from its header (--resample alongside is allowed and changes nothing); a `.npy` of shape [8, N]: through a memory map, at
+--sample_rate R (default 44100).  Window count and CSV times are those of the ceil(N * 44100 / R) resampled samples, and the CSV is
+byte for byte the one --resample --window_s ... (for a `.npy`: --sample_rate R --window_s ...) writes for the same file, with or
+without --track.
 """
 import argparse
 import csv
@@ -183,12 +191,71 @@ def check_chunk_flags(a):
     if a.window_s is None:
         raise ValueError("--chunk_s feeds a live session that slides a window over the recording: it needs --window_s")
     if a.resample or a.sample_rate is not None:
-        raise ValueError("--chunk_s does not go with --resample / --sample_rate: resampling needs the whole recording "
-                         "(the filter's history is not carried across chunks)")
+        raise ValueError("--chunk_s does not go with --resample / --sample_rate: it reads 44.1 kHz input only "
+                         "(--live_s reads a recording of any rate a chunk at a time and resamples it as it arrives)")
     if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
         raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
     if os.path.splitext(a.input)[1].lower() not in (".npy", ".wav"):
         raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+
+
+def check_live_flags(a):
+    """--live_s: what can be refused from the flags alone, before any device work"""
+    if a.live_s is None:
+        return
+    if a.window_s is None:
+        raise ValueError("--live_s feeds a live session that slides a window over the recording: it needs --window_s")
+    if a.chunk_s is not None:
+        raise ValueError("--live_s does not go with --chunk_s: one of the two says how the recording is cut into chunks")
+    if not a.live_s > 0:
+        raise ValueError(f"--live_s {a.live_s}: a positive number of seconds (at least one frame)")
+    ext = os.path.splitext(a.input)[1].lower()
+    if ext not in (".npy", ".wav"):
+        raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms at --sample_rate, or an 8-channel PCM .wav of any rate)")
+    if ext == ".wav" and a.sample_rate is not None:
+        raise ValueError(f"{a.input}: a .wav holds its rate: --live_s reads it from the header (--sample_rate R is for a .npy)")
+    if ext == ".npy" and a.resample:
+        raise ValueError(f"{a.input}: --resample reads a .wav; --live_s takes a .npy at --sample_rate R")
+    rate = SAMPLE_RATE if a.sample_rate is None else a.sample_rate
+    if rate < 1:
+        raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
+    if ext == ".npy" and int(round(a.live_s * rate)) < 1:
+        raise ValueError(f"--live_s {a.live_s}: a positive number of seconds (at least one frame)")
+
+
+def open_live(path: str, live_s: float, sample_rate=None):
+    """-> (n_frames, rate, chunks): the recording's length in frames at its own rate in Hz and an iterator over it round(live_s * rate)
+    frames at a time - (raw frames, bytes per sample) of a 16-, 24- or 32-bit PCM `.wav` of any rate (for `LiveSession.push_pcm`; the
+    checks are `read_recording`'s), (float32 [8, n], None) of a `.npy` taken to be at sample_rate (default 44100; for `push`).  Only
+    one chunk is in host memory at a time."""
+    if os.path.splitext(path)[1].lower() == ".wav":
+        w = wave.open(path, "rb")
+        try:
+            width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
+            if w.getcomptype() != "NONE" or width not in (2, 3, 4):
+                raise ValueError(f"{path}: only 16-, 24- or 32-bit PCM is supported, found {8 * width}-bit {w.getcomptype()}")
+            if channels != CHANNELS:
+                raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
+            if rate < 1:
+                raise ValueError(f"{path}: sample rate {rate} Hz")
+            chunk = int(round(live_s * rate))
+            if chunk < 1:
+                raise ValueError(f"--live_s {live_s}: a positive number of seconds (at least one frame at {rate} Hz)")
+        except ValueError:
+            w.close()
+            raise
+
+        def frames():
+            with w:
+                while True:
+                    raw = w.readframes(chunk)
+                    if len(raw) < width * CHANNELS:
+                        return
+                    yield raw[:len(raw) - len(raw) % (width * CHANNELS)], width
+        return w.getnframes(), rate, frames()
+    rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
+    n_total, chunks = open_chunked(path, int(round(live_s * rate)))
+    return n_total, rate, chunks
 
 
 def open_chunked(path: str, chunk: int):
@@ -226,9 +293,10 @@ def open_chunked(path: str, chunk: int):
     return m.shape[1], ((np.ascontiguousarray(m[:, i:i + chunk]), None) for i in range(0, m.shape[1], chunk))
 
 
-def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track):
-    """Feeds the chunks of `open_chunked` to a live session -> what `detect_stream` / `track_stream` return for the whole recording"""
-    session = det.open_stream(win_len, hop, batch=batch, track=track)
+def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track, sample_rate=None):
+    """Feeds the chunks of `open_chunked` / `open_live` (those at sample_rate) to a live session -> what `detect_stream` /
+    `track_stream` return for the whole recording (resampled to 44.1 kHz)"""
+    session = det.open_stream(win_len, hop, batch=batch, track=track, sample_rate=sample_rate)
     parts = [session.push(c) if width is None else session.push_pcm(c, width) for c, width in chunks]
     parts.append(session.flush())
     session.close()
@@ -253,8 +321,10 @@ def main(argv=None):
     ap.add_argument("--resample", action="store_true", help="a .wav of any rate, 16/24/32-bit PCM: decode and resample to 44.1 kHz on the device")
     ap.add_argument("--sample_rate", type=int, default=None, help="the rate in Hz of a .npy input; resampled to 44.1 kHz on the device")
     ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
+    ap.add_argument("--live_s", type=float, default=None, help="read a recording of any rate this many seconds at a time into a live session that resamples (with --window_s)")
     a = ap.parse_args(argv)
     check_chunk_flags(a)
+    check_live_flags(a)
     track = None
     if a.track:
         if a.window_s is None:
@@ -264,7 +334,12 @@ def main(argv=None):
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     dev = "cuda:0"
     resampled = a.resample or a.sample_rate is not None
-    if a.chunk_s is not None:
+    chunked, rate = a.chunk_s is not None or a.live_s is not None, None
+    if a.live_s is not None:
+        from mm_distillnet_amd.audio import resample_len
+        n_frames, rate, chunks = open_live(a.input, a.live_s, a.sample_rate)
+        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, resample_len(n_frames, rate, SAMPLE_RATE))
+    elif a.chunk_s is not None:
         n_total, chunks = open_chunked(a.input, int(round(a.chunk_s * SAMPLE_RATE)))
         win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, n_total)
     elif resampled:                           # the waveforms are made on the device: it is needed before the sizes are known
@@ -272,7 +347,7 @@ def main(argv=None):
         waves = load_resampled(a, dev)
     else:
         waves = read_input(a.input)
-    if a.window_s is not None and a.chunk_s is None:
+    if a.window_s is not None and not chunked:
         if waves.shape[0] != 1:
             raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
                              f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
@@ -282,17 +357,17 @@ def main(argv=None):
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
-    if a.chunk_s is not None:
-        streamed = run_chunked(det, chunks, win_len, hop, a.batch, track)
+    if chunked:
+        streamed = run_chunked(det, chunks, win_len, hop, a.batch, track, rate)
     elif not resampled:
         waves = torch.from_numpy(waves).to(dev)
     if track is not None:
-        rows, window, ids = streamed if a.chunk_s is not None else det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
+        rows, window, ids = streamed if chunked else det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
         n = write_track_csv(a.output, rows, window, ids, hop)
         print("%d windows, %d boxes, %d tracks -> %s" % (n_win, n, len(np.unique(ids[ids >= 0])), a.output))
         return rows, window, ids
     if a.window_s is not None:
-        rows, window = streamed if a.chunk_s is not None else det.detect_stream(waves[0], win_len, hop, batch=a.batch)
+        rows, window = streamed if chunked else det.detect_stream(waves[0], win_len, hop, batch=a.batch)
         n = write_stream_csv(a.output, rows, window, hop)
         print("%d windows, %d boxes -> %s" % (n_win, n, a.output))
         return rows, window

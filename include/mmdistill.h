@@ -650,6 +650,33 @@ int mmd_ring_push(const float* src, long long src_stride, int channels, long lon
 // frames > cap, pos < 0, or cap / pos above 2^50.
 int mmd_ring_push_pcm(const unsigned char* pcm, long long frames, int channels, int width, float* ring, long long cap, long long pos, hipStream_t stream);
 
+// Resampling for a live session whose source is not at 44.1 kHz (AudioDetector.open_stream(sample_rate=R); upstream resamples whole
+// files with librosa.load(path, sr=44100), mp3_to_pkl.py:31): mmd_resample_poly's rule from a ring into a ring.  in_ring[channels,
+// in_cap] holds the input-rate samples as the two writers above leave them, absolute input sample p at in_ring[c * in_cap + p % cap]
+// with cap = in_cap; n_valid = input samples pushed so far.  The outputs t_lo .. t_hi-1 (absolute, at the output rate) are stored at
+// out_ring[c * out_cap + t % cap] with cap = out_cap - the ring mmd_melspec_windows_ring reads.  bank, phase_off, L, M, taps as
+// mmd_resample_poly takes them (the same DEVICE tables, the same caller's duty):
+//   y[t] = sum_{j < taps} bank[j * L + r] * x[n + j - taps / 2 + 1],  t = q * L + r,  n = q * M + phase_off[r],
+// acc = 0, then acc = fmaf(w, x, acc) for j = 0 .. taps-1 over ALL taps; x[i] enters as 0.f for i < 0 and for i >= n_valid (multiplied,
+// not skipped), so every output has bit for bit the value mmd_resample_poly gives it for a recording of n_valid samples whose tail
+// is in the ring - once its last input (t * M) / L + taps / 2 has been pushed, for any n_valid; before that, the value for the
+// recording that ENDS at n_valid (what a flush wants).  One tile body with that kernel (csrc/resample_tile.h).  [t_lo, t_hi) need not
+// be period-aligned: outputs outside it are masked.  Both moduli are taken on the host once; loads and stores wrap with one compare
+// and one subtract (t_hi - t_lo <= out_cap: a store wraps once), the device divides nothing and only q * M, q * L and the row offsets
+// are 64-bit.  One launch, plain vector stores, no atomics, no allocation, no host synchronisation; nothing outside those t_hi - t_lo
+// slots per channel is written, nothing outside in_ring is read, two calls give the same bits.  That no input the range needs has
+// been overwritten is checked as far as the host can: the range's oldest input, (t_lo * M) / L - taps / 2 + 1, must be at or behind
+// n_valid - in_cap (a negative index counts like any other: a range that starts before the recording needs that much room).  Caps: channels <= 65535, L, M, taps as mmd_resample_poly, in_cap, out_cap, n_valid, t_hi <= 2^50, in_cap >=
+// mmd_ring_resample_span(L, M, taps), the least input span a block stages.  -22 before any launch on null pointers, channels outside
+// 1 .. 65535, L or M outside 1 .. 1024, taps odd or outside 2 .. 4096, in_cap < 1, out_cap < 1, n_valid < 0, t_lo < 0, t_hi <= t_lo,
+// t_hi - t_lo > out_cap, a cap or position above 2^50, in_cap below the staged span, or an oldest input that is no longer in the ring.
+int mmd_ring_resample(const float* in_ring, long long in_cap, int channels, long long n_valid, const float* bank, const int* phase_off, int L, int M, int taps, float* out_ring, long long out_cap, long long t_lo, long long t_hi, hipStream_t stream);
+
+// The least in_cap mmd_ring_resample takes for L, M, taps: the input span (floats per channel) of a block of ONE period, taps + the
+// phase offsets' spread inside a tile of <= 64 phases (at most M).  A block stages as many periods as fit in min(in_cap, 12288)
+// floats, so a small ring costs blocks, never bits.  Host only, no launch; -22 on L or M outside 1 .. 1024, taps odd or outside 2 .. 4096.
+int mmd_ring_resample_span(int L, int M, int taps);
+
 // ---- device-side detection record (csrc/stream.hip): the rows mmd_nms_teacher leaves for a group of windows, appended behind every
 // group with one host copy at the end of the recording (the shape of mmd_eval_match's record).
 // rows[B, cap_img, 6] / cnt[B]: decode / NMS output (counts are clamped to 0 .. cap_img).  ctl[2] (DEVICE) = {n_valid, first_window}:

@@ -204,25 +204,55 @@ def resample_len(n_in: int, sr_in: int, sr_out: int = 44100) -> int:
     return -((-int(n_in) * f.numerator) // f.denominator)
 
 
-def resample_bank(sr_in: int, sr_out: int = 44100):
-    """-> (L, M, half, bank float32 [L, 2 * half], phase_off int32 [L]) for sr_in -> sr_out.
-
-    L / M = sr_out / sr_in in lowest terms, scale = min(1, L / M), half = ceil(64 / scale).  bank[p][j] = h(p / L - k) at k = j - half + 1
-    with h(tau) = scale * rolloff * sinc(scale * rolloff * tau) * kaiser(tau * scale / 64), computed in float64 (the argument as the one
-    quotient (p - k L) / L) and rounded once: output t is sum_j bank[(t M) % L][j] * x[(t M) // L + j - half + 1].  phase_off[r] =
-    (r * M) // L is the input offset of output phase r = t % L inside its period.  Raises ValueError, naming the reduced ratio, for what
-    `mmd_resample_poly` does not take: L or M above 1024, or more than 4096 taps (M / L above 32)."""
+def resample_ratio(sr_in: int, sr_out: int = 44100):
+    """-> (L, M, half): L / M = sr_out / sr_in in lowest terms, half = ceil(64 / min(1, L / M)) - a filter of 2 * half taps.  Raises
+    ValueError, naming the reduced ratio, for what `mmd_resample_poly` does not take: L or M above 1024, or more than 4096 taps (M / L
+    above 32)."""
     if int(sr_in) < 1 or int(sr_out) < 1:
         raise ValueError(f"sample rates must be positive, found {sr_in} -> {sr_out}")
     f = Fraction(int(sr_out), int(sr_in))
     L, M = f.numerator, f.denominator
     if L > RS_MAX_FACTOR or M > RS_MAX_FACTOR:
         raise ValueError(f"{sr_in} Hz -> {sr_out} Hz reduces to the ratio {L} / {M}: factors above {RS_MAX_FACTOR} are not supported")
-    scale = 1.0 if L >= M else L / M
     half = RS_ZEROS if L >= M else -((-RS_ZEROS * M) // L)
     if 2 * half > RS_MAX_TAPS:
         raise ValueError(f"{sr_in} Hz -> {sr_out} Hz reduces to the ratio {L} / {M}: its filter has {2 * half} taps, "
                          f"more than {RS_MAX_TAPS} (a reduction by more than {RS_MAX_TAPS // (2 * RS_ZEROS)} is not supported)")
+    return L, M, half
+
+
+def live_resample_ready(n_pushed: int, L: int, M: int, half: int, final: bool = False) -> int:
+    """Outputs 0 .. ready-1 of the resampler that a live session can compute once n_pushed input samples have arrived.  Output t reads
+    the inputs (t * M) // L - half + 1 .. (t * M) // L + half.  Not final: every t whose LAST tap is in, (t * M) // L + half <= n_pushed -
+    1, i.e. t * M < (n_pushed - half) * L: max(0, ceil((n_pushed - half) * L / M)).  final (the recording ends at n_pushed: `flush`):
+    ceil(n_pushed * L / M) = `resample_len`, the tail of the filter reading zeros.  The count depends on the total pushed alone."""
+    n_pushed, L, M, half = int(n_pushed), int(L), int(M), int(half)
+    if final:
+        return -((-n_pushed * L) // M)
+    return max(0, -((-(n_pushed - half) * L) // M))
+
+
+def live_in_ring_min(L: int, M: int, half: int) -> int:
+    """The fewest input samples per channel a live session's input ring may hold: the 2 * half inputs of the oldest output still to
+    come, up to M inputs the ready rule leaves between two outputs, and at least one new sample per piece - 2 * half + M + 1 - and no
+    fewer than the least span one block of `mmd_ring_resample` stages (`mmd_ring_resample_span`: asked of the library, no device work;
+    it is at most 2 * half + M, so the first bound decides)."""
+    from . import _lib
+    span = _lib.LIB.load().mmd_ring_resample_span(int(L), int(M), 2 * int(half))
+    if span < 0:
+        raise ValueError(f"mmd_ring_resample_span refuses L = {L}, M = {M}, taps = {2 * half}")
+    return max(2 * int(half) + int(M) + 1, span)
+
+
+def resample_bank(sr_in: int, sr_out: int = 44100):
+    """-> (L, M, half, bank float32 [L, 2 * half], phase_off int32 [L]) for sr_in -> sr_out.
+
+    L / M = sr_out / sr_in in lowest terms, scale = min(1, L / M), half = ceil(64 / scale).  bank[p][j] = h(p / L - k) at k = j - half + 1
+    with h(tau) = scale * rolloff * sinc(scale * rolloff * tau) * kaiser(tau * scale / 64), computed in float64 (the argument as the one
+    quotient (p - k L) / L) and rounded once: output t is sum_j bank[(t M) % L][j] * x[(t M) // L + j - half + 1].  phase_off[r] =
+    (r * M) // L is the input offset of output phase r = t % L inside its period.  Raises ValueError as `resample_ratio` does."""
+    L, M, half = resample_ratio(sr_in, sr_out)
+    scale = 1.0 if L >= M else L / M
     p = np.arange(L, dtype=np.int64)[:, None]
     k = np.arange(-half + 1, half + 1, dtype=np.int64)[None, :]
     tau = (p - k * L).astype(np.float64) / L
@@ -273,6 +303,15 @@ class Resampler:
         out = torch.empty(*wav.shape[:-1], n_out, device=self.device)
         self.call("mmd_resample_poly", wav, wav.numel() // n_in, n_in, bank, phase_off, L, M, taps, out, n_out)
         return out
+
+    def ring_resample_into(self, in_ring: torch.Tensor, n_valid: int, sr_in: int, out_ring: torch.Tensor, t_lo: int, t_hi: int,
+                           sr_out: int = 44100):
+        """`resample` for a recording that arrives (`mmd_ring_resample`, one launch, nothing allocated): in_ring float32 [C, in_cap]
+        holds absolute input sample p < n_valid at slot p % in_cap; the outputs t_lo .. t_hi-1 go to out_ring [C, out_cap] at slot
+        t % out_cap, with the bits `resample` gives them on the whole recording (`live_resample_ready` says which are computable)."""
+        L, M, taps, bank, phase_off = self._bank(sr_in, sr_out)
+        self.call("mmd_ring_resample", in_ring, in_ring.shape[1], in_ring.shape[0], int(n_valid), bank, phase_off, L, M, taps, out_ring,
+                  out_ring.shape[1], int(t_lo), int(t_hi))
 
     def pcm_to_float(self, raw: torch.Tensor, frames: int, channels: int, width: int) -> torch.Tensor:
         """interleaved little-endian signed PCM, raw uint8 [frames * channels * width] on the device (a WAV's frames as read) ->

@@ -40,31 +40,7 @@
 // needs no zeroing and two launches give the same bits.
 #include "common.h"
 #include "pcm_tile.h"
-
-#define RS_THREADS 256
-#define RS_QT 4                                      // periods per thread
-#define RS_PHMAX 64                                  // phases per block at most
-#define RS_LDS_FLOATS 12288                          // staged input span at most (48 KB)
-#define RS_FMAX 1024                                 // L, M at most
-#define RS_TAPS_MAX 4096
-#define RS_ROWS_MAX 65535                            // rows ride in gridDim.z
-
-struct RsPlan { int PH, PS, QB, dbound, span; };
-
-// dbound: phase_off[b] - phase_off[a] = floor(b M / L) - floor(a M / L) <= floor((b - a) M / L) + 1 for the PH phases of a tile
-static inline RsPlan rs_plan(int L, int M, int taps, long long n_periods) {
-  RsPlan p;
-  const int ntile = cdiv(L, RS_PHMAX);
-  p.PH = cdiv(L, ntile);
-  p.PS = RS_THREADS / p.PH;
-  p.dbound = (int)(((long long)(p.PH - 1) * M) / L) + 1;
-  long long qb = (RS_LDS_FLOATS - taps - p.dbound) / M + 1;          // >= 1: taps + dbound <= 4096 + 1024 < RS_LDS_FLOATS
-  if (qb > (long long)p.PS * RS_QT) qb = (long long)p.PS * RS_QT;
-  if (qb > n_periods) qb = n_periods;
-  p.QB = (int)qb;
-  p.span = (p.QB - 1) * M + p.dbound + taps;
-  return p;
-}
+#include "resample_tile.h"                           // the plan of a block and its tap loop, shared with mmd_ring_resample (live.hip)
 
 __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const float* __restrict__ x, long long n_in, const float* __restrict__ bank,
                                                                    const int* __restrict__ phase_off, int L, int M, int taps,
@@ -85,27 +61,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const float* 
   }
   __syncthreads();
 
-  // ---- thread (ph, pq): phase r0 + ph, periods q0 + pq + i * PS.  The table is the caller's: its differences are clamped into the
-  //      staged span (a bad table gives wrong samples, never a read outside the tile), idle threads read the tile's first taps.
-  const int ph = tid % pl.PH, pq = tid / pl.PH;
-  const int r = min(r0 + ph, L - 1);
-  const bool lane_ok = r0 + ph < L && pq < pl.PS;
-  const int d = min(max(phase_off[r] - off0, 0), pl.dbound);
-  int base[RS_QT];
+  // ---- thread (ph, pq): phase r0 + ph, periods q0 + pq + i * PS (resample_tile.h)
   float acc[RS_QT];
-#pragma unroll
-  for (int i = 0; i < RS_QT; ++i) {
-    const int qi = pq + i * pl.PS;
-    base[i] = (lane_ok && qi < pl.QB) ? qi * M + d : 0;
-    acc[i] = 0.f;
-  }
-  const float* b = bank + r;
-#pragma unroll 4
-  for (int j = 0; j < taps; ++j) {
-    const float w = b[(size_t)j * L];
-#pragma unroll
-    for (int i = 0; i < RS_QT; ++i) acc[i] = fmaf(w, s_x[base[i] + j], acc[i]);
-  }
+  const bool lane_ok = rs_tile_taps(s_x, bank, phase_off, L, M, taps, pl, r0, off0, acc);
+  const int ph = tid % pl.PH, pq = tid / pl.PH;
 #pragma unroll
   for (int i = 0; i < RS_QT; ++i) {
     const int qi = pq + i * pl.PS;
@@ -117,7 +76,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_poly_kernel(const float* 
 extern "C" int mmd_resample_poly(const float* x, int rows, long long n_in, const float* bank, const int* phase_off, int L, int M, int taps,
                                  float* y, long long n_out, hipStream_t stream) {
   if (!x || !bank || !phase_off || !y || rows < 1 || rows > RS_ROWS_MAX || n_in < 1 || n_in > (1ll << 50)) return MMD_EINVAL;
-  if (L < 1 || L > RS_FMAX || M < 1 || M > RS_FMAX || (taps & 1) || taps < 2 || taps > RS_TAPS_MAX) return MMD_EINVAL;
+  if (!rs_factors_ok(L, M, taps)) return MMD_EINVAL;
   if (n_out != (n_in * L + M - 1) / M) return MMD_EINVAL;
   const long long n_periods = (n_out + L - 1) / L;
   const RsPlan pl = rs_plan(L, M, taps, n_periods);

@@ -16,7 +16,9 @@ front of every group's append: each row of the record also gets the id of its tr
 
 `open_stream` is the same chain for audio that ARRIVES: a `LiveSession` keeps a bounded ring of samples at a fixed device address
 (csrc/live.hip: `mmd_ring_push`, `mmd_ring_push_pcm`), the front end reads the windows out of it across the wrap
-(`mmd_melspec_windows_ring`), and one captured graph serves the whole session and every recording pushed through it."""
+(`mmd_melspec_windows_ring`), and one captured graph serves the whole session and every recording pushed through it.  A source at
+another rate than 44.1 kHz (`open_stream(sample_rate=R)`) goes through a second ring of input-rate samples, from which
+`mmd_ring_resample` computes the 44.1 kHz samples the schedule asks for with the bits `Resampler.resample` gives the whole recording."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
@@ -26,7 +28,8 @@ import torch
 
 from .arch import NetSpec
 from . import _lib
-from .audio import MelFrontEnd, live_group_span, live_schedule, stream_window_starts
+from .audio import (MelFrontEnd, Resampler, live_group_span, live_in_ring_min, live_resample_ready, live_schedule, resample_ratio,
+                    stream_window_starts)
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -61,6 +64,7 @@ class AudioDetector:
         self._live: Optional["LiveSession"] = None     # open_stream's session; a stream and a session never coexist
         self.live_captures = 0                    # graphs open_stream's sessions captured
         self.live_replays = 0                     # groups of windows a session served by a captured graph
+        self.resampler: Optional[Resampler] = None     # the filter banks of sessions at other rates than 44.1 kHz (made with the first)
         self.last_cls: Optional[torch.Tensor] = None   # head outputs of the last call (views of the net's arena: valid until the next call)
         self.last_reg: Optional[torch.Tensor] = None
 
@@ -318,20 +322,27 @@ class AudioDetector:
     # ------------------------------------------------------------------ live streaming
     @torch.no_grad()
     def open_stream(self, win_len: int, hop: int, batch: int = 8, track: Optional[TrackConfig] = None,
-                    ring_len: Optional[int] = None) -> "LiveSession":
+                    ring_len: Optional[int] = None, sample_rate: Optional[int] = None, in_ring_len: Optional[int] = None) -> "LiveSession":
         """Opens a live session: `detect_stream` / `track_stream` (track: a TrackConfig) for audio that arrives in chunks - see
         `LiveSession`.  win_len, hop, batch as `detect_stream`.  ring_len: samples per channel the session keeps on the device, at
         least one group's span (batch - 1) * hop + win_len (ValueError below that); default TWICE that span - the least is the span
         itself, a second one lets a push of up to a span go in as one ring write while the group before it is still pending, and
         the ring stays small against everything else the detector holds (8 channels x 2 x 1.7 s at 44.1 kHz: 4.8 MB for one-second
         windows every 0.1 s in groups of 8).  The detector holds one stream or session at a time: opening one closes the session
-        before it and drops `detect_stream`'s buffers, and a later `detect_stream` / `track_stream` closes the session."""
+        before it and drops `detect_stream`'s buffers, and a later `detect_stream` / `track_stream` closes the session.
+
+        sample_rate: the rate in Hz of the samples that will be pushed.  None or 44100: they are the front end's own, nothing is
+        resampled and nothing below exists.  Another rate R: the session resamples to 44.1 kHz as the chunks arrive (`LiveSession`);
+        win_len, hop, ring_len and the window indices stay in 44.1 kHz samples.  A ratio `audio.resample_ratio` refuses raises its
+        ValueError here.  in_ring_len (only with such a rate): input-rate samples per channel the session keeps, at least
+        `audio.live_in_ring_min` (taps + M + 1, and the least span one block of `mmd_ring_resample` stages; ValueError below that);
+        default taps + M + ceil(ring_len * M / L) - a push of up to a ring's worth of audio is then one piece."""
         if track is not None and not isinstance(track, TrackConfig):
             raise ValueError("open_stream: track must be a TrackConfig or None")
         if self._live is not None:
             self._live.close()
         self._stream = None
-        self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len)
+        self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len, sample_rate, in_ring_len)
         return self._live
 
 
@@ -363,9 +374,23 @@ class LiveSession:
     two overflow flags into pinned host memory.  A push that completes several groups empties the record that way before each further
     group.  Host chunks go through two pinned staging buffers used in turn; before a buffer is written again the session waits for
     the event behind the copy that last read it - two pushes back - never for the detection chain.  The control rows of a push's
-    groups lie in one pinned table that is only rewritten after that push's final wait."""
+    groups lie in one pinned table that is only rewritten after that push's final wait.
 
-    def __init__(self, det: AudioDetector, win_len: int, hop: int, batch: int, track: Optional[TrackConfig], ring_len: Optional[int]):
+    Another sample rate (`open_stream(sample_rate=R)`, L / M = 44100 / R in lowest terms, a filter of taps = 2 * half taps).  `push` /
+    `push_pcm` then take samples at R.  The session owns a second ring, in_ring [8, in_ring_len] of input-rate samples; the chunk is
+    written there by the same two writers (in pieces of at most in_ring_len - taps - M samples), and after each piece the outputs
+    whose last tap has arrived (`audio.live_resample_ready`) are handed to `audio.live_schedule` exactly as a 44.1 kHz push of that
+    many samples: every ring write of the schedule becomes one `mmd_ring_resample` for just those outputs - what the schedule skips
+    (hop > win_len) is never computed - and the group runs are untouched.  The captured graph is the same; the resampling launches sit
+    outside it, like the ring writes, and the synchronisation rules above hold as they stand.  `flush` first produces the outputs up to
+    `audio.resample_len` of the total pushed, the filter's tail reading zeros as it does at the end of a whole recording, runs the
+    groups that completes, then the short last group.  The contract: for ANY way of cutting a recording at rate R into chunks, what
+    the pushes and `flush` return, concatenated, is bit for bit what `detect_stream` / `track_stream` return for
+    `Resampler.resample(whole recording, R)` at the same settings - `mmd_ring_resample` forms the sums of `mmd_resample_poly`, and an
+    output depends on its 2 * half inputs alone.  Results come `half` input samples later (1.5 ms at 48 kHz)."""
+
+    def __init__(self, det: AudioDetector, win_len: int, hop: int, batch: int, track: Optional[TrackConfig], ring_len: Optional[int],
+                 sample_rate: Optional[int] = None, in_ring_len: Optional[int] = None):
         C = det.net.spec.in_channels
         if hop < 1:
             raise ValueError("open_stream: hop = %d: the windows must advance by at least one sample" % hop)
@@ -376,9 +401,26 @@ class LiveSession:
         cap = 2 * span if ring_len is None else int(ring_len)
         if cap < span:
             raise ValueError("open_stream: ring_len = %d is shorter than one group of %d windows (%d samples)" % (cap, batch, span))
+        # another rate than the front end's: (rate, L, M, half) and the input ring's size, both settled before any device work
+        self.rs, self.in_ring, self.in_ring_len, self.in_written = None, None, None, 0
+        if sample_rate is not None and int(sample_rate) != 44100:
+            L, M, half = resample_ratio(int(sample_rate))
+            least = live_in_ring_min(L, M, half)
+            in_cap = 2 * half + M - ((-cap * M) // L) if in_ring_len is None else int(in_ring_len)       # taps + M + ceil(cap * M / L)
+            if in_cap < least:
+                raise ValueError("open_stream: in_ring_len = %d is shorter than the %d samples resampling %d Hz needs (%d taps + M = %d + 1, "
+                                 "and no fewer than a block stages)" % (in_cap, least, int(sample_rate), 2 * half, M))
+            self.rs, self.in_ring_len = (int(sample_rate), L, M, half), in_cap
+        elif in_ring_len is not None:
+            raise ValueError("open_stream: in_ring_len goes with a sample_rate other than 44100 (nothing is resampled)")
         self.det, self.track, self.C, self.win_len, self.hop, self.batch, self.ring_len = det, track, C, win_len, hop, batch, cap
         self.written, self.group, self.flushed, self.closed = 0, 0, False, False
         dev = det.device
+        if self.rs is not None:
+            if det.resampler is None:
+                det.resampler = Resampler(dev)
+            det.resampler._bank(self.rs[0], 44100)       # the bank goes to the device now, not in the first push
+            self.in_ring = torch.zeros(C, self.in_ring_len, device=dev)
         rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
         if rec_cap > 0x7fffffff // 8:
             raise ValueError("open_stream: a record of %d rows" % rec_cap)
@@ -435,10 +477,11 @@ class LiveSession:
                 t.zero_()
 
     def reset(self):
-        """Starts a new recording on the same session: position 0, window 0, the tracker zeroed (ids start at 0 again); the graph, the
-        ring and every buffer stay (the ring needs no clearing: no window reads a slot this recording has not written)."""
+        """Starts a new recording on the same session: position 0 (the input position too), window 0, the tracker zeroed (ids start at
+        0 again); the graph, the rings and every buffer stay (they need no clearing: no window reads a slot this recording has not
+        written, and the resampler reads zeros for whatever this recording has not pushed)."""
         self._check_open()
-        self.written, self.group, self.flushed = 0, 0, False
+        self.written, self.group, self.flushed, self.in_written = 0, 0, False, 0
         self._zero_state()
 
     def close(self):
@@ -446,7 +489,7 @@ class LiveSession:
         if not self.closed:
             torch.cuda.synchronize()
             self.closed = True
-            self.g = self._blob = self._h_blob = self._stage = None
+            self.g = self._blob = self._h_blob = self._stage = self.in_ring = None
             if self.det._live is self:
                 self.det._live = None
 
@@ -522,6 +565,30 @@ class LiveSession:
             parts.append(self._drain())
         return self._result(parts)
 
+    def _produce(self, final: bool):
+        """the 44.1 kHz samples the input pushed so far allows (final: up to the recording's end), through the schedule: every ring write
+        is one `mmd_ring_resample` from the input ring"""
+        rate, L, M, half = self.rs
+        ready = live_resample_ready(self.in_written, L, M, half, final)
+        if ready == self.written:
+            return self._result([])
+        rs, in_ring, ring, n_valid = self.det.resampler, self.in_ring, self.g["ring"], self.in_written
+        return self._advance(ready - self.written, lambda off, cnt, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
+
+    def _feed(self, n: int, write):
+        """one chunk of n samples; write(offset into the chunk, samples, ring, its length, absolute position) queues one ring write"""
+        if self.rs is None:
+            ring, cap = self.g["ring"], self.ring_len
+            return self._advance(n, lambda off, cnt, pos: write(off, cnt, ring, cap, pos))
+        _, L, M, half = self.rs
+        piece, parts = self.in_ring_len - 2 * half - M, []       # the oldest input a pending output needs survives the piece
+        for off in range(0, n, piece):
+            cnt = min(piece, n - off)
+            write(off, cnt, self.in_ring, self.in_ring_len, self.in_written)
+            self.in_written += cnt
+            parts.append(self._produce(False))
+        return self._result(parts)
+
     # ---- chunks
     def _to_device(self, host: torch.Tensor) -> torch.Tensor:
         """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
@@ -538,7 +605,8 @@ class LiveSession:
         return dev
 
     def push(self, chunk):
-        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of every microphone"""
+        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of every microphone (at the
+        session's sample_rate)"""
         self._check_open(pushing=True)
         if isinstance(chunk, np.ndarray):
             if chunk.dtype != np.float32:
@@ -551,9 +619,9 @@ class LiveSession:
             chunk = self._to_device(chunk)
         elif chunk.stride(1) != 1 or chunk.stride(0) < chunk.shape[1]:
             chunk = chunk.contiguous()
-        ptr, stride, ring = chunk.data_ptr(), chunk.stride(0), self.g["ring"]
-        return self._advance(chunk.shape[1], lambda off, cnt, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt, ring,
-                                                                             self.ring_len, pos))
+        ptr, stride = chunk.data_ptr(), chunk.stride(0)
+        return self._feed(chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt,
+                                                                                     ring, cap, pos))
 
     def push_pcm(self, raw, width: int):
         """raw: bytes, a bytearray or a uint8 tensor (host or device) of whole frames of interleaved little-endian signed PCM, 8 channels
@@ -571,23 +639,24 @@ class LiveSession:
         if raw.numel() < fb or raw.numel() % fb:
             raise ValueError("push_pcm: %d bytes are not whole frames of %d x %d bytes" % (raw.numel(), self.C, width))
         raw = raw.contiguous() if raw.is_cuda else self._to_device(raw)
-        ptr, ring = raw.data_ptr(), self.g["ring"]
-        return self._advance(raw.numel() // fb, lambda off, cnt, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C, width,
-                                                                                ring, self.ring_len, pos))
+        ptr = raw.data_ptr()
+        return self._feed(raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C,
+                                                                                        width, ring, cap, pos))
 
     @torch.no_grad()
     def flush(self):
         """Ends the recording: runs the last, shorter group - the complete windows no full group took, padded by repeating the last one
-        - and returns its results; a tail shorter than a window is dropped, as `detect_stream` drops it.  Afterwards only `reset` or
-        `close`."""
+        - and returns its results; a tail shorter than a window is dropped, as `detect_stream` drops it.  A resampling session first
+        produces the recording's last outputs (and runs the full groups they complete).  Afterwards only `reset` or `close`."""
         self._check_open()
         if self.flushed:
             return self._result([])
         self.flushed = True
+        parts = [self._produce(True)] if self.rs is not None else []
         W = 0 if self.written < self.win_len else 1 + (self.written - self.win_len) // self.hop
         first = self.group * self.batch
-        if W <= first:
-            return self._result([])
-        table = self._control_rows([([w * self.hop for w in range(first, W)], first)])
-        self._run_group(table[0])
-        return self._result([self._drain()])
+        if W > first:
+            table = self._control_rows([([w * self.hop for w in range(first, W)], first)])
+            self._run_group(table[0])
+            parts.append(self._drain())
+        return self._result(parts)
