@@ -78,14 +78,35 @@ def read_npy(path: str) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
+def _check_wav(path: str, w, any_rate: bool):
+    """The header rules of an open `wave` reader -> (bytes per sample, rate in Hz).  any_rate False: 8 channels of 16-bit PCM at 44.1 kHz,
+    what the front end takes as it is; True: 8 channels of 16-, 24- or 32-bit PCM at any rate, what the device decodes and resamples."""
+    width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
+    if not any_rate and rate != SAMPLE_RATE:
+        raise ValueError(f"{path}: sample rate {rate} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
+    if w.getcomptype() != "NONE" or width not in ((2, 3, 4) if any_rate else (2,)):
+        bits = "16-, 24- or 32-bit" if any_rate else "16-bit"
+        raise ValueError(f"{path}: only {bits} PCM is supported, found {8 * width}-bit {w.getcomptype()}")
+    if channels != CHANNELS:
+        raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
+    if rate < 1:
+        raise ValueError(f"{path}: sample rate {rate} Hz")
+    return width, rate
+
+
+def _wav_chunks(w, chunk: int, width: int):
+    """(raw whole frames, bytes per sample) of an open `wave` reader, `chunk` frames at a time; closes the reader behind the last"""
+    with w:
+        while True:
+            raw = w.readframes(chunk)
+            if len(raw) < width * CHANNELS:
+                return
+            yield raw[:len(raw) - len(raw) % (width * CHANNELS)], width
+
+
 def read_wav(path: str) -> np.ndarray:
     with wave.open(path, "rb") as w:
-        if w.getframerate() != SAMPLE_RATE:
-            raise ValueError(f"{path}: sample rate {w.getframerate()} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
-        if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
-            raise ValueError(f"{path}: only 16-bit PCM is supported, found {8 * w.getsampwidth()}-bit {w.getcomptype()}")
-        if w.getnchannels() != CHANNELS:
-            raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {w.getnchannels()}")
+        _check_wav(path, w, any_rate=False)
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, CHANNELS)
     return np.ascontiguousarray((pcm.astype(np.float32) / np.float32(32768.0)).T)[None]
 
@@ -105,18 +126,12 @@ def read_recording(path: str):
     interleaved little-endian signed samples; frames; channels; bytes per sample; rate in Hz).  Nothing is decoded on the host:
     `Resampler.pcm_to_float` and `Resampler.resample` take it from there (--resample)."""
     with wave.open(path, "rb") as w:
-        width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
-        if w.getcomptype() != "NONE" or width not in (2, 3, 4):
-            raise ValueError(f"{path}: only 16-, 24- or 32-bit PCM is supported, found {8 * width}-bit {w.getcomptype()}")
-        if channels != CHANNELS:
-            raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
-        if rate < 1:
-            raise ValueError(f"{path}: sample rate {rate} Hz")
+        width, rate = _check_wav(path, w, any_rate=True)
         raw = np.frombuffer(w.readframes(w.getnframes()), dtype=np.uint8)
-    frames = raw.size // (channels * width)
+    frames = raw.size // (CHANNELS * width)
     if frames < 1:
         raise ValueError(f"{path}: no frames")
-    return raw[:frames * channels * width].copy(), frames, channels, width, rate
+    return raw[:frames * CHANNELS * width].copy(), frames, CHANNELS, width, rate
 
 
 def load_resampled(a, dev):
@@ -151,29 +166,31 @@ def write_csv(path: str, rows_per_clip) -> int:
     return n
 
 
-def write_stream_csv(path: str, rows, window, hop: int) -> int:
-    """rows [R, 6] / window [R] of `AudioDetector.detect_stream` at a hop of `hop` samples"""
+def _write_windows_csv(path: str, columns, rows, window, hop: int, track=None) -> int:
+    """one row per box: window, its start in seconds, the box[, its track id]"""
     rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
+    last = [[]] * len(rows)
+    if track is not None:
+        track = np.asarray(track).reshape(-1)
+        if len(track) != len(rows) or len(window) != len(rows):
+            raise ValueError("write_track_csv: %d rows, %d windows, %d track ids" % (len(rows), len(window), len(track)))
+        last = [[t] for t in track.tolist()]
     with open(path, "w", newline="") as f:
         out = csv.writer(f)
-        out.writerow(STREAM_COLUMNS)
-        for w, r in zip(window.tolist(), rows):
-            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r])
+        out.writerow(columns)
+        for w, r, t in zip(window.tolist(), rows, last):
+            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + t)
     return len(rows)
+
+
+def write_stream_csv(path: str, rows, window, hop: int) -> int:
+    """rows [R, 6] / window [R] of `AudioDetector.detect_stream` at a hop of `hop` samples"""
+    return _write_windows_csv(path, STREAM_COLUMNS, rows, window, hop)
 
 
 def write_track_csv(path: str, rows, window, track, hop: int) -> int:
     """rows [R, 6] / window [R] / track [R] of `AudioDetector.track_stream` at a hop of `hop` samples"""
-    rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
-    track = np.asarray(track).reshape(-1)
-    if len(track) != len(rows) or len(window) != len(rows):
-        raise ValueError("write_track_csv: %d rows, %d windows, %d track ids" % (len(rows), len(window), len(track)))
-    with open(path, "w", newline="") as f:
-        out = csv.writer(f)
-        out.writerow(TRACK_COLUMNS)
-        for w, r, t in zip(window.tolist(), rows, track.tolist()):
-            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + [t])
-    return len(rows)
+    return _write_windows_csv(path, TRACK_COLUMNS, rows, window, hop, track)
 
 
 def stream_sizes(window_s: float, hop_s, n_total: int):
@@ -231,28 +248,14 @@ def open_live(path: str, live_s: float, sample_rate=None):
     if os.path.splitext(path)[1].lower() == ".wav":
         w = wave.open(path, "rb")
         try:
-            width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
-            if w.getcomptype() != "NONE" or width not in (2, 3, 4):
-                raise ValueError(f"{path}: only 16-, 24- or 32-bit PCM is supported, found {8 * width}-bit {w.getcomptype()}")
-            if channels != CHANNELS:
-                raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
-            if rate < 1:
-                raise ValueError(f"{path}: sample rate {rate} Hz")
+            width, rate = _check_wav(path, w, any_rate=True)
             chunk = int(round(live_s * rate))
             if chunk < 1:
                 raise ValueError(f"--live_s {live_s}: a positive number of seconds (at least one frame at {rate} Hz)")
         except ValueError:
             w.close()
             raise
-
-        def frames():
-            with w:
-                while True:
-                    raw = w.readframes(chunk)
-                    if len(raw) < width * CHANNELS:
-                        return
-                    yield raw[:len(raw) - len(raw) % (width * CHANNELS)], width
-        return w.getnframes(), rate, frames()
+        return w.getnframes(), rate, _wav_chunks(w, chunk, width)
     rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
     n_total, chunks = open_chunked(path, int(round(live_s * rate)))
     return n_total, rate, chunks
@@ -265,24 +268,11 @@ def open_chunked(path: str, chunk: int):
     if os.path.splitext(path)[1].lower() == ".wav":
         w = wave.open(path, "rb")
         try:
-            if w.getframerate() != SAMPLE_RATE:
-                raise ValueError(f"{path}: sample rate {w.getframerate()} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
-            if w.getsampwidth() != 2 or w.getcomptype() != "NONE":
-                raise ValueError(f"{path}: only 16-bit PCM is supported, found {8 * w.getsampwidth()}-bit {w.getcomptype()}")
-            if w.getnchannels() != CHANNELS:
-                raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {w.getnchannels()}")
+            width, _ = _check_wav(path, w, any_rate=False)
         except ValueError:
             w.close()
             raise
-
-        def frames():
-            with w:
-                while True:
-                    raw = w.readframes(chunk)
-                    if len(raw) < 2 * CHANNELS:
-                        return
-                    yield raw[:len(raw) - len(raw) % (2 * CHANNELS)], 2
-        return w.getnframes(), frames()
+        return w.getnframes(), _wav_chunks(w, chunk, width)
     m = np.load(path, mmap_mode="r", allow_pickle=False)
     if m.dtype != np.float32:
         raise ValueError(f"{path}: waveforms must be float32, found {m.dtype}")
@@ -300,7 +290,7 @@ def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track, sample_r
     parts = [session.push(c) if width is None else session.push_pcm(c, width) for c, width in chunks]
     parts.append(session.flush())
     session.close()
-    return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
+    return session.concat(parts)
 
 
 def main(argv=None):

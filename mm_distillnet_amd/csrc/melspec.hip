@@ -305,23 +305,6 @@ extern "C" int mmd_melspec_frames(long long n_samples) {
   return (int)(1 + n_samples / MEL_HOP);
 }
 
-extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long long n_samples, const int* band_start,
-                                 const int* band_len, const float* band_w, int band_stride, float* out, hipStream_t stream) {
-  if (!wav_a || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535) return MMD_EINVAL;
-  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX) return MMD_EINVAL;
-  const int T = mmd_melspec_frames(n_samples);
-  if (T < 0) return MMD_EINVAL;
-  const dim3 grid(cdiv(T, MEL_FPB), channels), block(256);
-  unsigned int* none = nullptr;
-  if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, none, (const long long*)nullptr, 0ll);
-  return mmd_check_launch();
-}
-
 // The maxima workspace is cleared by the project's zero-fill KERNEL (mmd_zero_bytes, optim.hip), not by hipMemsetAsync: a memset node
 // recorded by stream capture is not reliably executed on later replays of the graph (optim.hip found the same on the accumulator arenas).
 // Seen here as: from the second replay of AudioDetector's waveform graph on, max_ws held stale or foreign words in front of the
@@ -336,78 +319,65 @@ static void power_to_db_launch(float* x, int batch, size_t per_sample, int C, co
   hipLaunchKernelGGL(power_to_db_kernel, grid, dim3(256), 0, stream, x, per_sample, C, mx_ws);
 }
 
-extern "C" int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples,
-                                 const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws,
-                                 float* out, hipStream_t stream) {
+// The launch sequence of the four entry points below: [zero max_ws ->] melspec_power_kernel<MIX = wav_b, TRACK = db, WIN = win> [-> dB pass].
+// n_samples: the length of one sample (a window's, in the window modes).  win = MEL_WIN_LINEAR / MEL_WIN_RING: win_start[batch] into ONE
+// recording / ring wav_a[channels, extent], no wav_b; MEL_WIN_NONE: wav_a (+ wav_b) [batch, channels, n_samples], no win_start.
+static int melspec_launch(int win, const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples,
+                          const long long* win_start, long long extent, const int* band_start, const int* band_len, const float* band_w,
+                          int band_stride, int db, float* max_ws, float* out, hipStream_t stream) {
   if (!wav_a || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 || batch > 65535)
     return MMD_EINVAL;
   if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
   const int T = mmd_melspec_frames(n_samples);
-  if (T < 0) return MMD_EINVAL;
+  if (T < 0 || (win != MEL_WIN_NONE && (!win_start || n_samples > extent))) return MMD_EINVAL;
   const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
   unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
   if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
-  if (wav_b && db)
-    hipLaunchKernelGGL((melspec_power_kernel<true, true, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
-  else if (wav_b)
-    hipLaunchKernelGGL((melspec_power_kernel<true, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
-  else if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
-  else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_NONE>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, (const long long*)nullptr, 0ll);
+#define MEL_LAUNCH(MIX, TRACK, WIN)                                                                                                  \
+  hipLaunchKernelGGL((melspec_power_kernel<MIX, TRACK, WIN>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, \
+                     band_len, band_w, band_stride, out, mx, win_start, extent)
+  // (named in the order the code object has always held the eight instantiations: its bytes stay what they were)
+  if (win == MEL_WIN_NONE && !db) {
+    if (wav_b) MEL_LAUNCH(true, false, MEL_WIN_NONE); else MEL_LAUNCH(false, false, MEL_WIN_NONE);
+  } else if (win == MEL_WIN_NONE) {
+    if (wav_b) MEL_LAUNCH(true, true, MEL_WIN_NONE); else MEL_LAUNCH(false, true, MEL_WIN_NONE);
+  } else if (win == MEL_WIN_LINEAR) {
+    if (db) MEL_LAUNCH(false, true, MEL_WIN_LINEAR); else MEL_LAUNCH(false, false, MEL_WIN_LINEAR);
+  } else {
+    if (db) MEL_LAUNCH(false, true, MEL_WIN_RING); else MEL_LAUNCH(false, false, MEL_WIN_RING);
+  }
+#undef MEL_LAUNCH
   if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
   return mmd_check_launch();
+}
+
+// one sample's power map: mmd_melspec_batch at batch 1, db 0
+extern "C" int mmd_melspec_power(const float* wav_a, const float* wav_b, int channels, long long n_samples, const int* band_start,
+                                 const int* band_len, const float* band_w, int band_stride, float* out, hipStream_t stream) {
+  return melspec_launch(MEL_WIN_NONE, wav_a, wav_b, 1, channels, n_samples, nullptr, 0ll, band_start, band_len, band_w, band_stride, 0,
+                        nullptr, out, stream);
+}
+
+extern "C" int mmd_melspec_batch(const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples,
+                                 const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws,
+                                 float* out, hipStream_t stream) {
+  return melspec_launch(MEL_WIN_NONE, wav_a, wav_b, batch, channels, n_samples, nullptr, 0ll, band_start, band_len, band_w, band_stride,
+                        db, max_ws, out, stream);
 }
 
 extern "C" int mmd_melspec_windows(const float* wav, int channels, long long n_total, const long long* win_start, int batch,
                                    long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride,
                                    int db, float* max_ws, float* out, hipStream_t stream) {
-  if (!wav || !win_start || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 ||
-      batch > 65535)
-    return MMD_EINVAL;
-  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
-  const int T = mmd_melspec_frames(win_len);
-  if (T < 0 || win_len > n_total) return MMD_EINVAL;
-  const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
-  unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
-  const float* none = nullptr;
-  if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
-  if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_LINEAR>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, win_start, n_total);
-  else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_LINEAR>), grid, block, 0, stream, wav, none, win_len, T, channels, band_start,
-                       band_len, band_w, band_stride, out, mx, win_start, n_total);
-  if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
-  return mmd_check_launch();
+  return melspec_launch(MEL_WIN_LINEAR, wav, nullptr, batch, channels, win_len, win_start, n_total, band_start, band_len, band_w,
+                        band_stride, db, max_ws, out, stream);
 }
 
-// the ring mode of mmd_melspec_windows: same checks, same launch sequence, cap in n_total's place
+// the ring mode of mmd_melspec_windows: cap in n_total's place
 extern "C" int mmd_melspec_windows_ring(const float* ring, int channels, long long cap, const long long* win_start, int batch,
                                         long long win_len, const int* band_start, const int* band_len, const float* band_w,
                                         int band_stride, int db, float* max_ws, float* out, hipStream_t stream) {
-  if (!ring || !win_start || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 ||
-      batch > 65535)
-    return MMD_EINVAL;
-  if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
-  const int T = mmd_melspec_frames(win_len);
-  if (T < 0 || win_len > cap) return MMD_EINVAL;
-  const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
-  unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
-  const float* none = nullptr;
-  if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
-  if (db)
-    hipLaunchKernelGGL((melspec_power_kernel<false, true, MEL_WIN_RING>), grid, block, 0, stream, ring, none, win_len, T, channels,
-                       band_start, band_len, band_w, band_stride, out, mx, win_start, cap);
-  else
-    hipLaunchKernelGGL((melspec_power_kernel<false, false, MEL_WIN_RING>), grid, block, 0, stream, ring, none, win_len, T, channels,
-                       band_start, band_len, band_w, band_stride, out, mx, win_start, cap);
-  if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
-  return mmd_check_launch();
+  return melspec_launch(MEL_WIN_RING, ring, nullptr, batch, channels, win_len, win_start, cap, band_start, band_len, band_w,
+                        band_stride, db, max_ws, out, stream);
 }
 
 extern "C" int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_ws, hipStream_t stream) {

@@ -21,6 +21,7 @@ another rate than 44.1 kHz (`open_stream(sample_rate=R)`) goes through a second 
 `mmd_ring_resample` computes the 44.1 kHz samples the schedule asks for with the bits `Resampler.resample` gives the whole recording."""
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -55,10 +56,10 @@ class AudioDetector:
         self.cand_cap = int(cand_cap)
         self.cap = int(cand_cap)                  # 0: set to the anchor count at the first call
         self.overflow = torch.zeros(1, dtype=torch.int32, device=device)
-        self._graphs: Dict[tuple, dict] = {}      # ("wave", B, N) / ("spec", B, S) -> static input, front-end buffers, graph, outputs
+        self._graphs: Dict[tuple, SimpleNamespace] = {}     # ("wave", B, N) / ("spec", B, S) -> static input, front-end buffers, graph, outputs
         self.graph_replays = 0                    # calls served by a captured graph
         self.use_graph = True                     # False: every call runs eagerly (timing the graph against the plain launch sequence)
-        self._stream: Optional[dict] = None       # detect_stream's buffers and graph: ONE recording at a time (the graph bakes its address in)
+        self._stream: Optional["_GroupChain"] = None      # detect_stream's chain: ONE recording at a time (the graph bakes its address in)
         self.stream_captures = 0                  # graphs detect_stream captured
         self.stream_replays = 0                   # groups of windows detect_stream served by a captured graph
         self._live: Optional["LiveSession"] = None     # open_stream's session; a stream and a session never coexist
@@ -80,28 +81,27 @@ class AudioDetector:
         self.net.load_state(state)
 
     # ------------------------------------------------------------------ the chain
-    def _buffers(self, kind: str, shape) -> dict:
+    def _buffers(self, kind: str, shape) -> SimpleNamespace:
         """static input (and, for waveforms, the front end's buffers) of one input shape"""
-        g = {"x": torch.empty(shape, device=self.device)}
+        g = SimpleNamespace(x=torch.empty(shape, device=self.device), graph=None)
         if kind == "wave":
             B, C, N = shape
-            g["mel"] = torch.empty(B, self.front.n_mels, self.front.n_frames(N), C, device=self.device)
-            g["max_ws"] = torch.empty(B * C, device=self.device)
-            g["audio"] = torch.empty(B, C, self.S, self.S, device=self.device)
+            g.mel = torch.empty(B, self.front.n_mels, self.front.n_frames(N), C, device=self.device)
+            g.max_ws = torch.empty(B * C, device=self.device)
+            g.audio = torch.empty(B, C, self.S, self.S, device=self.device)
         return g
 
-    def _chain(self, kind: str, g: dict):
+    def _chain(self, kind: str, g):
         """Issues front end -> forward -> decode -> NMS on the current stream; nothing is allocated outside the bump arenas."""
-        S = self.S
         if kind == "wave":
-            self.front.melspec_into(g["x"], None, True, g["max_ws"], g["mel"])
-            audio = self.front.resize_into(g["mel"], S, g["audio"])
+            self.front.melspec_into(g.x, None, True, g.max_ws, g.mel)
+            audio = self.front.resize_into(g.mel, self.S, g.audio)
         else:
-            audio = g["x"]
+            audio = g.x
         self._tail(audio, g)
 
-    def _tail(self, audio: torch.Tensor, g: dict):
-        """forward -> decode -> NMS of a ready student input [B, 8, S, S]"""
+    def _tail(self, audio: torch.Tensor, g):
+        """forward -> decode -> NMS of a ready student input [B, 8, S, S]; the outputs become g.cls, g.reg, g.rows, g.cnt"""
         S = self.S
         B = audio.shape[0]
         self.ws.reset()
@@ -112,40 +112,48 @@ class AudioDetector:
             self.cap = A
         rows, cnt = decode_nms(self.ws, self.net, cls, reg, B, A, S, self.cap, self.conf_threshold, self.valid_mask, self.label_map,
                                self.nms_threshold, self.inclusive_nms, self.overflow)
-        g.update(cls=cls, reg=reg, rows=rows, cnt=cnt)
+        g.cls, g.reg, g.rows, g.cnt = cls, reg, rows, cnt
 
-    def _rows(self, g: dict) -> List[np.ndarray]:
+    def _rows(self, g) -> List[np.ndarray]:
         torch.cuda.synchronize()
-        self.last_cls, self.last_reg = g["cls"], g["reg"]
-        cnt = g["cnt"].cpu().tolist()
-        return [g["rows"][i, :cnt[i]].cpu().numpy() for i in range(len(cnt))]
+        self.last_cls, self.last_reg = g.cls, g.reg
+        cnt = g.cnt.cpu().tolist()
+        return [g.rows[i, :cnt[i]].cpu().numpy() for i in range(len(cnt))]
+
+    def _freeze_arenas(self, frozen: bool):
+        """False in front of the first run of a new shape or chain, which sizes the three bump arenas (chunks are only ever appended:
+        the graphs captured before stay valid); True behind it, and a graph may be captured"""
+        for a in (self.ws, self.net.arena, self.net.zarena):
+            a.frozen = frozen
+
+    @staticmethod
+    def _capture(issue) -> "torch.cuda.CUDAGraph":
+        """the launches of issue() as a graph, on arenas that a run of issue() has sized"""
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            issue()
+        torch.cuda.synchronize()
+        return graph
 
     @torch.no_grad()
     def _detect(self, kind: str, x: torch.Tensor) -> List[np.ndarray]:
         key = (kind,) + tuple(x.shape)
         g = self._graphs.get(key)
-        if g is not None and self.use_graph and "graph" in g:
-            g["x"].copy_(x, non_blocking=True)
-            g["graph"].replay()
+        if g is not None and self.use_graph and g.graph is not None:
+            g.x.copy_(x, non_blocking=True)
+            g.graph.replay()
             self.graph_replays += 1
             return self._rows(g)
         # no graph for this shape yet: run eagerly on the static buffers (the first run sizes the arenas), then capture
-        arenas = (self.ws, self.net.arena, self.net.zarena)
         if g is None:
-            for a in arenas:
-                a.frozen = False                  # chunks are only ever appended: the graphs of earlier shapes stay valid
+            self._freeze_arenas(False)
             g = self._graphs[key] = self._buffers(kind, tuple(x.shape))
-        g["x"].copy_(x, non_blocking=True)
+        g.x.copy_(x, non_blocking=True)
         self._chain(kind, g)
         out = self._rows(g)
-        for a in arenas:
-            a.frozen = True
+        self._freeze_arenas(True)
         if self.use_graph:
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self._chain(kind, g)
-            torch.cuda.synchronize()
-            g["graph"] = graph
+            g.graph = self._capture(lambda: self._chain(kind, g))
         return out
 
     def detect_spectrogram(self, audio: torch.Tensor) -> List[np.ndarray]:
@@ -166,22 +174,6 @@ class AudioDetector:
 
     # ------------------------------------------------------------------ streaming
     STREAM_ROWS_PER_WINDOW = 256      # default record size per window when cand_cap = 0 (unlimited rows per image)
-
-    def _stream_chain(self, g: dict):
-        """One group of windows: front end on the windows the control row names -> forward -> decode -> NMS [-> track update] -> append
-        to the record.  The track update reads the record's count before the append advances it.  A live session's windows come out
-        of its ring (g["ring"]), a stream's out of the recording (g["wave"])."""
-        if g.get("ring") is not None:
-            self.front.melspec_windows_ring_into(g["ring"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
-        else:
-            self.front.melspec_windows_into(g["wave"], g["starts"], g["win_len"], True, g["max_ws"], g["mel"])
-        audio = self.front.resize_into(g["mel"], self.S, g["audio"])
-        self._tail(audio, g)
-        B = audio.shape[0]
-        if g["track"] is not None:
-            _tracker.update(g["rows"], g["cnt"], g["ctl"], g["rec_state"][0:1], g["rec_cap"], g["rec_track"], g["trk_state"], g["track"])
-        _lib.call("mmd_det_record_append", g["rows"], g["cnt"], B, g["rows"].shape[1], g["ctl"], g["rec_rows"], g["rec_win"],
-                  g["rec_cap"], g["rec_state"][0:1], g["rec_state"][1:2])
 
     @torch.no_grad()
     def detect_stream(self, wave: torch.Tensor, win_len: int, hop: int, batch: int = 8, rec_cap: Optional[int] = None):
@@ -243,74 +235,23 @@ class AudioDetector:
         rec_cap = int(rec_cap)
         if rec_cap < 1 or rec_cap > 0x7fffffff:
             raise ValueError("%s: rec_cap = %d" % (who, rec_cap))
-        # control table, one row per group: int64 starts[batch], then {n_valid, first_window} as two int32 in the last word
-        G = (W + batch - 1) // batch
-        table = np.empty((G, batch + 1), np.int64)
-        tail = table.view(np.int32).reshape(G, 2 * (batch + 1))[:, 2 * batch:]
-        for gi in range(G):
-            real = starts[gi * batch:(gi + 1) * batch]
-            table[gi, :batch] = real + [real[-1]] * (batch - len(real))
-            tail[gi] = (len(real), gi * batch)
-        table = torch.from_numpy(table).to(self.device)
+        groups = [(starts[first:first + batch], first) for first in range(0, W, batch)]
+        table = torch.from_numpy(_GroupChain.control_table(groups, batch)).to(self.device)
 
         key = (win_len, batch, self.S, wave.data_ptr(), n_total, rec_cap, None if track is None else track.key())
-        arenas = (self.ws, self.net.arena, self.net.zarena)
         g = self._stream
-        if g is None or g["key"] != key:
+        if g is None or g.key != key:
             self._stream = g = None               # the old recording's buffers go before the new ones come
-            for a in arenas:
-                a.frozen = False                  # chunks are only ever appended: the graphs of `_detect` stay valid
-            cur = torch.zeros(batch + 1, dtype=torch.int64, device=self.device)
-            g = {"key": key, "track": track, "wave": wave, "win_len": win_len, "rec_cap": rec_cap, "cur": cur, "starts": cur[:batch],
-                 "ctl": cur[batch:].view(torch.int32),
-                 "mel": torch.empty(batch, self.front.n_mels, self.front.n_frames(win_len), C, device=self.device),
-                 "max_ws": torch.empty(batch * C, device=self.device),
-                 "audio": torch.empty(batch, C, self.S, self.S, device=self.device),
-                 "rec_rows": torch.empty(rec_cap, 6, device=self.device),
-                 "rec_win": torch.empty(rec_cap, dtype=torch.int32, device=self.device),
-                 "rec_state": torch.zeros(2, dtype=torch.int32, device=self.device)}       # {rec_count, overflow flag}
-            if track is not None:
-                g["rec_track"] = torch.empty(rec_cap, dtype=torch.int32, device=self.device)
-                g["trk_state"] = _tracker.new_state(self.device, track)
-            self._stream = g
-        if self.use_graph and "graph" not in g:
-            # a warm-up group sizes the arenas (what it appends is dropped: the record's state is zeroed below), then the capture
-            g["cur"].copy_(table[0], non_blocking=True)
-            self._stream_chain(g)
-            torch.cuda.synchronize()
-            for a in arenas:
-                a.frozen = True
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                self._stream_chain(g)
-            torch.cuda.synchronize()
-            g["graph"] = graph
-            self.stream_captures += 1
-        g["rec_state"].zero_()
-        if track is not None:
-            for t in g["trk_state"]:
-                t.zero_()
-        for gi in range(G):
-            g["cur"].copy_(table[gi], non_blocking=True)
-            if self.use_graph:
-                g["graph"].replay()
-                self.stream_replays += 1
-            else:
-                self._stream_chain(g)
+            self._stream = g = _GroupChain(self, "stream", wave, False, win_len, batch, rec_cap, track, key)
+            g.prepare()
+        g.zero()
+        for row in table:
+            g.run(row)
         torch.cuda.synchronize()
-        for a in arenas:
-            a.frozen = True
-        self.last_cls, self.last_reg = g["cls"], g["reg"]
-        n, over = g["rec_state"].cpu().tolist()
-        self.check_overflow()
-        if over or n > rec_cap:
-            raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, rec_cap))
-        rows, window = g["rec_rows"][:n].cpu().numpy(), g["rec_win"][:n].cpu().numpy()
-        if track is None:
-            return rows, window, None
-        if int(g["trk_state"][1][1].item()):
-            raise RuntimeError(_tracker.overflow_message(track, window))
-        return rows, window, g["rec_track"][:n].cpu().numpy()
+        self.last_cls, self.last_reg = g.cls, g.reg
+        got = g.read(lambda lo, hi: g.blob[lo:hi].cpu().numpy(), int(self.overflow.item()),
+                     0 if track is None else int(g.trk_state[1][1].item()))
+        return got if track is not None else got + (None,)
 
     def _overflow_message(self) -> str:
         return "detection capacity exceeded (cand_cap = %d rows per image; 0 = unlimited)" % self.cand_cap
@@ -344,6 +285,111 @@ class AudioDetector:
         self._stream = None
         self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len, sample_rate, in_ring_len)
         return self._live
+
+
+class _GroupChain:
+    """The buffers and the graph of one group of `batch` windows, for `detect_stream` / `track_stream` (source: the recording [8,
+    n_total]) and for a `LiveSession` (source: its ring [8, ring_len]): front end on the windows the control row names -> resize ->
+    forward -> decode -> NMS [-> track update] -> append to the record.
+
+    The control row `cur` is int64 starts[batch], then {n_valid, first_window} as two int32 in the last word (`control_table`).  The
+    record is ONE block of int32 words, rows [rec_cap, 6] (float bits) | window [rec_cap] | track [rec_cap] | {count, overflow}, so a
+    client may copy it in one piece."""
+
+    def __init__(self, det: AudioDetector, kind: str, source: torch.Tensor, ring: bool, win_len: int, batch: int, rec_cap: int,
+                 track: Optional[TrackConfig], key=None):
+        dev, C = det.device, det.net.spec.in_channels
+        self.det, self.kind, self.source, self.ring, self.win_len, self.rec_cap, self.track, self.key = \
+            det, kind, source, ring, win_len, rec_cap, track, key       # kind: "stream" / "live", the detector's counters to bump
+        self.cur = torch.zeros(batch + 1, dtype=torch.int64, device=dev)
+        self.starts, self.ctl = self.cur[:batch], self.cur[batch:].view(torch.int32)
+        self.mel = torch.empty(batch, det.front.n_mels, det.front.n_frames(win_len), C, device=dev)
+        self.max_ws = torch.empty(batch * C, device=dev)
+        self.audio = torch.empty(batch, C, det.S, det.S, device=dev)
+        self.blob = blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, device=dev)
+        self.rec_rows = blob[:6 * rec_cap].view(torch.float32).view(rec_cap, 6)
+        self.rec_win, self.rec_track, self.rec_state = blob[6 * rec_cap:7 * rec_cap], blob[7 * rec_cap:8 * rec_cap], blob[8 * rec_cap:]
+        self.trk_state = None if track is None else _tracker.new_state(dev, track)
+        self.graph = None
+
+    def issue(self):
+        """One group on the current stream.  The track update reads the record's count before the append advances it."""
+        det, front = self.det, self.det.front
+        windows_into = front.melspec_windows_ring_into if self.ring else front.melspec_windows_into
+        windows_into(self.source, self.starts, self.win_len, True, self.max_ws, self.mel)
+        audio = front.resize_into(self.mel, det.S, self.audio)
+        det._tail(audio, self)
+        if self.track is not None:
+            _tracker.update(self.rows, self.cnt, self.ctl, self.rec_state[0:1], self.rec_cap, self.rec_track, self.trk_state, self.track)
+        _lib.call("mmd_det_record_append", self.rows, self.cnt, audio.shape[0], self.rows.shape[1], self.ctl, self.rec_rows, self.rec_win,
+                  self.rec_cap, self.rec_state[0:1], self.rec_state[1:2])
+
+    def _count(self, what: str):
+        """the detector's stream_captures / stream_replays / live_captures / live_replays"""
+        setattr(self.det, self.kind + what, getattr(self.det, self.kind + what) + 1)
+
+    def _capture(self):
+        self.graph = self.det._capture(self.issue)
+        self._count("_captures")
+
+    def prepare(self):
+        """A warm-up group sizes the arenas - the control row is still zero: window 0, no real window, nothing recorded or tracked -
+        then the capture."""
+        det = self.det
+        det._freeze_arenas(False)
+        self.issue()
+        torch.cuda.synchronize()
+        det._freeze_arenas(True)
+        self.zero()
+        if det.use_graph:
+            self._capture()
+
+    def run(self, row: torch.Tensor):
+        """One group from a control row (device or pinned host memory), replayed or eager"""
+        det = self.det
+        if det.use_graph and self.graph is None:
+            self._capture()                       # prepared with use_graph = False
+        self.cur.copy_(row, non_blocking=True)
+        if det.use_graph:
+            self.graph.replay()
+            self._count("_replays")
+        else:
+            self.issue()
+
+    def zero(self):
+        """An empty record, no tracks (ids start at 0 again)"""
+        self.rec_state.zero_()
+        if self.track is not None:
+            for t in self.trk_state:
+                t.zero_()
+
+    def read(self, fetch, det_overflow: int, trk_overflow: int):
+        """fetch(lo, hi) -> a host copy (numpy int32 the caller does not reuse) of the record's words [lo, hi), made after the
+        device finished; the two flags are the detector's and the tracker's overflow -> (rows [n, 6], window [n][, track [n]])"""
+        R = self.rec_cap
+        n, over = fetch(8 * R, 8 * R + 2).tolist()
+        if det_overflow:
+            raise RuntimeError(self.det._overflow_message())
+        if over or n > R:
+            raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, R))
+        rows, window = fetch(0, 6 * n).view(np.float32).reshape(n, 6), fetch(6 * R, 6 * R + n)
+        if self.track is None:
+            return rows, window
+        if trk_overflow:
+            raise RuntimeError(_tracker.overflow_message(self.track, window))
+        return rows, window, fetch(7 * R, 7 * R + n)
+
+    @staticmethod
+    def control_table(groups: list, batch: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """groups: (starts [1 .. batch], first_window) per group -> int64 [len(groups), batch + 1], one control row per group: the
+        starts, the last one repeated up to batch, then {n_valid, first_window} as two int32 in the last word.  out: an int64
+        [>= len(groups), batch + 1] table to write the rows into (a session's pinned one); its first len(groups) rows are returned."""
+        table = np.empty((len(groups), batch + 1), np.int64) if out is None else out[:len(groups)]
+        tail = table.view(np.int32).reshape(len(groups), 2 * (batch + 1))[:, 2 * batch:]
+        for k, (real, first) in enumerate(groups):
+            table[k, :batch] = list(real) + [real[-1]] * (batch - len(real))
+            tail[k] = (len(real), first)
+        return table
 
 
 class LiveSession:
@@ -396,7 +442,7 @@ class LiveSession:
             raise ValueError("open_stream: hop = %d: the windows must advance by at least one sample" % hop)
         if batch < 1 or batch > 1024:
             raise ValueError("open_stream: batch = %d (1 .. 1024)" % batch)
-        n_frames = det.front.n_frames(win_len)    # raises on a window too short for the reflect padding
+        det.front.n_frames(win_len)               # raises on a window too short for the reflect padding
         span = live_group_span(win_len, hop, batch)
         cap = 2 * span if ring_len is None else int(ring_len)
         if cap < span:
@@ -424,44 +470,14 @@ class LiveSession:
         rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
         if rec_cap > 0x7fffffff // 8:
             raise ValueError("open_stream: a record of %d rows" % rec_cap)
-        self.rec_cap = rec_cap
-        # the record as ONE block of int32 words: rows [rec_cap, 6] (float bits), window [rec_cap], track [rec_cap], {count, overflow}
-        blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, device=dev)
-        self._blob, self._h_blob = blob, torch.zeros(8 * rec_cap + 2, dtype=torch.int32, pin_memory=True)
+        self._h_blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, pin_memory=True)      # the record's host copy
         self._h_flags = torch.zeros(3, dtype=torch.int32, pin_memory=True)       # detector overflow; tracker {next_id, overflow}
-        cur = torch.zeros(batch + 1, dtype=torch.int64, device=dev)
-        self.g = g = {"track": track, "ring": torch.zeros(C, cap, device=dev), "win_len": win_len, "rec_cap": rec_cap, "cur": cur,
-                      "starts": cur[:batch], "ctl": cur[batch:].view(torch.int32),
-                      "mel": torch.empty(batch, det.front.n_mels, n_frames, C, device=dev),
-                      "max_ws": torch.empty(batch * C, device=dev), "audio": torch.empty(batch, C, det.S, det.S, device=dev),
-                      "rec_rows": blob[:6 * rec_cap].view(torch.float32).view(rec_cap, 6), "rec_win": blob[6 * rec_cap:7 * rec_cap],
-                      "rec_track": blob[7 * rec_cap:8 * rec_cap], "rec_state": blob[8 * rec_cap:]}
-        if track is not None:
-            g["trk_state"] = _tracker.new_state(dev, track)
+        self.chain = _GroupChain(det, "live", torch.zeros(C, cap, device=dev), True, win_len, batch, rec_cap, track)
         self._h_ctl = torch.zeros(1, batch + 1, dtype=torch.int64, pin_memory=True)
         self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
         self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
         self._pushes = 0
-        # a warm-up group on the zeroed ring sizes the arenas; its control row says 0 real windows: nothing is recorded or tracked
-        arenas = (det.ws, det.net.arena, det.net.zarena)
-        for a in arenas:
-            a.frozen = False                      # chunks are only ever appended: the graphs of `_detect` stay valid
-        det._stream_chain(g)
-        torch.cuda.synchronize()
-        for a in arenas:
-            a.frozen = True
-        self._zero_state()
-        if det.use_graph:
-            self._capture()
-
-    def _capture(self):
-        det, g = self.det, self.g
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            det._stream_chain(g)
-        torch.cuda.synchronize()
-        g["graph"] = graph
-        det.live_captures += 1
+        self.chain.prepare()                      # the warm-up group reads the zeroed ring
 
     # ---- state
     def _check_open(self, pushing: bool = False):
@@ -470,77 +486,46 @@ class LiveSession:
         if pushing and self.flushed:
             raise RuntimeError("the recording was flushed: reset() starts the next one")
 
-    def _zero_state(self):
-        self.g["rec_state"].zero_()
-        if self.track is not None:
-            for t in self.g["trk_state"]:
-                t.zero_()
-
     def reset(self):
         """Starts a new recording on the same session: position 0 (the input position too), window 0, the tracker zeroed (ids start at
         0 again); the graph, the rings and every buffer stay (they need no clearing: no window reads a slot this recording has not
         written, and the resampler reads zeros for whatever this recording has not pushed)."""
         self._check_open()
         self.written, self.group, self.flushed, self.in_written = 0, 0, False, 0
-        self._zero_state()
+        self.chain.zero()
 
     def close(self):
         """Releases the session's buffers and graph."""
         if not self.closed:
             torch.cuda.synchronize()
             self.closed = True
-            self.g = self._blob = self._h_blob = self._stage = self.in_ring = None
+            self.chain = self._h_blob = self._stage = self.in_ring = None
             if self.det._live is self:
                 self.det._live = None
 
     # ---- one group
     def _control_rows(self, rows: list) -> torch.Tensor:
-        """rows: (starts [<= batch], first_window) per group -> the pinned table, one row per group as `_run_stream` lays it out: int64
-        starts[batch] (the last window repeated up to batch), then {n_valid, first_window} as two int32 in the last word"""
+        """rows: (starts [<= batch], first_window) per group -> the pinned table, one control row per group"""
         if self._h_ctl.shape[0] < len(rows):
             self._h_ctl = torch.zeros(len(rows), self.batch + 1, dtype=torch.int64, pin_memory=True)
-        table = self._h_ctl.numpy()
-        tail = table.view(np.int32).reshape(table.shape[0], 2 * (self.batch + 1))[:, 2 * self.batch:]
-        for k, (real, first) in enumerate(rows):
-            table[k, :self.batch] = real + [real[-1]] * (self.batch - len(real))
-            tail[k] = (len(real), first)
+        _GroupChain.control_table(rows, self.batch, self._h_ctl.numpy())
         return self._h_ctl
-
-    def _run_group(self, row: torch.Tensor):
-        det, g = self.det, self.g
-        if det.use_graph and "graph" not in g:
-            self._capture()                       # the session was opened with use_graph = False
-        g["cur"].copy_(row, non_blocking=True)
-        if det.use_graph:
-            g["graph"].replay()
-            det.live_replays += 1
-        else:
-            det._stream_chain(g)
 
     def _drain(self):
         """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
-        det, g, R = self.det, self.g, self.rec_cap
-        self._h_blob.copy_(self._blob, non_blocking=True)
+        det, chain = self.det, self.chain
+        self._h_blob.copy_(chain.blob, non_blocking=True)
         self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
         if self.track is not None:
-            self._h_flags[1:3].copy_(g["trk_state"][1], non_blocking=True)
-        g["rec_state"].zero_()
+            self._h_flags[1:3].copy_(chain.trk_state[1], non_blocking=True)
+        chain.rec_state.zero_()
         torch.cuda.synchronize()
-        det.last_cls, det.last_reg = g["cls"], g["reg"]
+        det.last_cls, det.last_reg = chain.cls, chain.reg
         h = self._h_blob.numpy()
-        n, over = int(h[8 * R]), int(h[8 * R + 1])
-        if int(self._h_flags[0]):
-            raise RuntimeError(det._overflow_message())
-        if over or n > R:
-            raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, R))
-        rows, window = h[:6 * n].view(np.float32).reshape(n, 6).copy(), h[6 * R:6 * R + n].copy()
-        if self.track is None:
-            return rows, window
-        if int(self._h_flags[2]):
-            raise RuntimeError(_tracker.overflow_message(self.track, window))
-        return rows, window, h[7 * R:7 * R + n].copy()
+        return chain.read(lambda lo, hi: h[lo:hi].copy(), int(self._h_flags[0]), int(self._h_flags[2]))
 
-    def _result(self, parts: list):
+    def concat(self, parts: list):
+        """what several pushes (and `flush`) returned -> one result of the same form; no parts: the empty one"""
         if not parts:
             parts = [(np.zeros((0, 6), np.float32), np.zeros(0, np.int32)) + ((np.zeros(0, np.int32),) if self.track is not None else ())]
         return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
@@ -558,12 +543,12 @@ class LiveSession:
             else:
                 if k:
                     parts.append(self._drain())   # the record holds one group
-                self._run_group(table[k])
+                self.chain.run(table[k])
                 k += 1
         self.written, self.group = written, group
         if k:
             parts.append(self._drain())
-        return self._result(parts)
+        return self.concat(parts)
 
     def _produce(self, final: bool):
         """the 44.1 kHz samples the input pushed so far allows (final: up to the recording's end), through the schedule: every ring write
@@ -571,14 +556,14 @@ class LiveSession:
         rate, L, M, half = self.rs
         ready = live_resample_ready(self.in_written, L, M, half, final)
         if ready == self.written:
-            return self._result([])
-        rs, in_ring, ring, n_valid = self.det.resampler, self.in_ring, self.g["ring"], self.in_written
+            return self.concat([])
+        rs, in_ring, ring, n_valid = self.det.resampler, self.in_ring, self.chain.source, self.in_written
         return self._advance(ready - self.written, lambda off, cnt, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
 
     def _feed(self, n: int, write):
         """one chunk of n samples; write(offset into the chunk, samples, ring, its length, absolute position) queues one ring write"""
         if self.rs is None:
-            ring, cap = self.g["ring"], self.ring_len
+            ring, cap = self.chain.source, self.ring_len
             return self._advance(n, lambda off, cnt, pos: write(off, cnt, ring, cap, pos))
         _, L, M, half = self.rs
         piece, parts = self.in_ring_len - 2 * half - M, []       # the oldest input a pending output needs survives the piece
@@ -587,7 +572,7 @@ class LiveSession:
             write(off, cnt, self.in_ring, self.in_ring_len, self.in_written)
             self.in_written += cnt
             parts.append(self._produce(False))
-        return self._result(parts)
+        return self.concat(parts)
 
     # ---- chunks
     def _to_device(self, host: torch.Tensor) -> torch.Tensor:
@@ -650,13 +635,13 @@ class LiveSession:
         produces the recording's last outputs (and runs the full groups they complete).  Afterwards only `reset` or `close`."""
         self._check_open()
         if self.flushed:
-            return self._result([])
+            return self.concat([])
         self.flushed = True
         parts = [self._produce(True)] if self.rs is not None else []
         W = 0 if self.written < self.win_len else 1 + (self.written - self.win_len) // self.hop
         first = self.group * self.batch
         if W > first:
             table = self._control_rows([([w * self.hop for w in range(first, W)], first)])
-            self._run_group(table[0])
+            self.chain.run(table[0])
             parts.append(self._drain())
-        return self._result(parts)
+        return self.concat(parts)

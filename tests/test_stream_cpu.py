@@ -42,6 +42,28 @@ def test_window_starts_refuses_bad_arguments():
         starts(4095, 4096, 100)
 
 
+# ---------------------------------------------------------------------------------------------- control table
+def test_control_table_lays_out_starts_padding_and_the_two_int32_halves():
+    """One control row per group, as csrc/stream.hip and the front end read it: int64 starts[batch], a short group padded with its last
+    real window, then n_valid in the low and first_window in the high int32 of the last (little-endian) word.  No device."""
+    from mm_distillnet_amd.detector import _GroupChain
+    cases = ((3, [([0, 1531, 3062], 0), ([4593, 6124, 7655], 3), ([9186, 10717], 6)]),          # two full groups, a short last one
+             (4, [([7, 2 ** 40 + 5], 2 ** 31 - 3)]),                                           # a start past 2^32, a large window index
+             (1, [([0], 0), ([1531], 1), ([3062], 2)]))                                        # batch = 1: never padded
+    for batch, groups in cases:
+        table = _GroupChain.control_table(groups, batch)
+        assert table.dtype == np.int64 and table.shape == (len(groups), batch + 1) and table.flags.c_contiguous
+        for row, (real, first) in zip(table, groups):
+            assert row[:batch].tolist() == real + [real[-1]] * (batch - len(real))
+            assert row[batch:].view("<i4").tolist() == [len(real), first]
+            assert int(row[batch]) == len(real) + (first << 32)
+        # into a provided table (a session's pinned one, longer than needed and dirty): the same bytes, the other rows untouched
+        given = np.full((len(groups) + 2, batch + 1), -1, np.int64)
+        got = _GroupChain.control_table(groups, batch, given)
+        assert got.tobytes() == table.tobytes() and np.shares_memory(got, given)
+        assert np.array_equal(given[:len(groups)], table) and (given[len(groups):] == -1).all()
+
+
 # ---------------------------------------------------------------------------------------------- detect.py
 def test_window_option_refuses_a_stack_of_clips_before_any_gpu_call(tmp_path, monkeypatch):
     det = _detect()
