@@ -214,14 +214,14 @@ def bn_bwd_reduce(g_in, z, scale, shift, mean, invstd, act, mul_bc, mul_b, add_b
     return g, Ag, sums, A
 
 
-def bn_bwd_apply(g, Ag, z, mean, invstd, gamma, sums, count, dgamma0=None, dbeta0=None):
+def bn_bwd_apply(g, Ag, z, mean, invstd, gamma, sums, count, dgamma0=None, dbeta0=None, k=None):
     """dz = gamma*invstd*(g - m1 - xhat*m2), m = sums / count (sums: the float64 numbers the kernel receives); dgamma += sum g*xhat,
-    dbeta += sum g"""
+    dbeta += sum g.  k: the factor gamma*invstd itself where the kernel is handed that (the GEMM operand forms receive `scale`)"""
     C = z.shape[1]
     dt = z.dtype
     m1, m2 = (sums[:C] / float(count)).to(dt), (sums[C:] / float(count)).to(dt)
     xh = (z - mean) * invstd
-    k = gamma * invstd
+    k = gamma * invstd if k is None else k
     dz = k * (g - m1 - xh * m2)
     A = k.abs() * (Ag + m1.abs() + (xh * m2).abs())
     out = {"dz": (dz, A)}

@@ -4,10 +4,12 @@ MMD_PW_FORM_NATIVE) and mmd_pwconv_fwd_bf16 - written from the contract of pw_fw
 not from the kernels' loops; a copy of the host dispatch (route); and the one case table (PW_CASES) that test_pw_ref_cpu.py and
 test_gpu_pw_float64.py share.
 
-OUT OF SCOPE here (the backward half can be picked up from this module: pw_fwd is the forward of every one of them): every *_bwd_* entry
-point (input gradient, weight gradient, their BatchNorm-backward operand forms), the grouped weight gradient (pw_wgrad_grouped.hip),
-mmd_pwconv_fwd_pyr*, the grouped-nets mode (mmd_set_group), the stem im2col GEMM (mmd_pw_stem_gemm), the slab family (form 4,
-pw_slab.hip: route names it where the auto form could take a launch, and no case may land there) and the MMD_STREAM dev kernel.
+The weight gradient - the grouped launch of pw_wgrad_grouped.hip and the per-layer mmd_pwconv_bwd_weight* entry points, their
+BatchNorm-backward operand forms included - lives in wg_ref.py, which takes its X operand from pw_operand below.
+OUT OF SCOPE still (pw_fwd is the forward of every one of them): the input-gradient entry points (mmd_pwconv_bwd_data*) with their
+BatchNorm-backward operand forms, mmd_pwconv_fwd_pyr*, the grouped-nets mode (mmd_set_group), the stem im2col GEMM (mmd_pw_stem_gemm) and
+the stem weight gradient, the slab family (form 4, pw_slab.hip: route names it where the auto form could take a launch, and no case may
+land there) and the MMD_STREAM dev kernel.
 
 Conventions are those of elt_ref.py / dw_ref.py.  pw_fwd computes in the dtype (and on the device) of its tensor arguments: float64 is the
 oracle, float32 the "plain fp32" evaluation that calibrates K.  It returns {"y", "sum", "sumsq"} of (value, A), A_i the magnitude of
@@ -71,14 +73,8 @@ def remap_index(M, N, rpi, y_batch_stride, y_offset, device="cpu"):
     return ((m // rpi) * y_batch_stride + y_offset + (m % rpi) * N).unsqueeze(1) + torch.arange(N, device=device)
 
 
-def pw_fwd(x, w, in_scale=None, in_shift=None, A_shift=None, in_act=0, live=None, gate=None, rpi=0, bias=None, out_scale=None,
-           out_shift=None, out_act=0, residual=None, stats0=None, dot=None, bf16=False):
-    """pw_fwd_impl: y = act(raw*out_scale + out_shift) + residual, raw = (gate[row // rpi] * act(x*scale + shift)) @ w^T + bias,
-    stats0 + [sum raw, sum raw^2].  live = (float64 sums [2K], count, gamma, beta) instead of in_scale / in_shift.  dot: the product
-    (default a @ w^T); bf16: operand and weight rounded to bf16, exact products.  -> {"y", "sum", "sumsq"} of (value, A), y as [M, N]"""
-    dt = x.dtype
-    if live is not None:
-        in_scale, in_shift, A_shift = live_coef(*live)
+def pw_operand(x, in_scale=None, in_shift=None, A_shift=None, in_act=0, gate=None, rpi=0):
+    """the GEMM's X operand a = gate[row // rpi] * act(x*scale + shift) with its magnitude (the forward's and the weight gradient's)"""
     if in_scale is None:
         u, Au = x, x.abs()
     else:
@@ -87,6 +83,18 @@ def pw_fwd(x, w, in_scale=None, in_shift=None, A_shift=None, in_act=0, live=None
     if gate is not None:
         gr = gate[torch.arange(x.shape[0], device=x.device) // rpi]
         a, Aa = a * gr, Aa * gr.abs()
+    return a, Aa
+
+
+def pw_fwd(x, w, in_scale=None, in_shift=None, A_shift=None, in_act=0, live=None, gate=None, rpi=0, bias=None, out_scale=None,
+           out_shift=None, out_act=0, residual=None, stats0=None, dot=None, bf16=False):
+    """pw_fwd_impl: y = act(raw*out_scale + out_shift) + residual, raw = (gate[row // rpi] * act(x*scale + shift)) @ w^T + bias,
+    stats0 + [sum raw, sum raw^2].  live = (float64 sums [2K], count, gamma, beta) instead of in_scale / in_shift.  dot: the product
+    (default a @ w^T); bf16: operand and weight rounded to bf16, exact products.  -> {"y", "sum", "sumsq"} of (value, A), y as [M, N]"""
+    dt = x.dtype
+    if live is not None:
+        in_scale, in_shift, A_shift = live_coef(*live)
+    a, Aa = pw_operand(x, in_scale, in_shift, A_shift, in_act, gate, rpi)
     if bf16:
         raw = (a.bfloat16().double() @ w.bfloat16().double().t()).to(dt)
     else:
@@ -357,3 +365,27 @@ def case_ref(case, mode, inp, dt, dev="cpu", **model):
 
 def inputs_of(case, mode):
     return case_inputs(case, wide=mode[0] == "wide")
+
+
+# ------------------------------------------------------------------------------------------------ shared by the GPU test modules
+GPU_ERROR = []          # a launch or runtime error met by an earlier test: nothing more is launched on a device that may have faulted
+
+
+class Out:
+    """an output tensor of `shape` followed by 16 guard rows; fill: 'nan' (must be overwritten), 'sent' (the sentinel: only a window of it
+    is written) or a CPU tensor (must be accumulated on)"""
+
+    def __init__(self, shape, fill, dtype=torch.float32, device="cuda"):
+        n = math.prod(shape)
+        self.n = n
+        self.buf = torch.full((n + 16 * shape[-1],), SENTINEL, dtype=dtype, device=device)
+        self.t = self.buf[:n].view(shape)
+        if isinstance(fill, str):
+            if fill == "nan":
+                self.t.fill_(float("nan"))
+        else:
+            self.t.copy_(fill.to(dtype))
+
+    def get(self):
+        assert bool((self.buf[self.n:] == SENTINEL).all()), "guard rows behind the output were written"
+        return self.t

@@ -11,7 +11,6 @@ afterwards, and the launch must agree with the ws_slots = 0 launch (sums to 1e-1
 launches, the family they fall through to); the split and the native form of one launch must differ in bits; a long-K launch is repeated
 three times with the same bits.  Each check prints `PW64 <family> <form> <case> <mode> <worst err / (unit A)> (K)` before it asserts.  The
 float64 references run on the GPU in torch (a plain matmul: nothing of the library under test)."""
-import math
 import os
 import time
 
@@ -23,6 +22,7 @@ pytestmark = pytest.mark.gpu
 from mm_distillnet_amd import _lib
 
 import pw_ref as R
+from pw_ref import Out, GPU_ERROR          # the guarded output buffer; the list of GPU errors met by earlier tests
 
 call = _lib.call
 DEV = "cuda"
@@ -33,26 +33,6 @@ SPLIT_DEFAULT = not os.environ.get("MMD_MFMA_F32")
 
 def g(t):
     return None if t is None else t.detach().contiguous().to(DEV)
-
-
-class Out:
-    """an output tensor of `shape` followed by 16 guard rows; fill: 'nan' (must be overwritten), 'sent' (the sentinel: only a window of it
-    is written) or a CPU tensor (must be accumulated on)"""
-
-    def __init__(self, shape, fill, dtype=torch.float32):
-        n = math.prod(shape)
-        self.n = n
-        self.buf = torch.full((n + 16 * shape[-1],), R.SENTINEL, dtype=dtype, device=DEV)
-        self.t = self.buf[:n].view(shape)
-        if isinstance(fill, str):
-            if fill == "nan":
-                self.t.fill_(float("nan"))
-        else:
-            self.t.copy_(fill.to(dtype))
-
-    def get(self):
-        assert bool((self.buf[self.n:] == R.SENTINEL).all()), "guard rows behind the output were written"
-        return self.t
 
 
 def judge(family, label, got, ref, A):
@@ -107,9 +87,6 @@ def launch(case, mode, flabel, dev, inp, rec, use_ws=True):
     if st:
         got["sum"], got["sumsq"] = st.get()[:N], st.get()[N:]
     return got, ws
-
-
-GPU_ERROR = []          # a launch or runtime error met by an earlier test: nothing more is launched on a device that may have faulted
 
 
 def run_case(name, flabel):
