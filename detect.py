@@ -5,6 +5,8 @@
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
                      [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS]
+    python detect.py --config_file F --checkpoint P --input X0 --input X1 [--input X2 ...] --output out.csv
+                     --window_s SECONDS --chunk_s SECONDS [--hop_s SECONDS] [--batch N] [--track ...]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -42,6 +44,13 @@ resampler's filter history is carried across chunks in a ring of input samples o
 --sample_rate R (default 44100).  Window count and CSV times are those of the ceil(N * 44100 / R) resampled samples, and the CSV is
 byte for byte the one --resample --window_s ... (for a `.npy`: --sample_rate R --window_s ...) writes for the same file, with or
 without --track.
+
+With several --input (only with --window_s and --chunk_s) every file is one recording of its own - several microphone arrays side by
+side - and they go through ONE bank of live sessions (`AudioDetector.open_bank`), session k = the k-th --input.  The files are read
+--chunk_s at a time in round robin, exhausted files drop out of the rotation, and one forward pass serves --batch ready windows of
+whichever recordings completed them (--batch defaults to the number of files: one fresh window of each).  The CSV gains a first column:
+session,window,t_start_s,x1,y1,x2,y2,score,label[,track]; window and track ids count per session, and the rows come in the order the
+bank ran them.  Several inputs do not go with --resample / --sample_rate / --live_s: the bank reads 44.1 kHz input only.
 """
 import argparse
 import csv
@@ -65,6 +74,7 @@ CHANNELS, SAMPLE_RATE = 8, 44100
 COLUMNS = ("clip", "x1", "y1", "x2", "y2", "score", "label")
 STREAM_COLUMNS = ("window", "t_start_s", "x1", "y1", "x2", "y2", "score", "label")
 TRACK_COLUMNS = STREAM_COLUMNS + ("track",)
+BANK_COLUMNS = ("session",) + STREAM_COLUMNS
 
 
 def read_npy(path: str) -> np.ndarray:
@@ -193,6 +203,20 @@ def write_track_csv(path: str, rows, window, track, hop: int) -> int:
     return _write_windows_csv(path, TRACK_COLUMNS, rows, window, hop, track)
 
 
+def write_bank_csv(path: str, rows, session, window, hop: int, track=None) -> int:
+    """rows [R, 6] / session [R] / window [R][ / track [R]] of a `LiveBank` at a hop of `hop` samples"""
+    rows, session, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(session).reshape(-1), np.asarray(window).reshape(-1)
+    last = [[]] * len(rows) if track is None else [[t] for t in np.asarray(track).reshape(-1).tolist()]
+    if not (len(session) == len(window) == len(last) == len(rows)):
+        raise ValueError("write_bank_csv: %d rows, %d sessions, %d windows, %d track ids" % (len(rows), len(session), len(window), len(last)))
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(BANK_COLUMNS + (("track",) if track is not None else ()))
+        for q, w, r, t in zip(session.tolist(), window.tolist(), rows, last):
+            out.writerow([q, w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + t)
+    return len(rows)
+
+
 def stream_sizes(window_s: float, hop_s, n_total: int):
     """-> (win_len, hop, number of windows) in samples; raises ValueError as `stream_window_starts` does"""
     from mm_distillnet_amd.audio import stream_window_starts
@@ -214,6 +238,23 @@ def check_chunk_flags(a):
         raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
     if os.path.splitext(a.input)[1].lower() not in (".npy", ".wav"):
         raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+
+
+def check_bank_flags(a):
+    """several --input: what can be refused from the flags alone, before any device work"""
+    if len(a.inputs) < 2:
+        return
+    if a.window_s is None or a.chunk_s is None:
+        raise ValueError("several --input are read side by side into a bank of live sessions: they need --window_s and --chunk_s")
+    if a.resample or a.sample_rate is not None or a.live_s is not None:
+        raise ValueError("several --input do not go with --resample / --sample_rate / --live_s: the bank reads 44.1 kHz input only")
+    if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
+        raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
+    for path in a.inputs:
+        if os.path.splitext(path)[1].lower() not in (".npy", ".wav"):
+            raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
+    if a.batch is not None and a.batch < 1:
+        raise ValueError(f"--batch {a.batch}")
 
 
 def check_live_flags(a):
@@ -293,16 +334,38 @@ def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track, sample_r
     return session.concat(parts)
 
 
-def main(argv=None):
+def run_bank(det, sources: list, win_len: int, hop: int, batch: int, track):
+    """sources: the chunk iterators of `open_chunked`, one per session -> what the bank returns for the round robin over them: one chunk
+    of every file that still has one, in file order, again and again; `flush` at the end"""
+    bank = det.open_bank(len(sources), win_len, hop, batch=batch, track=track)
+    parts, live = [], list(enumerate(iter(src) for src in sources))
+    while live:
+        still = []
+        for k, it in live:
+            got = next(it, None)
+            if got is None:
+                continue
+            c, width = got
+            parts.append(bank.push(k, c) if width is None else bank.push_pcm(k, c, width))
+            still.append((k, it))
+        live = still
+    parts.append(bank.flush())
+    bank.close()
+    return bank.concat(parts)
+
+
+def parse_args(argv=None):
+    """-> the arguments; a.input is the one --input (as it always was) or, with several, the first, and a.inputs lists them all.
+    --batch: None when not given - 8 with one input, the number of inputs with several."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--config_file", required=True)
     ap.add_argument("--checkpoint", required=True)
-    ap.add_argument("--input", required=True)
+    ap.add_argument("--input", required=True, action="append", help="a recording; several (with --window_s --chunk_s): one bank session each")
     ap.add_argument("--output", required=True)
     ap.add_argument("--overwrite", type=str, default=None)
     ap.add_argument("--window_s", type=float, default=None, help="slide a window of this many seconds over ONE recording")
     ap.add_argument("--hop_s", type=float, default=None, help="seconds between window starts (default: --window_s)")
-    ap.add_argument("--batch", type=int, default=8, help="windows per launch sequence (with --window_s)")
+    ap.add_argument("--batch", type=int, default=None, help="windows per launch sequence (with --window_s; default 8, with several --input their number)")
     ap.add_argument("--track", action="store_true", help="link the boxes of consecutive windows into tracks (with --window_s)")
     ap.add_argument("--track_iou", type=float, default=0.3, help="smallest IoU at which a track and a box are paired")
     ap.add_argument("--track_beta", type=float, default=0.5, help="velocity gain of the constant-velocity model")
@@ -313,8 +376,34 @@ def main(argv=None):
     ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
     ap.add_argument("--live_s", type=float, default=None, help="read a recording of any rate this many seconds at a time into a live session that resamples (with --window_s)")
     a = ap.parse_args(argv)
+    a.inputs, a.input = a.input, a.input[0]
+    check_bank_flags(a)
+    if len(a.inputs) == 1 and a.batch is None:
+        a.batch = 8
     check_chunk_flags(a)
     check_live_flags(a)
+    return a
+
+
+def main_bank(a, cfg, track):
+    """several --input through one bank"""
+    chunk = int(round(a.chunk_s * SAMPLE_RATE))
+    opened = [open_chunked(path, chunk) for path in a.inputs]
+    sizes = [stream_sizes(a.window_s, a.hop_s, n_total) for n_total, _ in opened]
+    win_len, hop, n_win = sizes[0][0], sizes[0][1], sum(z[2] for z in sizes)
+    torch.cuda.set_device(0)
+    sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
+    c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    det = AudioDetector.from_step_config(sspec, "cuda:0", T.step_config(cfg))
+    det.load(c["state_dict"] if "state_dict" in c else c)
+    got = run_bank(det, [chunks for _, chunks in opened], win_len, hop, len(a.inputs) if a.batch is None else a.batch, track)
+    n = write_bank_csv(a.output, *got[:3], hop, got[3] if track is not None else None)
+    print("%d sessions, %d windows, %d boxes -> %s" % (len(a.inputs), n_win, n, a.output))
+    return got
+
+
+def main(argv=None):
+    a = parse_args(argv)
     track = None
     if a.track:
         if a.window_s is None:
@@ -322,6 +411,8 @@ def main(argv=None):
         from mm_distillnet_amd.tracker import TrackConfig
         track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
+    if len(a.inputs) > 1:
+        return main_bank(a, cfg, track)
     dev = "cuda:0"
     resampled = a.resample or a.sample_rate is not None
     chunked, rate = a.chunk_s is not None or a.live_s is not None, None

@@ -602,6 +602,18 @@ int mmd_melspec_windows(const float* wav, int channels, long long n_total, const
 // win_len > cap.
 int mmd_melspec_windows_ring(const float* ring, int channels, long long cap, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
 
+// mmd_melspec_windows_ring for the rings of a BANK of sessions (AudioDetector.open_bank; the melspectrogram call is merge_audios',
+// src/datasets/MultimodalDetection.py:329-353, the dB map mp3_to_pkl.py:31-41's): rings[n_sessions, channels, cap], one block of
+// memory, absolute sample p of channel c of session s at rings[(s * channels + c) * cap + p % cap].  win_sess[batch] (DEVICE int32)
+// names the session of each window, win_start[batch] (DEVICE int64) its ABSOLUTE position in that session's recording; sessions may
+// repeat and come in any order.  One kernel body, one more mode: only the row base (sess * channels + c) * cap differs, so for db = 0
+// and db = 1 window b's output is bit for bit what mmd_melspec_windows_ring gives for rings + win_sess[b] * channels * cap with the
+// same start.  A session outside 0 .. n_sessions-1 is the CALLER'S ERROR (the kernel clamps it into that range: the wrong window, but
+// no read leaves rings); a negative start is clamped to 0 as in the ring mode.  Launch sequence, max_ws[batch * channels] and out as
+// mmd_melspec_windows_ring: they need no zeroing, two calls give the same bits, no allocation, no host synchronisation.  -22 before
+// any launch on the refusals of mmd_melspec_windows_ring, on a null win_sess and on n_sessions < 1.
+int mmd_melspec_windows_rings(const float* rings, int n_sessions, int channels, long long cap, const int* win_sess, const long long* win_start, int batch, long long win_len, const int* band_start, const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out, hipStream_t stream);
+
 // ---- sample-rate conversion and PCM decoding (csrc/resample.hip): what librosa.load(path, sr=44100) does in front of the mel
 // spectrogram upstream (mp3_to_pkl.py:31; merge_audios, src/datasets/MultimodalDetection.py:335-336).
 // x[rows, n_in] at sr_in -> y[rows, n_out] at sr_out, rows = batch x channels, with L / M = sr_out / sr_in in lowest terms and
@@ -690,6 +702,12 @@ int mmd_ring_resample_span(int L, int M, int taps);
 // rec_cap < 1.
 int mmd_det_record_append(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, float* rec_rows, int* rec_win, int rec_cap, int* rec_count, int* rec_overflow, hipStream_t stream);
 
+// mmd_det_record_append for a bank of sessions (AudioDetector.open_bank), whose groups mix windows of several recordings: n_valid (one
+// DEVICE int32, clamped to 0 .. B) and per-image DEVICE tables win_sess[B], win_idx[B] in place of ctl.  The same scan, order, clamping
+// and overflow rule; each appended row i gets rec_win[i] = win_idx[image] and rec_sess[i] = win_sess[image] (rec_sess[rec_cap] int32,
+// no zeroing needed; the table's values are copied, not checked).  -22 as mmd_det_record_append.
+int mmd_det_record_append_bank(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess, const int* win_idx, float* rec_rows, int* rec_win, int* rec_sess, int rec_cap, int* rec_count, int* rec_overflow, hipStream_t stream);
+
 // ---- streaming tracking (csrc/track.hip, AudioDetector.track_stream): links the rows of a group of windows to the tracks of the
 // windows before - a greedy IoU tracker with a constant-velocity alpha-beta model, alpha = 1 (the rule: DESIGN.md, streaming tracking;
 // tests/track_ref.py restates it in numpy float32 and gives the same bits).  rows / cnt / B / cap_img / ctl as mmd_det_record_append.
@@ -709,6 +727,19 @@ int mmd_det_record_append(const float* rows, const int* cnt, int B, int cap_img,
 // One block of 256 threads, no atomics: two runs give the same bits.  -22 before any launch on null pointers, B < 1, B > 1024,
 // cap_img < 1, rec_cap < 1, max_tracks outside 1 .. 256, max_age < 0.
 int mmd_track_update(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, hipStream_t stream);
+
+// mmd_track_update for a bank of sessions (AudioDetector.open_bank): one tracker per session, trk_slots int32 [n_sessions, max_tracks,
+// 16] and trk_glob int32 [n_sessions, 2], each session's part as mmd_track_update describes it (a zero fill of session s's part resets
+// that session alone).  n_valid / win_sess[B] / win_idx[B] as mmd_det_record_append_bank, whose launch for the same group this one
+// MUST PRECEDE.  One 256-thread block per session: block s walks the rows i < n_valid in row order and runs the per-window body of
+// mmd_track_update (ONE __device__ function for both kernels: one rule, one rounding) for those with win_sess[i] == s, with
+// win_idx[i] as the window's index (`last_window`); a session's windows must come in rising order across and inside groups.  So
+// session s's state and ids are what mmd_track_update leaves after the same windows alone.  Record offsets are the clamped exclusive
+// scan over ALL rows on top of *rec_count, computed by every block; the blocks write disjoint parts of rec_track.  A session with no
+// row in the group is not touched: no word of its state changes, nothing ages.  A row whose session is outside 0 .. n_sessions-1
+// (the CALLER'S ERROR) is tracked by no block and its rec_track entries are not written.  No atomics, plain vector stores.  -22 as
+// mmd_track_update, and on n_sessions outside 1 .. 65535.
+int mmd_track_update_bank(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess, const int* win_idx, int n_sessions, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, hipStream_t stream);
 
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction

@@ -110,6 +110,74 @@ def live_schedule(written: int, group: int, n: int, win_len: int, hop: int, batc
         written = hi
 
 
+def bank_state(n_sessions: int):
+    """The state `bank_schedule` starts a bank of n_sessions from: (written, next, fifo) - per session the samples written so far and
+    the next window to complete, and the FIFO of ready windows (session, window) in order of completion.  Tuples: a state is a value."""
+    n_sessions = int(n_sessions)
+    if n_sessions < 1:
+        raise ValueError(f"a bank of {n_sessions} sessions")
+    return (0,) * n_sessions, (0,) * n_sessions, ()
+
+
+def bank_schedule(state, session: int, n: int, win_len: int, hop: int, batch: int, cap: int):
+    """`live_schedule` for a bank of sessions that push independently (`AudioDetector.open_bank`): what one push of n samples to
+    `session` does, as a list of steps in order: ("write", session, lo, hi) - absolute samples lo .. hi-1 of that session go into its
+    ring (hi - lo <= cap) - and ("run", [(session, window), ...]) - one tick: a forward pass over those `batch` windows.
+    state: (written, next, fifo) as `bank_state` gives it.  -> (steps, state').
+
+    The rule.  Window w of session s is ready once its last sample w * hop + win_len - 1 has been pushed.  Ready windows enter ONE
+    FIFO in the order they complete - inside one push that is window order.  A tick runs exactly when the FIFO holds `batch`
+    windows, and takes all of them, in FIFO order.  Ring writes and ticks alternate inside a push as they do in `live_schedule`: a write to
+    session s never passes (first window of s not yet run) * hop + cap - the slot of sample p is that of p - cap, so nothing a
+    window of s that has not run may still need is overwritten, whatever the chunk's length.  cap >= `live_group_span`(win_len, hop,
+    batch) (ValueError below that) is enough: between ticks the FIFO holds fewer than batch windows, so the first window f of s not yet
+    run has fewer than batch windows of s behind it waiting, and by sample f * hop + span session s alone has completed windows
+    f .. f + batch - 1 - the FIFO reached batch and the tick with f ran before the write limit f * hop + cap.  No forced short tick is
+    ever needed.  Samples in front of the first window of s not yet run are no window's any more (hop > win_len leaves such gaps):
+    they are skipped, not written.  The ticks and their composition depend only on the sequence of cumulative (session, samples)
+    totals: cutting one push into several consecutive pushes to the same session changes nothing."""
+    written, nxt, fifo = list(state[0]), list(state[1]), list(state[2])
+    s, n, win_len, hop, batch, cap = int(session), int(n), int(win_len), int(hop), int(batch), int(cap)
+    if not 0 <= s < len(written):
+        raise ValueError(f"session {s} of a bank of {len(written)}")
+    if hop < 1 or batch < 1 or n < 0:
+        raise ValueError(f"hop = {hop}, batch = {batch}, n = {n}")
+    span = live_group_span(win_len, hop, batch)
+    if cap < span:
+        raise ValueError(f"a ring of {cap} samples is shorter than one group of {batch} windows ({span} samples)")
+    steps, w, end = [], written[s], written[s] + n
+    while True:
+        while nxt[s] * hop + win_len <= w:      # the windows the samples so far complete, in window order
+            fifo.append((s, nxt[s]))
+            nxt[s] += 1
+            if len(fifo) == batch:
+                steps.append(("run", fifo))
+                fifo = []
+        if w == end:
+            written[s] = w
+            return steps, (tuple(written), tuple(nxt), tuple(fifo))
+        first = min([q[1] for q in fifo if q[0] == s], default=nxt[s])      # the first window of s not yet run
+        hi = min(end, first * hop + cap)        # > w: fewer than batch windows of s wait, so w < nxt * hop + win_len <= first * hop + span
+        lo = max(w, first * hop)
+        if lo < hi:
+            steps.append(("write", s, lo, hi))
+        w = hi
+
+
+def bank_step(state):
+    """The short tick: runs NOW whatever the FIFO holds (1 .. batch-1 windows; the control row pads the tick by repeating its last
+    window, and the padding is not recorded).  -> (steps, state'): one ("run", windows) step, or none with an empty FIFO."""
+    written, nxt, fifo = state
+    return ([("run", list(fifo))] if fifo else []), (tuple(written), tuple(nxt), ())
+
+
+def bank_reset(state, session: int):
+    """A new recording on `session`: its position and next window back to 0, its queued windows dropped; the others keep theirs."""
+    written, nxt, fifo = list(state[0]), list(state[1]), state[2]
+    written[session] = nxt[session] = 0
+    return tuple(written), tuple(nxt), tuple(q for q in fifo if q[0] != session)
+
+
 class MelFrontEnd:
     """Holds the band-form filter bank on `device`; every call runs on the current stream and allocates only its result."""
 
@@ -157,6 +225,15 @@ class MelFrontEnd:
         C, cap = ring.shape
         self.call("mmd_melspec_windows_ring", ring, C, cap, win_start, win_start.shape[0], int(win_len), self.start, self.length,
                   self.band, self.stride, 1 if db else 0, max_ws, out)
+        return out
+
+    def melspec_windows_rings_into(self, rings, win_sess, win_start, win_len: int, db: bool, max_ws, out):
+        """`melspec_windows_ring_into` for the rings of a bank of sessions (`mmd_melspec_windows_rings`): rings [n_sessions, C, cap],
+        win_sess int32 [B] and win_start int64 [B] on the device: window b comes out of rings[win_sess[b]] with the bits
+        `melspec_windows_ring_into` gives it there."""
+        n_sessions, C, cap = rings.shape
+        self.call("mmd_melspec_windows_rings", rings, n_sessions, C, cap, win_sess, win_start, win_start.shape[0], int(win_len),
+                  self.start, self.length, self.band, self.stride, 1 if db else 0, max_ws, out)
         return out
 
     def melspec(self, wav_a: torch.Tensor, wav_b: torch.Tensor = None, db: bool = False) -> torch.Tensor:

@@ -94,15 +94,20 @@ __device__ __forceinline__ int mel_pad(int i) { return i + (i >> 4); }
 // win_start[b] an ABSOLUTE sample position: window sample s lives at slot (win_start[b] + s) % cap.  The start is reduced modulo cap
 // once per block; s <= N - 1 < cap, so a slot wraps at most once: one compare and one subtract at the staging load, which is the only
 // line that differs.  A negative start is clamped to 0; every slot read is inside the channel's row.
+// WIN = MEL_WIN_RINGS (mmd_melspec_windows_rings): MEL_WIN_RING for wav_a[n_sess, C, n_total], the rings of a bank of sessions in one
+// block of memory; sample b reads the ring of session win_sess[b].  Only the row base differs: (sess * C + c) * n_total.  The session is
+// clamped into 0 .. n_sess-1: a bad table reads the wrong ring, never outside wav_a.
 #define MEL_WIN_NONE 0
 #define MEL_WIN_LINEAR 1
 #define MEL_WIN_RING 2
+#define MEL_WIN_RINGS 3
 template <bool MIX, bool TRACK, int WIN>
 __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restrict__ wav_a, const float* __restrict__ wav_b, long long N,
                                                             int T, int C, const int* __restrict__ band_start,
                                                             const int* __restrict__ band_len, const float* __restrict__ band_w,
                                                             int band_stride, float* __restrict__ out, unsigned int* __restrict__ mx_ws,
-                                                            const long long* __restrict__ win_start, long long n_total) {
+                                                            const long long* __restrict__ win_start, long long n_total,
+                                                            const int* __restrict__ win_sess, int n_sess) {
   __shared__ float s_x[MEL_STAGE];
   __shared__ float2 s_z[4][MEL_ZROW];
   __shared__ float s_w[MEL_WMAX];
@@ -110,8 +115,14 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
   const int c = blockIdx.y, f0 = blockIdx.x * MEL_FPB;
   const size_t smp = blockIdx.z;
   const float* pa;
-  long long r0 = 0;                                  // MEL_WIN_RING: the window's first slot
-  if (WIN == MEL_WIN_RING) {
+  long long r0 = 0;                                  // MEL_WIN_RING / MEL_WIN_RINGS: the window's first slot
+  if (WIN == MEL_WIN_RINGS) {
+    const long long w0 = win_start[smp];
+    r0 = w0 < 0 ? 0 : w0 % n_total;
+    int ss = win_sess[smp];
+    ss = ss < 0 ? 0 : (ss > n_sess - 1 ? n_sess - 1 : ss);
+    pa = wav_a + ((size_t)ss * C + c) * (size_t)n_total;
+  } else if (WIN == MEL_WIN_RING) {
     const long long w0 = win_start[smp];
     r0 = w0 < 0 ? 0 : w0 % n_total;
     pa = wav_a + (size_t)c * (size_t)n_total;
@@ -135,7 +146,7 @@ __global__ __launch_bounds__(256) void melspec_power_kernel(const float* __restr
     s = s < 0 ? -s : s;
     s = s >= N ? 2 * (N - 1) - s : s;
     s = s < 0 ? 0 : (s > N - 1 ? N - 1 : s);
-    if (WIN == MEL_WIN_RING) {
+    if (WIN == MEL_WIN_RING || WIN == MEL_WIN_RINGS) {
       s += r0;
       s = s >= n_total ? s - n_total : s;
     }
@@ -319,32 +330,37 @@ static void power_to_db_launch(float* x, int batch, size_t per_sample, int C, co
   hipLaunchKernelGGL(power_to_db_kernel, grid, dim3(256), 0, stream, x, per_sample, C, mx_ws);
 }
 
-// The launch sequence of the four entry points below: [zero max_ws ->] melspec_power_kernel<MIX = wav_b, TRACK = db, WIN = win> [-> dB pass].
+// The launch sequence of the five entry points below: [zero max_ws ->] melspec_power_kernel<MIX = wav_b, TRACK = db, WIN = win> [-> dB pass].
 // n_samples: the length of one sample (a window's, in the window modes).  win = MEL_WIN_LINEAR / MEL_WIN_RING: win_start[batch] into ONE
 // recording / ring wav_a[channels, extent], no wav_b; MEL_WIN_NONE: wav_a (+ wav_b) [batch, channels, n_samples], no win_start.
+// MEL_WIN_RINGS: MEL_WIN_RING with wav_a[n_sess, channels, extent] and win_sess[batch]; the other modes pass no win_sess.
 static int melspec_launch(int win, const float* wav_a, const float* wav_b, int batch, int channels, long long n_samples,
                           const long long* win_start, long long extent, const int* band_start, const int* band_len, const float* band_w,
-                          int band_stride, int db, float* max_ws, float* out, hipStream_t stream) {
+                          int band_stride, int db, float* max_ws, float* out, hipStream_t stream, const int* win_sess = nullptr,
+                          int n_sess = 0) {
   if (!wav_a || !band_start || !band_len || !band_w || !out || channels <= 0 || channels > 65535 || batch <= 0 || batch > 65535)
     return MMD_EINVAL;
   if (band_stride <= 0 || band_stride * MEL_NMEL > MEL_WMAX || (db != 0 && db != 1) || (db && !max_ws)) return MMD_EINVAL;
   const int T = mmd_melspec_frames(n_samples);
   if (T < 0 || (win != MEL_WIN_NONE && (!win_start || n_samples > extent))) return MMD_EINVAL;
+  if (win == MEL_WIN_RINGS && (!win_sess || n_sess < 1)) return MMD_EINVAL;
   const dim3 grid(cdiv(T, MEL_FPB), channels, batch), block(256);
   unsigned int* mx = db ? reinterpret_cast<unsigned int*>(max_ws) : nullptr;
   if (db && mel_zero_max(mx, batch, channels, stream) != MMD_OK) return MMD_ELAUNCH;
 #define MEL_LAUNCH(MIX, TRACK, WIN)                                                                                                  \
   hipLaunchKernelGGL((melspec_power_kernel<MIX, TRACK, WIN>), grid, block, 0, stream, wav_a, wav_b, n_samples, T, channels, band_start, \
-                     band_len, band_w, band_stride, out, mx, win_start, extent)
-  // (named in the order the code object has always held the eight instantiations: its bytes stay what they were)
+                     band_len, band_w, band_stride, out, mx, win_start, extent, win_sess, n_sess)
+  // (named in the order the code object has always held the first eight instantiations; the two of MEL_WIN_RINGS come behind them)
   if (win == MEL_WIN_NONE && !db) {
     if (wav_b) MEL_LAUNCH(true, false, MEL_WIN_NONE); else MEL_LAUNCH(false, false, MEL_WIN_NONE);
   } else if (win == MEL_WIN_NONE) {
     if (wav_b) MEL_LAUNCH(true, true, MEL_WIN_NONE); else MEL_LAUNCH(false, true, MEL_WIN_NONE);
   } else if (win == MEL_WIN_LINEAR) {
     if (db) MEL_LAUNCH(false, true, MEL_WIN_LINEAR); else MEL_LAUNCH(false, false, MEL_WIN_LINEAR);
-  } else {
+  } else if (win == MEL_WIN_RING) {
     if (db) MEL_LAUNCH(false, true, MEL_WIN_RING); else MEL_LAUNCH(false, false, MEL_WIN_RING);
+  } else {
+    if (db) MEL_LAUNCH(false, true, MEL_WIN_RINGS); else MEL_LAUNCH(false, false, MEL_WIN_RINGS);
   }
 #undef MEL_LAUNCH
   if (db) power_to_db_launch(out, batch, (size_t)MEL_NMEL * T * channels, channels, mx, stream);
@@ -378,6 +394,15 @@ extern "C" int mmd_melspec_windows_ring(const float* ring, int channels, long lo
                                         int band_stride, int db, float* max_ws, float* out, hipStream_t stream) {
   return melspec_launch(MEL_WIN_RING, ring, nullptr, batch, channels, win_len, win_start, cap, band_start, band_len, band_w,
                         band_stride, db, max_ws, out, stream);
+}
+
+// the rings of a bank of sessions: window b out of the ring of session win_sess[b]
+extern "C" int mmd_melspec_windows_rings(const float* rings, int n_sessions, int channels, long long cap, const int* win_sess,
+                                         const long long* win_start, int batch, long long win_len, const int* band_start,
+                                         const int* band_len, const float* band_w, int band_stride, int db, float* max_ws, float* out,
+                                         hipStream_t stream) {
+  return melspec_launch(MEL_WIN_RINGS, rings, nullptr, batch, channels, win_len, win_start, cap, band_start, band_len, band_w,
+                        band_stride, db, max_ws, out, stream, win_sess, n_sessions);
 }
 
 extern "C" int mmd_power_to_db(float* x, int batch, int h, int w, int channels, float* max_ws, hipStream_t stream) {

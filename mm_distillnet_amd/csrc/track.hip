@@ -13,6 +13,9 @@
 //
 // Offsets: the clamped exclusive scan of cnt[0 .. n_valid-1] on top of *rec_count that det_record_append_kernel does - *rec_count is
 // read, never written, so the launch has to precede the append of the same group.
+//
+// A bank of sessions (mmd_track_update_bank) keeps one such table per session and runs one block per session over the same group: the
+// per-window body is ONE __device__ function, trk_window, that both kernels call.
 #include "common.h"
 
 #define TRK_BMAX 1024       // windows per call (DR_BMAX of stream.hip)
@@ -31,20 +34,172 @@ __device__ __forceinline__ unsigned long long trk_wave_max(unsigned long long v)
   return v;
 }
 
+// The detections of one window and the block's scratch, in LDS
+struct TrackShared {
+  float dx1[TRK_DMAX], dy1[TRK_DMAX], dx2[TRK_DMAX], dy2[TRK_DMAX], darea[TRK_DMAX], dscore[TRK_DMAX], dlabel[TRK_DMAX];
+  int dtrack[TRK_DMAX];            // the id detection d's row gets (-1: none)
+  int dused[TRK_DMAX];             // detection d is matched
+  int live[TRK_SMAX];              // slot t is live (for the births)
+  int birth[TRK_SMAX];             // 1 + the detection that is born into slot t (0: none)
+  unsigned long long wmax[4];
+  int next, over;                  // the tracker's {next_id, overflow} while the block runs
+};
+
+// Slot tid of the track table, in registers for the whole call
+struct TrackSlot {
+  int live, id, hits, misses, last;
+  float x1, y1, x2, y2, vx, vy, label, score;
+};
+
+__device__ __forceinline__ void trk_slot_load(TrackSlot& t, const int* __restrict__ slots, int tid, bool mine) {
+  t.live = 0; t.id = 0; t.hits = 0; t.misses = 0; t.last = 0;
+  t.x1 = t.y1 = t.x2 = t.y2 = t.vx = t.vy = t.label = t.score = 0.f;
+  if (mine) {
+    const int* s = slots + tid * TRK_WORDS;
+    t.live = s[0] != 0;
+    if (t.live) {
+      t.id = s[1];
+      t.x1 = __int_as_float(s[2]); t.y1 = __int_as_float(s[3]); t.x2 = __int_as_float(s[4]); t.y2 = __int_as_float(s[5]);
+      t.vx = __int_as_float(s[6]); t.vy = __int_as_float(s[7]); t.label = __int_as_float(s[8]); t.score = __int_as_float(s[9]);
+      t.hits = s[10]; t.misses = s[11]; t.last = s[12];
+    }
+  }
+}
+
+__device__ __forceinline__ void trk_slot_store(const TrackSlot& t, int* __restrict__ slots, int tid, bool mine) {
+  if (mine) {
+    int* s = slots + tid * TRK_WORDS;
+    s[0] = t.live; s[1] = t.id;
+    s[2] = __float_as_int(t.x1); s[3] = __float_as_int(t.y1); s[4] = __float_as_int(t.x2); s[5] = __float_as_int(t.y2);
+    s[6] = __float_as_int(t.vx); s[7] = __float_as_int(t.vy); s[8] = __float_as_int(t.label); s[9] = __float_as_int(t.score);
+    s[10] = t.hits; s[11] = t.misses; s[12] = t.last;
+  }
+}
+
+// One window through the tracker - the rule and the rounding of both kernels below.  Called by all 256 threads of the block: src = the
+// window's rows [n_all, 6], o = the record row of its first row, widx = the window's index (a track's `last`).  sh.next / sh.over were
+// set before the first window and are visible (a __syncthreads behind them); the call ends with a __syncthreads.
+__device__ __forceinline__ void trk_window(TrackShared& sh, TrackSlot& t, const float* __restrict__ src, int n_all, long long o, int widx,
+                                           int rec_cap, int* __restrict__ rec_track, bool mine, const TrackParams& p) {
+  const int tid = threadIdx.x;
+  const int n = min(n_all, TRK_DMAX);
+  if (tid < n) {
+    const float* r = src + tid * 6;
+    const float a = r[0], b = r[1], c = r[2], d = r[3];
+    sh.dx1[tid] = a; sh.dy1[tid] = b; sh.dx2[tid] = c; sh.dy2[tid] = d;
+    sh.darea[tid] = __fmul_rn(__fsub_rn(c, a), __fsub_rn(d, b));
+    sh.dscore[tid] = r[4]; sh.dlabel[tid] = r[5];
+    sh.dtrack[tid] = -1; sh.dused[tid] = 0;
+  }
+  sh.birth[tid] = 0;
+  if (tid == 0 && n_all > TRK_DMAX) sh.over = 1;
+  // 1. predict
+  float area = 0.f;
+  if (t.live) {
+    t.x1 = __fadd_rn(t.x1, t.vx); t.x2 = __fadd_rn(t.x2, t.vx); t.y1 = __fadd_rn(t.y1, t.vy); t.y2 = __fadd_rn(t.y2, t.vy);
+    area = __fmul_rn(__fsub_rn(t.x2, t.x1), __fsub_rn(t.y2, t.y1));
+  }
+  __syncthreads();
+
+  // 2. this slot's best candidate among the unmatched detections: 0 = none
+  auto best = [&]() -> unsigned long long {
+    unsigned long long k = 0;
+    for (int d = 0; d < n; ++d) {
+      if (sh.dused[d] || !(sh.dlabel[d] == t.label)) continue;
+      const float ww = __fsub_rn(fminf(t.x2, sh.dx2[d]), fmaxf(t.x1, sh.dx1[d]));
+      const float hh = __fsub_rn(fminf(t.y2, sh.dy2[d]), fmaxf(t.y1, sh.dy1[d]));
+      float iou = 0.f;
+      if (!(ww <= 0.f) && !(hh <= 0.f)) {
+        const float inter = __fmul_rn(ww, hh);
+        const float u = __fsub_rn(__fadd_rn(area, sh.darea[d]), inter);
+        iou = u > 0.f ? __fdiv_rn(inter, u) : 0.f;
+      }
+      if (!(iou >= p.iou_min)) continue;                // false for NaN; iou >= +0, and a non-negative float's bits order like the float
+      const unsigned long long key = ((unsigned long long)__float_as_uint(iou) << 32) |
+                                     ((unsigned long long)(0xFFFFu - (unsigned)tid) << 16) | (unsigned long long)(0xFFFFu - (unsigned)d);
+      k = key > k ? key : k;
+    }
+    return k;
+  };
+  bool matched = false;
+  unsigned long long key = (t.live && n > 0) ? best() : 0ull;
+
+  // 3. greedy match: the block-wide largest key, until none is left (at most min(live slots, n) rounds)
+  for (;;) {
+    const unsigned long long wm = trk_wave_max(key);
+    if ((tid & 63) == 0) sh.wmax[tid >> 6] = wm;
+    __syncthreads();
+    unsigned long long m = sh.wmax[0];
+    m = sh.wmax[1] > m ? sh.wmax[1] : m;
+    m = sh.wmax[2] > m ? sh.wmax[2] : m;
+    m = sh.wmax[3] > m ? sh.wmax[3] : m;
+    if (m == 0) break;                                  // uniform: every thread read the same four words
+    const int ms = 0xFFFF - (int)((m >> 16) & 0xFFFFu), md = 0xFFFF - (int)(m & 0xFFFFu);
+    if (tid == ms) {
+      // 4. matched slot: the velocity takes beta of the residual of the centre, the box and the score become the detection's
+      const float dx1 = sh.dx1[md], dy1 = sh.dy1[md], dx2 = sh.dx2[md], dy2 = sh.dy2[md];
+      const float rx = __fsub_rn(__fmul_rn(__fadd_rn(dx1, dx2), 0.5f), __fmul_rn(__fadd_rn(t.x1, t.x2), 0.5f));
+      const float ry = __fsub_rn(__fmul_rn(__fadd_rn(dy1, dy2), 0.5f), __fmul_rn(__fadd_rn(t.y1, t.y2), 0.5f));
+      t.vx = __fadd_rn(t.vx, __fmul_rn(p.beta, rx));
+      t.vy = __fadd_rn(t.vy, __fmul_rn(p.beta, ry));
+      t.x1 = dx1; t.y1 = dy1; t.x2 = dx2; t.y2 = dy2; t.score = sh.dscore[md];
+      t.hits += 1; t.misses = 0; t.last = widx;
+      matched = true;
+      key = 0;
+      sh.dtrack[md] = t.id;
+      sh.dused[md] = 1;
+    }
+    __syncthreads();                                    // sh.dused[md] is visible, and every thread is done with sh.wmax
+    if (key != 0 && 0xFFFF - (int)(key & 0xFFFFu) == md) key = best();
+  }
+
+  // 5. unmatched live slots age; freeing comes before the births
+  if (t.live && !matched) {
+    t.misses += 1;
+    if (t.misses > p.max_age) {
+      t.live = 0; t.id = 0; t.hits = 0; t.misses = 0; t.last = 0;
+      t.x1 = t.y1 = t.x2 = t.y2 = t.vx = t.vy = t.label = t.score = 0.f;
+    }
+  }
+  sh.live[tid] = mine ? t.live : 1;                      // slots behind max_tracks are never free
+  __syncthreads();
+  // 6. births, in detection order, each into the lowest free slot (the free slots are taken in rising order: one pointer)
+  if (tid == 0) {
+    int f = 0, next = sh.next, over = sh.over;
+    for (int d = 0; d < n; ++d) {
+      if (sh.dused[d] || !(sh.dscore[d] >= p.birth_score)) continue;
+      while (f < p.max_tracks && sh.live[f]) ++f;
+      if (f < p.max_tracks) {
+        sh.birth[f] = d + 1;
+        sh.dtrack[d] = next++;
+        ++f;
+      } else {
+        over = 1;
+      }
+    }
+    sh.next = next; sh.over = over;
+  }
+  __syncthreads();
+  if (mine && sh.birth[tid]) {
+    const int d = sh.birth[tid] - 1;
+    t.live = 1; t.id = sh.dtrack[d];
+    t.x1 = sh.dx1[d]; t.y1 = sh.dy1[d]; t.x2 = sh.dx2[d]; t.y2 = sh.dy2[d];
+    t.vx = 0.f; t.vy = 0.f; t.label = sh.dlabel[d]; t.score = sh.dscore[d];
+    t.hits = 1; t.misses = 0; t.last = widx;
+  }
+  // 7. the rows' ids: -1 for every row that was neither matched nor born, and for the rows behind TRK_DMAX
+  for (int j = tid; j < n_all; j += 256)
+    if (o + j < rec_cap) rec_track[o + j] = j < n ? sh.dtrack[j] : -1;
+  __syncthreads();                                      // the next window overwrites the detections
+}
+
 __global__ __launch_bounds__(256) void track_update_kernel(const float* __restrict__ rows, const int* __restrict__ cnt, int B, int cap_img,
                                                            const int* __restrict__ ctl, const int* __restrict__ rec_count, int rec_cap,
                                                            int* __restrict__ rec_track, int* __restrict__ slots, int* __restrict__ glob,
                                                            TrackParams p) {
   __shared__ long long s_off[TRK_BMAX + 1];     // as det_record_append_kernel: record row of window i's first row
   __shared__ int s_nv;
-  __shared__ float s_dx1[TRK_DMAX], s_dy1[TRK_DMAX], s_dx2[TRK_DMAX], s_dy2[TRK_DMAX], s_darea[TRK_DMAX], s_dscore[TRK_DMAX],
-      s_dlabel[TRK_DMAX];
-  __shared__ int s_dtrack[TRK_DMAX];            // the id detection d's row gets (-1: none)
-  __shared__ int s_dused[TRK_DMAX];             // detection d is matched
-  __shared__ int s_live[TRK_SMAX];              // slot t is live (for the births)
-  __shared__ int s_birth[TRK_SMAX];             // 1 + the detection that is born into slot t (0: none)
-  __shared__ unsigned long long s_wmax[4];
-  __shared__ int s_next, s_over;
+  __shared__ TrackShared sh;
   const int tid = threadIdx.x;
   if (tid == 0) {
     const int nv = max(0, min(ctl[0], B));
@@ -55,151 +210,71 @@ __global__ __launch_bounds__(256) void track_update_kernel(const float* __restri
     }
     s_off[nv] = o;
     s_nv = nv;
-    s_next = glob[0];
-    s_over = 0;
+    sh.next = glob[0];
+    sh.over = 0;
   }
-  // slot tid in registers
   const bool mine = tid < p.max_tracks;
-  int live = 0, id = 0, hits = 0, misses = 0, last = 0;
-  float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f, vx = 0.f, vy = 0.f, label = 0.f, score = 0.f;
-  if (mine) {
-    const int* s = slots + tid * TRK_WORDS;
-    live = s[0] != 0;
-    if (live) {
-      id = s[1];
-      x1 = __int_as_float(s[2]); y1 = __int_as_float(s[3]); x2 = __int_as_float(s[4]); y2 = __int_as_float(s[5]);
-      vx = __int_as_float(s[6]); vy = __int_as_float(s[7]); label = __int_as_float(s[8]); score = __int_as_float(s[9]);
-      hits = s[10]; misses = s[11]; last = s[12];
-    }
-  }
+  TrackSlot t;
+  trk_slot_load(t, slots, tid, mine);
   __syncthreads();
   const int nv = s_nv, first = ctl[1];
-
-  for (int i = 0; i < nv; ++i) {
-    const long long o = s_off[i];
-    const int n_all = (int)(s_off[i + 1] - o);          // 0 .. cap_img
-    const int n = min(n_all, TRK_DMAX);
-    const float* src = rows + (size_t)i * cap_img * 6;
-    if (tid < n) {
-      const float* r = src + tid * 6;
-      const float a = r[0], b = r[1], c = r[2], d = r[3];
-      s_dx1[tid] = a; s_dy1[tid] = b; s_dx2[tid] = c; s_dy2[tid] = d;
-      s_darea[tid] = __fmul_rn(__fsub_rn(c, a), __fsub_rn(d, b));
-      s_dscore[tid] = r[4]; s_dlabel[tid] = r[5];
-      s_dtrack[tid] = -1; s_dused[tid] = 0;
-    }
-    s_birth[tid] = 0;
-    if (tid == 0 && n_all > TRK_DMAX) s_over = 1;
-    // 1. predict
-    float area = 0.f;
-    if (live) {
-      x1 = __fadd_rn(x1, vx); x2 = __fadd_rn(x2, vx); y1 = __fadd_rn(y1, vy); y2 = __fadd_rn(y2, vy);
-      area = __fmul_rn(__fsub_rn(x2, x1), __fsub_rn(y2, y1));
-    }
-    __syncthreads();
-
-    // 2. this slot's best candidate among the unmatched detections: 0 = none
-    auto best = [&]() -> unsigned long long {
-      unsigned long long k = 0;
-      for (int d = 0; d < n; ++d) {
-        if (s_dused[d] || !(s_dlabel[d] == label)) continue;
-        const float ww = __fsub_rn(fminf(x2, s_dx2[d]), fmaxf(x1, s_dx1[d]));
-        const float hh = __fsub_rn(fminf(y2, s_dy2[d]), fmaxf(y1, s_dy1[d]));
-        float iou = 0.f;
-        if (!(ww <= 0.f) && !(hh <= 0.f)) {
-          const float inter = __fmul_rn(ww, hh);
-          const float u = __fsub_rn(__fadd_rn(area, s_darea[d]), inter);
-          iou = u > 0.f ? __fdiv_rn(inter, u) : 0.f;
-        }
-        if (!(iou >= p.iou_min)) continue;                // false for NaN; iou >= +0, and a non-negative float's bits order like the float
-        const unsigned long long key = ((unsigned long long)__float_as_uint(iou) << 32) |
-                                       ((unsigned long long)(0xFFFFu - (unsigned)tid) << 16) | (unsigned long long)(0xFFFFu - (unsigned)d);
-        k = key > k ? key : k;
-      }
-      return k;
-    };
-    bool matched = false;
-    unsigned long long key = (live && n > 0) ? best() : 0ull;
-
-    // 3. greedy match: the block-wide largest key, until none is left (at most min(live slots, n) rounds)
-    for (;;) {
-      const unsigned long long wm = trk_wave_max(key);
-      if ((tid & 63) == 0) s_wmax[tid >> 6] = wm;
-      __syncthreads();
-      unsigned long long m = s_wmax[0];
-      m = s_wmax[1] > m ? s_wmax[1] : m;
-      m = s_wmax[2] > m ? s_wmax[2] : m;
-      m = s_wmax[3] > m ? s_wmax[3] : m;
-      if (m == 0) break;                                  // uniform: every thread read the same four words
-      const int ms = 0xFFFF - (int)((m >> 16) & 0xFFFFu), md = 0xFFFF - (int)(m & 0xFFFFu);
-      if (tid == ms) {
-        // 4. matched slot: the velocity takes beta of the residual of the centre, the box and the score become the detection's
-        const float dx1 = s_dx1[md], dy1 = s_dy1[md], dx2 = s_dx2[md], dy2 = s_dy2[md];
-        const float rx = __fsub_rn(__fmul_rn(__fadd_rn(dx1, dx2), 0.5f), __fmul_rn(__fadd_rn(x1, x2), 0.5f));
-        const float ry = __fsub_rn(__fmul_rn(__fadd_rn(dy1, dy2), 0.5f), __fmul_rn(__fadd_rn(y1, y2), 0.5f));
-        vx = __fadd_rn(vx, __fmul_rn(p.beta, rx));
-        vy = __fadd_rn(vy, __fmul_rn(p.beta, ry));
-        x1 = dx1; y1 = dy1; x2 = dx2; y2 = dy2; score = s_dscore[md];
-        hits += 1; misses = 0; last = first + i;
-        matched = true;
-        key = 0;
-        s_dtrack[md] = id;
-        s_dused[md] = 1;
-      }
-      __syncthreads();                                    // s_dused[md] is visible, and every thread is done with s_wmax
-      if (key != 0 && 0xFFFF - (int)(key & 0xFFFFu) == md) key = best();
-    }
-
-    // 5. unmatched live slots age; freeing comes before the births
-    if (live && !matched) {
-      misses += 1;
-      if (misses > p.max_age) {
-        live = 0; id = 0; hits = 0; misses = 0; last = 0;
-        x1 = y1 = x2 = y2 = vx = vy = label = score = 0.f;
-      }
-    }
-    s_live[tid] = mine ? live : 1;                        // slots behind max_tracks are never free
-    __syncthreads();
-    // 6. births, in detection order, each into the lowest free slot (the free slots are taken in rising order: one pointer)
-    if (tid == 0) {
-      int t = 0, next = s_next, over = s_over;
-      for (int d = 0; d < n; ++d) {
-        if (s_dused[d] || !(s_dscore[d] >= p.birth_score)) continue;
-        while (t < p.max_tracks && s_live[t]) ++t;
-        if (t < p.max_tracks) {
-          s_birth[t] = d + 1;
-          s_dtrack[d] = next++;
-          ++t;
-        } else {
-          over = 1;
-        }
-      }
-      s_next = next; s_over = over;
-    }
-    __syncthreads();
-    if (mine && s_birth[tid]) {
-      const int d = s_birth[tid] - 1;
-      live = 1; id = s_dtrack[d];
-      x1 = s_dx1[d]; y1 = s_dy1[d]; x2 = s_dx2[d]; y2 = s_dy2[d];
-      vx = 0.f; vy = 0.f; label = s_dlabel[d]; score = s_dscore[d];
-      hits = 1; misses = 0; last = first + i;
-    }
-    // 7. the rows' ids: -1 for every row that was neither matched nor born, and for the rows behind TRK_DMAX
-    for (int j = tid; j < n_all; j += 256)
-      if (o + j < rec_cap) rec_track[o + j] = j < n ? s_dtrack[j] : -1;
-    __syncthreads();                                      // the next window overwrites the detections
-  }
-
-  if (mine) {
-    int* s = slots + tid * TRK_WORDS;
-    s[0] = live; s[1] = id;
-    s[2] = __float_as_int(x1); s[3] = __float_as_int(y1); s[4] = __float_as_int(x2); s[5] = __float_as_int(y2);
-    s[6] = __float_as_int(vx); s[7] = __float_as_int(vy); s[8] = __float_as_int(label); s[9] = __float_as_int(score);
-    s[10] = hits; s[11] = misses; s[12] = last;
-  }
+  for (int i = 0; i < nv; ++i)
+    trk_window(sh, t, rows + (size_t)i * cap_img * 6, (int)(s_off[i + 1] - s_off[i]), s_off[i], first + i, rec_cap, rec_track, mine, p);
+  trk_slot_store(t, slots, tid, mine);
   if (tid == 0) {
-    glob[0] = s_next;
-    if (s_over) glob[1] = 1;
+    glob[0] = sh.next;
+    if (sh.over) glob[1] = 1;
+  }
+}
+
+// The tracker of a bank of sessions (AudioDetector.open_bank): block s owns slots[s] / glob[s] and runs, in row order, the rows i <
+// n_valid of the group with win_sess[i] == s through trk_window, with the row's own window index win_idx[i].  Every block does the
+// whole scan of the offsets itself (it is the append's); the blocks write disjoint rows of rec_track.  A block whose session has no
+// row in the group returns before it touches its state.
+__global__ __launch_bounds__(256) void track_update_bank_kernel(const float* __restrict__ rows, const int* __restrict__ cnt, int B,
+                                                                int cap_img, const int* __restrict__ n_valid,
+                                                                const int* __restrict__ win_sess, const int* __restrict__ win_idx,
+                                                                const int* __restrict__ rec_count, int rec_cap,
+                                                                int* __restrict__ rec_track, int* __restrict__ slots,
+                                                                int* __restrict__ glob, TrackParams p) {
+  __shared__ long long s_off[TRK_BMAX + 1];
+  __shared__ int s_mine[TRK_BMAX];              // row i is this block's session's
+  __shared__ int s_nv, s_any;
+  __shared__ TrackShared sh;
+  const int tid = threadIdx.x, sess = blockIdx.x;
+  slots += (size_t)sess * p.max_tracks * TRK_WORDS;
+  glob += (size_t)sess * 2;
+  if (tid == 0) {
+    const int nv = max(0, min(*n_valid, B));
+    long long o = max(*rec_count, 0);
+    int any = 0;
+    for (int i = 0; i < nv; ++i) {
+      s_off[i] = o;
+      o += max(0, min(cnt[i], cap_img));
+      const int m = win_sess[i] == sess;
+      s_mine[i] = m;
+      any |= m;
+    }
+    s_off[nv] = o;
+    s_nv = nv;
+    s_any = any;
+    sh.next = glob[0];
+    sh.over = 0;
+  }
+  __syncthreads();
+  if (!s_any) return;                                     // uniform: an absent session's state is not touched, nothing ages
+  const bool mine = tid < p.max_tracks;
+  TrackSlot t;
+  trk_slot_load(t, slots, tid, mine);
+  const int nv = s_nv;
+  for (int i = 0; i < nv; ++i) {
+    if (!s_mine[i]) continue;                             // uniform
+    trk_window(sh, t, rows + (size_t)i * cap_img * 6, (int)(s_off[i + 1] - s_off[i]), s_off[i], win_idx[i], rec_cap, rec_track, mine, p);
+  }
+  trk_slot_store(t, slots, tid, mine);
+  if (tid == 0) {
+    glob[0] = sh.next;
+    if (sh.over) glob[1] = 1;
   }
 }
 
@@ -213,5 +288,19 @@ extern "C" int mmd_track_update(const float* rows, const int* cnt, int B, int ca
   p.max_tracks = max_tracks; p.max_age = max_age; p.iou_min = iou_min; p.beta = beta; p.birth_score = birth_score;
   hipLaunchKernelGGL(track_update_kernel, dim3(1), dim3(256), 0, stream, rows, cnt, B, cap_img, ctl, rec_count, rec_cap, rec_track,
                      trk_slots, trk_glob, p);
+  return mmd_check_launch();
+}
+
+extern "C" int mmd_track_update_bank(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess,
+                                     const int* win_idx, int n_sessions, const int* rec_count, int rec_cap, int* rec_track,
+                                     int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age,
+                                     float birth_score, hipStream_t stream) {
+  if (!rows || !cnt || !n_valid || !win_sess || !win_idx || !rec_count || !rec_track || !trk_slots || !trk_glob) return MMD_EINVAL;
+  if (B <= 0 || B > TRK_BMAX || cap_img <= 0 || rec_cap <= 0 || (long long)cap_img * 6 > 0x7fffffffLL) return MMD_EINVAL;
+  if (n_sessions < 1 || n_sessions > 65535 || max_tracks < 1 || max_tracks > TRK_SMAX || max_age < 0) return MMD_EINVAL;
+  TrackParams p;
+  p.max_tracks = max_tracks; p.max_age = max_age; p.iou_min = iou_min; p.beta = beta; p.birth_score = birth_score;
+  hipLaunchKernelGGL(track_update_bank_kernel, dim3(n_sessions), dim3(256), 0, stream, rows, cnt, B, cap_img, n_valid, win_sess, win_idx,
+                     rec_count, rec_cap, rec_track, trk_slots, trk_glob, p);
   return mmd_check_launch();
 }

@@ -18,7 +18,11 @@ front of every group's append: each row of the record also gets the id of its tr
 (csrc/live.hip: `mmd_ring_push`, `mmd_ring_push_pcm`), the front end reads the windows out of it across the wrap
 (`mmd_melspec_windows_ring`), and one captured graph serves the whole session and every recording pushed through it.  A source at
 another rate than 44.1 kHz (`open_stream(sample_rate=R)`) goes through a second ring of input-rate samples, from which
-`mmd_ring_resample` computes the 44.1 kHz samples the schedule asks for with the bits `Resampler.resample` gives the whole recording."""
+`mmd_ring_resample` computes the 44.1 kHz samples the schedule asks for with the bits `Resampler.resample` gives the whole recording.
+
+`open_bank` is that chain for SEVERAL sources at once: a `LiveBank` keeps one ring and one tracker per session behind one captured
+graph, and each row of a group names the session and the window it is (`mmd_melspec_windows_rings`, `mmd_track_update_bank`,
+`mmd_det_record_append_bank`), so one forward pass serves one fresh window of every source."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -29,8 +33,8 @@ import torch
 
 from .arch import NetSpec
 from . import _lib
-from .audio import (MelFrontEnd, Resampler, live_group_span, live_in_ring_min, live_resample_ready, live_schedule, resample_ratio,
-                    stream_window_starts)
+from .audio import (MelFrontEnd, Resampler, bank_reset, bank_schedule, bank_state, bank_step, live_group_span, live_in_ring_min,
+                    live_resample_ready, live_schedule, resample_ratio, stream_window_starts)
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -65,6 +69,9 @@ class AudioDetector:
         self._live: Optional["LiveSession"] = None     # open_stream's session; a stream and a session never coexist
         self.live_captures = 0                    # graphs open_stream's sessions captured
         self.live_replays = 0                     # groups of windows a session served by a captured graph
+        self._bank: Optional["LiveBank"] = None        # open_bank's bank; a stream, a session and a bank never coexist
+        self.bank_captures = 0                    # graphs open_bank's banks captured
+        self.bank_replays = 0                     # ticks a bank served by a captured graph
         self.resampler: Optional[Resampler] = None     # the filter banks of sessions at other rates than 44.1 kHz (made with the first)
         self.last_cls: Optional[torch.Tensor] = None   # head outputs of the last call (views of the net's arena: valid until the next call)
         self.last_reg: Optional[torch.Tensor] = None
@@ -228,8 +235,7 @@ class AudioDetector:
             raise ValueError("%s: batch = %d (1 .. 1024)" % (who, batch))
         starts = stream_window_starts(n_total, win_len, hop)
         W = len(starts)
-        if self._live is not None:
-            self._live.close()                    # one stream or session at a time
+        self._close_live()                        # one stream, session or bank at a time
         if rec_cap is None:
             rec_cap = W * (self.cand_cap if self.cand_cap > 0 else self.STREAM_ROWS_PER_WINDOW)
         rec_cap = int(rec_cap)
@@ -280,11 +286,32 @@ class AudioDetector:
         default taps + M + ceil(ring_len * M / L) - a push of up to a ring's worth of audio is then one piece."""
         if track is not None and not isinstance(track, TrackConfig):
             raise ValueError("open_stream: track must be a TrackConfig or None")
-        if self._live is not None:
-            self._live.close()
+        self._close_live()
         self._stream = None
         self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len, sample_rate, in_ring_len)
         return self._live
+
+    def _close_live(self):
+        """closes the open session or bank, if any"""
+        for held in (self._live, self._bank):
+            if held is not None:
+                held.close()
+
+    @torch.no_grad()
+    def open_bank(self, n_sessions: int, win_len: int, hop: int, batch: Optional[int] = None, track: Optional[TrackConfig] = None,
+                  ring_len: Optional[int] = None) -> "LiveBank":
+        """Opens a bank of n_sessions live sessions behind one captured chain - see `LiveBank`: several microphone arrays (or files
+        replayed side by side) push independently, and one forward pass serves `batch` ready windows of whichever sessions completed
+        them.  win_len, hop, track as `open_stream`; batch: windows per tick, default n_sessions (one fresh window of each);
+        ring_len: samples per channel EACH session keeps on the device, at least (batch - 1) * hop + win_len (ValueError below
+        that), default twice that.  The input is at 44.1 kHz: per-session resampling is not built (there is no sample_rate).  The
+        detector holds one stream, session or bank at a time: opening any of them closes the others."""
+        if track is not None and not isinstance(track, TrackConfig):
+            raise ValueError("open_bank: track must be a TrackConfig or None")
+        self._close_live()
+        self._stream = None
+        self._bank = LiveBank(self, int(n_sessions), int(win_len), int(hop), int(n_sessions if batch is None else batch), track, ring_len)
+        return self._bank
 
 
 class _GroupChain:
@@ -294,38 +321,60 @@ class _GroupChain:
 
     The control row `cur` is int64 starts[batch], then {n_valid, first_window} as two int32 in the last word (`control_table`).  The
     record is ONE block of int32 words, rows [rec_cap, 6] (float bits) | window [rec_cap] | track [rec_cap] | {count, overflow}, so a
-    client may copy it in one piece."""
+    client may copy it in one piece.
+
+    Third mode, for a `LiveBank` (source: its rings [n_sessions, 8, ring_len]): the rows of a group are windows of several sessions.
+    The control row is int64 starts[batch] | int32 sess[batch] | int32 win[batch] | int32 {n_valid, pad} (`bank_control_table`), the
+    tracker keeps one state per session, and the record grows by one column: rows | window | track | session | {count, overflow}."""
 
     def __init__(self, det: AudioDetector, kind: str, source: torch.Tensor, ring: bool, win_len: int, batch: int, rec_cap: int,
                  track: Optional[TrackConfig], key=None):
         dev, C = det.device, det.net.spec.in_channels
         self.det, self.kind, self.source, self.ring, self.win_len, self.rec_cap, self.track, self.key = \
-            det, kind, source, ring, win_len, rec_cap, track, key       # kind: "stream" / "live", the detector's counters to bump
-        self.cur = torch.zeros(batch + 1, dtype=torch.int64, device=dev)
-        self.starts, self.ctl = self.cur[:batch], self.cur[batch:].view(torch.int32)
+            det, kind, source, ring, win_len, rec_cap, track, key       # kind: "stream" / "live" / "bank", the detector's counters to bump
+        self.bank = kind == "bank"
+        self.cols = 9 if self.bank else 8         # int32 words per record row
+        self.cur = torch.zeros(2 * batch + 1 if self.bank else batch + 1, dtype=torch.int64, device=dev)
+        self.starts, self.ctl = self.cur[:batch], self.cur[-1:].view(torch.int32)
+        if self.bank:
+            tables = self.cur[batch:2 * batch].view(torch.int32)
+            self.sess, self.win = tables[:batch], tables[batch:]
         self.mel = torch.empty(batch, det.front.n_mels, det.front.n_frames(win_len), C, device=dev)
         self.max_ws = torch.empty(batch * C, device=dev)
         self.audio = torch.empty(batch, C, det.S, det.S, device=dev)
-        self.blob = blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, device=dev)
+        self.blob = blob = torch.zeros(self.cols * rec_cap + 2, dtype=torch.int32, device=dev)
         self.rec_rows = blob[:6 * rec_cap].view(torch.float32).view(rec_cap, 6)
-        self.rec_win, self.rec_track, self.rec_state = blob[6 * rec_cap:7 * rec_cap], blob[7 * rec_cap:8 * rec_cap], blob[8 * rec_cap:]
+        self.rec_win, self.rec_track, self.rec_state = blob[6 * rec_cap:7 * rec_cap], blob[7 * rec_cap:8 * rec_cap], blob[self.cols * rec_cap:]
         self.trk_state = None if track is None else _tracker.new_state(dev, track)
+        if self.bank:
+            self.rec_sess = blob[8 * rec_cap:9 * rec_cap]
+            self.trk_state = None if track is None else _tracker.new_bank_state(dev, track, source.shape[0])
         self.graph = None
 
     def issue(self):
         """One group on the current stream.  The track update reads the record's count before the append advances it."""
         det, front = self.det, self.det.front
-        windows_into = front.melspec_windows_ring_into if self.ring else front.melspec_windows_into
-        windows_into(self.source, self.starts, self.win_len, True, self.max_ws, self.mel)
+        if self.bank:
+            front.melspec_windows_rings_into(self.source, self.sess, self.starts, self.win_len, True, self.max_ws, self.mel)
+        else:
+            windows_into = front.melspec_windows_ring_into if self.ring else front.melspec_windows_into
+            windows_into(self.source, self.starts, self.win_len, True, self.max_ws, self.mel)
         audio = front.resize_into(self.mel, det.S, self.audio)
         det._tail(audio, self)
+        if self.bank:
+            if self.track is not None:
+                _tracker.update_bank(self.rows, self.cnt, self.ctl, self.sess, self.win, self.rec_state[0:1], self.rec_cap, self.rec_track,
+                                     self.trk_state, self.track)
+            _lib.call("mmd_det_record_append_bank", self.rows, self.cnt, audio.shape[0], self.rows.shape[1], self.ctl, self.sess, self.win,
+                      self.rec_rows, self.rec_win, self.rec_sess, self.rec_cap, self.rec_state[0:1], self.rec_state[1:2])
+            return
         if self.track is not None:
             _tracker.update(self.rows, self.cnt, self.ctl, self.rec_state[0:1], self.rec_cap, self.rec_track, self.trk_state, self.track)
         _lib.call("mmd_det_record_append", self.rows, self.cnt, audio.shape[0], self.rows.shape[1], self.ctl, self.rec_rows, self.rec_win,
                   self.rec_cap, self.rec_state[0:1], self.rec_state[1:2])
 
     def _count(self, what: str):
-        """the detector's stream_captures / stream_replays / live_captures / live_replays"""
+        """the detector's stream_ / live_ / bank_ captures and replays"""
         setattr(self.det, self.kind + what, getattr(self.det, self.kind + what) + 1)
 
     def _capture(self):
@@ -365,19 +414,21 @@ class _GroupChain:
 
     def read(self, fetch, det_overflow: int, trk_overflow: int):
         """fetch(lo, hi) -> a host copy (numpy int32 the caller does not reuse) of the record's words [lo, hi), made after the
-        device finished; the two flags are the detector's and the tracker's overflow -> (rows [n, 6], window [n][, track [n]])"""
+        device finished; the two flags are the detector's and the tracker's overflow -> (rows [n, 6], window [n][, track [n]]); a
+        bank's chain: (rows [n, 6], session [n], window [n][, track [n]])"""
         R = self.rec_cap
-        n, over = fetch(8 * R, 8 * R + 2).tolist()
+        n, over = fetch(self.cols * R, self.cols * R + 2).tolist()
         if det_overflow:
             raise RuntimeError(self.det._overflow_message())
         if over or n > R:
             raise RuntimeError("detection record exceeded: %d rows needed, rec_cap = %d" % (n, R))
         rows, window = fetch(0, 6 * n).view(np.float32).reshape(n, 6), fetch(6 * R, 6 * R + n)
+        head = (rows, fetch(8 * R, 8 * R + n), window) if self.bank else (rows, window)
         if self.track is None:
-            return rows, window
+            return head
         if trk_overflow:
             raise RuntimeError(_tracker.overflow_message(self.track, window))
-        return rows, window, fetch(7 * R, 7 * R + n)
+        return head + (fetch(7 * R, 7 * R + n),)
 
     @staticmethod
     def control_table(groups: list, batch: int, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -391,8 +442,81 @@ class _GroupChain:
             tail[k] = (len(real), first)
         return table
 
+    @staticmethod
+    def bank_control_table(ticks: list, batch: int, hop: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """ticks: [(session, window), ...] (1 .. batch entries) per tick -> int64 [len(ticks), 2 * batch + 1], one control row per tick of a
+        bank's chain: int64 starts[batch] (window * hop) | int32 sess[batch] | int32 win[batch] | int32 {n_valid, 0}, the last real window
+        repeated up to batch.  out: an int64 [>= len(ticks), 2 * batch + 1] table to write the rows into; its first len(ticks) rows are
+        returned."""
+        batch, hop = int(batch), int(hop)
+        table = np.empty((len(ticks), 2 * batch + 1), np.int64) if out is None else out[:len(ticks)]
+        i32 = table.view(np.int32).reshape(len(ticks), 2 * (2 * batch + 1))
+        for k, real in enumerate(ticks):
+            if not 1 <= len(real) <= batch:
+                raise ValueError(f"a tick of {len(real)} windows at batch = {batch}")
+            full = list(real) + [real[-1]] * (batch - len(real))
+            table[k, :batch] = [w * hop for _, w in full]
+            i32[k, 2 * batch:3 * batch] = [q for q, _ in full]
+            i32[k, 3 * batch:4 * batch] = [w for _, w in full]
+            i32[k, 4 * batch:] = (len(real), 0)
+        return table
 
-class LiveSession:
+
+class _ChunkInput:
+    """What `LiveSession` and `LiveBank` share: the forms a chunk may arrive in, and the two pinned staging buffers host chunks go
+    through in turn (before a buffer is written again, the wait for the event behind the copy that last read it - two pushes back)."""
+
+    def _init_staging(self, det: AudioDetector, C: int):
+        self.det, self.C = det, C
+        self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
+        self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
+        self._pushes = 0
+
+    def _to_device(self, host: torch.Tensor) -> torch.Tensor:
+        """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
+        k = self._pushes & 1
+        self._pushes += 1
+        nbytes = host.numel() * host.element_size()
+        self._stage_ev[k].synchronize()           # the copy that last read this buffer (two pushes back) is done
+        if self._stage[k] is None or self._stage[k].numel() < nbytes:
+            self._stage[k] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+        pinned = self._stage[k][:nbytes].view(host.dtype).view(host.shape)
+        pinned.copy_(host)
+        dev = pinned.to(self.det.device, non_blocking=True)
+        self._stage_ev[k].record()
+        return dev
+
+    def _float_chunk(self, chunk) -> torch.Tensor:
+        """push's argument -> float32 [C, n] on the device, rows at least n apart, unit stride along the samples"""
+        if isinstance(chunk, np.ndarray):
+            if chunk.dtype != np.float32:
+                raise ValueError("push takes float32 [%d, n] samples, found %s" % (self.C, chunk.dtype))
+            chunk = torch.from_numpy(chunk if chunk.flags.writeable else chunk.copy())
+        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.dtype != torch.float32 or chunk.shape[0] != self.C or \
+                chunk.shape[1] < 1:
+            raise ValueError("push takes float32 [%d, n] samples, n >= 1" % self.C)
+        if not chunk.is_cuda:
+            chunk = self._to_device(chunk)
+        elif chunk.stride(1) != 1 or chunk.stride(0) < chunk.shape[1]:
+            chunk = chunk.contiguous()
+        return chunk
+
+    def _pcm_chunk(self, raw, width: int):
+        """push_pcm's arguments -> (uint8 frames on the device, bytes per frame)"""
+        width = int(width)
+        if width not in (2, 3, 4):
+            raise ValueError("push_pcm: width = %d (2, 3 or 4 bytes per sample)" % width)
+        if isinstance(raw, (bytes, bytearray, memoryview)):
+            raw = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy())
+        if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() != 1:
+            raise ValueError("push_pcm takes bytes, a bytearray or a one-dimensional uint8 tensor")
+        fb = self.C * width
+        if raw.numel() < fb or raw.numel() % fb:
+            raise ValueError("push_pcm: %d bytes are not whole frames of %d x %d bytes" % (raw.numel(), self.C, width))
+        return (raw.contiguous() if raw.is_cuda else self._to_device(raw)), fb
+
+
+class LiveSession(_ChunkInput):
     """A recording that arrives in chunks (`AudioDetector.open_stream`).  `push` / `push_pcm` write a chunk into a ring of samples on the
     device and return the results of the windows the chunk COMPLETED - (rows float32 [R, 6], window int32 [R]), with tracking also
     track int32 [R], in the dtypes and order of `detect_stream` / `track_stream`; window indices count from the start of the recording
@@ -474,9 +598,7 @@ class LiveSession:
         self._h_flags = torch.zeros(3, dtype=torch.int32, pin_memory=True)       # detector overflow; tracker {next_id, overflow}
         self.chain = _GroupChain(det, "live", torch.zeros(C, cap, device=dev), True, win_len, batch, rec_cap, track)
         self._h_ctl = torch.zeros(1, batch + 1, dtype=torch.int64, pin_memory=True)
-        self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
-        self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
-        self._pushes = 0
+        self._init_staging(det, C)
         self.chain.prepare()                      # the warm-up group reads the zeroed ring
 
     # ---- state
@@ -575,35 +697,11 @@ class LiveSession:
         return self.concat(parts)
 
     # ---- chunks
-    def _to_device(self, host: torch.Tensor) -> torch.Tensor:
-        """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
-        k = self._pushes & 1
-        self._pushes += 1
-        nbytes = host.numel() * host.element_size()
-        self._stage_ev[k].synchronize()           # the copy that last read this buffer (two pushes back) is done
-        if self._stage[k] is None or self._stage[k].numel() < nbytes:
-            self._stage[k] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        pinned = self._stage[k][:nbytes].view(host.dtype).view(host.shape)
-        pinned.copy_(host)
-        dev = pinned.to(self.det.device, non_blocking=True)
-        self._stage_ev[k].record()
-        return dev
-
     def push(self, chunk):
         """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of every microphone (at the
         session's sample_rate)"""
         self._check_open(pushing=True)
-        if isinstance(chunk, np.ndarray):
-            if chunk.dtype != np.float32:
-                raise ValueError("push takes float32 [%d, n] samples, found %s" % (self.C, chunk.dtype))
-            chunk = torch.from_numpy(chunk if chunk.flags.writeable else chunk.copy())
-        if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.dtype != torch.float32 or chunk.shape[0] != self.C or \
-                chunk.shape[1] < 1:
-            raise ValueError("push takes float32 [%d, n] samples, n >= 1" % self.C)
-        if not chunk.is_cuda:
-            chunk = self._to_device(chunk)
-        elif chunk.stride(1) != 1 or chunk.stride(0) < chunk.shape[1]:
-            chunk = chunk.contiguous()
+        chunk = self._float_chunk(chunk)
         ptr, stride = chunk.data_ptr(), chunk.stride(0)
         return self._feed(chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt,
                                                                                      ring, cap, pos))
@@ -613,18 +711,8 @@ class LiveSession:
         of `width` = 2, 3 or 4 bytes, as `wave.readframes` returns them; decoded on the device exactly as `Resampler.pcm_to_float`
         decodes (`mmd_ring_push_pcm`).  Otherwise as `push`."""
         self._check_open(pushing=True)
-        width = int(width)
-        if width not in (2, 3, 4):
-            raise ValueError("push_pcm: width = %d (2, 3 or 4 bytes per sample)" % width)
-        if isinstance(raw, (bytes, bytearray, memoryview)):
-            raw = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy())
-        if not isinstance(raw, torch.Tensor) or raw.dtype != torch.uint8 or raw.dim() != 1:
-            raise ValueError("push_pcm takes bytes, a bytearray or a one-dimensional uint8 tensor")
-        fb = self.C * width
-        if raw.numel() < fb or raw.numel() % fb:
-            raise ValueError("push_pcm: %d bytes are not whole frames of %d x %d bytes" % (raw.numel(), self.C, width))
-        raw = raw.contiguous() if raw.is_cuda else self._to_device(raw)
-        ptr = raw.data_ptr()
+        raw, fb = self._pcm_chunk(raw, width)
+        width, ptr = int(width), raw.data_ptr()
         return self._feed(raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C,
                                                                                         width, ring, cap, pos))
 
@@ -645,3 +733,176 @@ class LiveSession:
             self.chain.run(table[0])
             parts.append(self._drain())
         return self.concat(parts)
+
+
+class LiveBank(_ChunkInput):
+    """Several recordings that arrive in chunks, side by side (`AudioDetector.open_bank`): n_sessions rings [n_sessions, 8, ring_len]
+    and n_sessions trackers behind ONE chain and one captured graph.  `push(s, chunk)` / `push_pcm(s, raw, width)` write a chunk of
+    session s into its ring (the argument forms of `LiveSession`, 44.1 kHz only: per-session resampling is not built) and return the
+    results of the ticks the chunk completed; `step()` runs the pending windows now; `flush()` is `step()` and ends all recordings;
+    `reset(s)` starts a new recording on session s; `close()` releases the bank.
+
+    The schedule (`audio.bank_schedule`).  Window w of session s is ready once its last sample w * hop + win_len - 1 has been pushed;
+    ready windows enter one FIFO in the order they complete; a TICK - one forward pass - runs exactly when the FIFO holds `batch`
+    windows and takes all of them, in FIFO order.  With batch = n_sessions and sources that advance together, a tick is one fresh
+    window of every session: no result waits for later windows of its own recording.  `ticks` lists, per tick run so far, its
+    [(session, window), ...]; only `step` / `flush` run a shorter tick (1 .. batch-1 windows, padded by repeating the last one, the
+    padding not recorded).  A write to session s never passes (first window of s not yet run) * hop + ring_len, so no pending window
+    loses a sample whatever the chunk's length.
+
+    Results: every call returns (rows float32 [R, 6], session int32 [R], window int32 [R][, track int32 [R]]), tick by tick, inside a
+    tick in its window order, inside a window in `detect`'s order - or empty arrays.  Window indices count within the session's
+    recording; track ids count per session from 0.  `concat` joins several results.
+
+    The contract.
+    (a) The rows of tick k are bit for bit what `detect` returns for the stack of that tick's windows (`ticks[k]`, a short tick padded
+        by repetition) at batch size `batch`.
+    (b) With a tracker, the track ids of session s over a whole run equal `tracker.track_rows(rows_s, window_s, n_windows_s, cfg,
+        device)` on that session's own returned rows: every session has its own tracker state (`mmd_track_update_bank`), which sees
+        that session's windows alone, in order.
+    (c) The ticks depend only on the order in which windows complete, never on how a session's audio was cut into pushes.
+    Nothing is promised about a window's bits across different tick compositions.
+
+    One graph of the chain rings front end -> resize -> forward -> decode -> NMS [-> track update] -> record append is captured when
+    the bank opens (`AudioDetector.bank_captures`; with use_graph = False the chain runs eagerly) and serves every tick of every
+    recording (`bank_replays`).  The control row - int64 starts[batch] | int32 sess[batch] | int32 win[batch] | int32 {n_valid, pad} - is
+    one contiguous block, copied per tick out of a pinned table.  The record holds the rows of ONE tick (batch x cand_cap, or batch x
+    STREAM_ROWS_PER_WINDOW with cand_cap = 0); a tick with more raises the RuntimeError of `detect_stream`.
+
+    Synchronisation follows `LiveSession`: a push that completes no tick only queues its ring write; a push that completes ticks
+    drains the record once per tick, behind one copy of the block (rows, windows, track ids, sessions, count) and the overflow
+    flags into pinned host memory; host chunks go through the two pinned staging buffers under the same event rule."""
+
+    def __init__(self, det: AudioDetector, n_sessions: int, win_len: int, hop: int, batch: int, track: Optional[TrackConfig],
+                 ring_len: Optional[int]):
+        C = det.net.spec.in_channels
+        if n_sessions < 1 or n_sessions > 65535:
+            raise ValueError("open_bank: n_sessions = %d (1 .. 65535)" % n_sessions)
+        if hop < 1:
+            raise ValueError("open_bank: hop = %d: the windows must advance by at least one sample" % hop)
+        if batch < 1 or batch > 1024:
+            raise ValueError("open_bank: batch = %d (1 .. 1024)" % batch)
+        det.front.n_frames(win_len)               # raises on a window too short for the reflect padding
+        span = live_group_span(win_len, hop, batch)
+        cap = 2 * span if ring_len is None else int(ring_len)
+        if cap < span:
+            raise ValueError("open_bank: ring_len = %d is shorter than one group of %d windows (%d samples)" % (cap, batch, span))
+        rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
+        if rec_cap > 0x7fffffff // 9:
+            raise ValueError("open_bank: a record of %d rows" % rec_cap)
+        self.track, self.n_sessions, self.win_len, self.hop, self.batch, self.ring_len = track, n_sessions, win_len, hop, batch, cap
+        self.state, self.ticks, self.ended, self.closed = bank_state(n_sessions), [], [False] * n_sessions, False
+        self._init_staging(det, C)
+        self._h_blob = torch.zeros(9 * rec_cap + 2, dtype=torch.int32, pin_memory=True)      # the record's host copy
+        self._h_flags = torch.zeros(1 + 2 * n_sessions, dtype=torch.int32, pin_memory=True)  # detector overflow; per session {next_id, overflow}
+        self._h_ctl = torch.zeros(1, 2 * batch + 1, dtype=torch.int64, pin_memory=True)
+        self.chain = _GroupChain(det, "bank", torch.zeros(n_sessions, C, cap, device=det.device), True, win_len, batch, rec_cap, track)
+        self.chain.prepare()                      # the warm-up tick reads the zeroed rings: session 0, window 0, nothing recorded
+
+    # ---- state
+    def _check_open(self, pushing: bool = False, session: Optional[int] = None):
+        if self.closed:
+            raise RuntimeError("this live bank is closed (the detector holds one stream, session or bank at a time)")
+        if session is not None and not (isinstance(session, (int, np.integer)) and 0 <= session < self.n_sessions):
+            raise ValueError("session %r of a bank of %d" % (session, self.n_sessions))
+        if pushing and self.ended[session]:
+            raise RuntimeError("the recordings were flushed: reset(%d) starts the next one on this session" % session)
+
+    def reset(self, s: int):
+        """Starts a new recording on session s: its position and window count back to 0, its tracker zeroed (ids start at 0 again),
+        its queued windows dropped; the other sessions, the graph, the rings and every buffer stay.  After a `flush` it reopens
+        session s alone for pushes."""
+        self._check_open(session=s)
+        self.state, self.ended[int(s)] = bank_reset(self.state, int(s)), False
+        if self.track is not None:
+            for t in self.chain.trk_state:
+                t[int(s)].zero_()
+
+    def close(self):
+        """Releases the bank's buffers and graph."""
+        if not self.closed:
+            torch.cuda.synchronize()
+            self.closed = True
+            self.chain = self._h_blob = self._stage = None
+            if self.det._bank is self:
+                self.det._bank = None
+
+    # ---- ticks
+    def _drain(self):
+        """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
+        det, chain = self.det, self.chain
+        self._h_blob.copy_(chain.blob, non_blocking=True)
+        self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
+        if self.track is not None:
+            self._h_flags[1:].copy_(chain.trk_state[1].view(-1), non_blocking=True)
+        chain.rec_state.zero_()
+        torch.cuda.synchronize()
+        det.last_cls, det.last_reg = chain.cls, chain.reg
+        h = self._h_blob.numpy()
+        return chain.read(lambda lo, hi: h[lo:hi].copy(), int(self._h_flags[0]), int(self._h_flags[2::2].max()) if self.track is not None else 0)
+
+    def concat(self, parts: list):
+        """what several calls returned -> one result of the same form; no parts: the empty one"""
+        if not parts:
+            parts = [(np.zeros((0, 6), np.float32),) + (np.zeros(0, np.int32),) * (3 if self.track is not None else 2)]
+        return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
+
+    @torch.no_grad()
+    def _run(self, steps: list, write=None):
+        """the steps of `bank_schedule` / `bank_step`; write(offset into the chunk, samples, session, absolute position) queues one ring write"""
+        runs = [st[1] for st in steps if st[0] == "run"]
+        if self._h_ctl.shape[0] < len(runs):
+            self._h_ctl = torch.zeros(len(runs), 2 * self.batch + 1, dtype=torch.int64, pin_memory=True)
+        table = self._h_ctl
+        _GroupChain.bank_control_table(runs, self.batch, self.hop, table.numpy())
+        parts, k = [], 0
+        for st in steps:
+            if st[0] == "write":
+                write(st[2], st[3] - st[2], st[1], st[2])
+            else:
+                if k:
+                    parts.append(self._drain())   # the record holds one tick
+                self.chain.run(table[k])
+                self.ticks.append(list(st[1]))
+                k += 1
+        if k:
+            parts.append(self._drain())
+        return self.concat(parts)
+
+    def _advance(self, s: int, n: int, write):
+        """one chunk of n samples for session s; write(offset into the chunk, samples, ring of s, absolute position)"""
+        base, ring = self.state[0][s], self.chain.source[s]
+        steps, state = bank_schedule(self.state, s, n, self.win_len, self.hop, self.batch, self.ring_len)
+        out = self._run(steps, lambda lo, cnt, _, pos: write(lo - base, cnt, ring, pos))
+        self.state = state
+        return out
+
+    # ---- chunks
+    def push(self, s: int, chunk):
+        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of session s at 44.1 kHz"""
+        self._check_open(pushing=True, session=s)
+        chunk = self._float_chunk(chunk)
+        ptr, stride, cap = chunk.data_ptr(), chunk.stride(0), self.ring_len
+        return self._advance(int(s), chunk.shape[1], lambda off, cnt, ring, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt,
+                                                                                           ring, cap, pos))
+
+    def push_pcm(self, s: int, raw, width: int):
+        """raw: whole frames of interleaved little-endian signed PCM of session s, as `LiveSession.push_pcm` takes them"""
+        self._check_open(pushing=True, session=s)
+        raw, fb = self._pcm_chunk(raw, width)
+        width, ptr, cap = int(width), raw.data_ptr(), self.ring_len
+        return self._advance(int(s), raw.numel() // fb, lambda off, cnt, ring, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C,
+                                                                                              width, ring, cap, pos))
+
+    def step(self):
+        """Runs the windows that are ready but wait for a full tick, now: one short tick (nothing with none waiting)."""
+        self._check_open()
+        steps, self.state = bank_step(self.state)
+        return self._run(steps)
+
+    def flush(self):
+        """`step`, and ends all recordings: tails shorter than a window are dropped.  Afterwards a session takes pushes again only
+        behind its `reset`."""
+        self._check_open()
+        self.ended = [True] * self.n_sessions
+        return self.step()

@@ -56,6 +56,21 @@ def update(rows: torch.Tensor, cnt: torch.Tensor, ctl: torch.Tensor, rec_count: 
               int(cfg.max_tracks), float(cfg.iou_min), float(cfg.beta), int(cfg.max_age), float(cfg.birth_score))
 
 
+def new_bank_state(device, cfg: TrackConfig, n_sessions: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`new_state` for a bank of sessions: (slots int32 [n_sessions, max_tracks, 16], glob int32 [n_sessions, 2]), zeroed"""
+    return (torch.zeros(int(n_sessions), int(cfg.max_tracks), SLOT_WORDS, dtype=torch.int32, device=device),
+            torch.zeros(int(n_sessions), 2, dtype=torch.int32, device=device))
+
+
+def update_bank(rows: torch.Tensor, cnt: torch.Tensor, n_valid: torch.Tensor, win_sess: torch.Tensor, win_idx: torch.Tensor,
+                rec_count: torch.Tensor, rec_cap: int, rec_track: torch.Tensor, state, cfg: TrackConfig):
+    """One launch of mmd_track_update_bank on the current stream: `update` for a group whose row i is window win_idx[i] of session
+    win_sess[i], on the state of `new_bank_state` - in front of the mmd_det_record_append_bank that advances rec_count."""
+    _lib.call("mmd_track_update_bank", rows, cnt, rows.shape[0], rows.shape[1], n_valid, win_sess, win_idx, state[0].shape[0], rec_count,
+              int(rec_cap), rec_track, state[0], state[1], int(cfg.max_tracks), float(cfg.iou_min), float(cfg.beta), int(cfg.max_age),
+              float(cfg.birth_score))
+
+
 def overflow_message(cfg: TrackConfig, window) -> str:
     """what a set overflow flag means for the record whose window column is `window`"""
     window = np.asarray(window).reshape(-1)
