@@ -6,7 +6,7 @@
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
                      [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS]
     python detect.py --config_file F --checkpoint P --input X0 --input X1 [--input X2 ...] --output out.csv
-                     --window_s SECONDS --chunk_s SECONDS [--hop_s SECONDS] [--batch N] [--track ...]
+                     --window_s SECONDS --chunk_s SECONDS [--any_rate] [--hop_s SECONDS] [--batch N] [--track ...]
 
 X is a `.npy` holding float32 waveforms `[8, N]` (one clip) or `[B, 8, N]`, or an 8-channel 16-bit PCM `.wav` at 44.1 kHz (one clip;
 samples / 32768).  The waveforms go through the device front end (mel spectrogram, power_to_db per microphone, cubic resize to
@@ -50,7 +50,14 @@ side - and they go through ONE bank of live sessions (`AudioDetector.open_bank`)
 --chunk_s at a time in round robin, exhausted files drop out of the rotation, and one forward pass serves --batch ready windows of
 whichever recordings completed them (--batch defaults to the number of files: one fresh window of each).  The CSV gains a first column:
 session,window,t_start_s,x1,y1,x2,y2,score,label[,track]; window and track ids count per session, and the rows come in the order the
-bank ran them.  Several inputs do not go with --resample / --sample_rate / --live_s: the bank reads 44.1 kHz input only.
+bank ran them.  Several inputs do not go with --resample / --sample_rate / --live_s: without --any_rate the bank reads 44.1 kHz input only.
+
+With --any_rate (only with several --input, --window_s and --chunk_s) every file is a `.wav` of 8 channels of 16-, 24- or 32-bit PCM at
+ANY rate, each session at the rate R in its file's header (`AudioDetector.open_bank(sample_rates=...)`: the session resamples to 44.1 kHz
+as its chunks arrive).  The files are read round by round, round(chunk_s * R) frames of every file that still has some, and each
+round is ONE `LiveBank.push_all_pcm`: one staging copy and one launch for the ring writes of all sessions, one for their resampling.  The
+CSV has the same columns; window counts and times are those of the ceil(N * 44100 / R) resampled samples, in seconds of the recording.
+A `.npy` is refused under --any_rate (it holds no rate).
 """
 import argparse
 import csv
@@ -243,14 +250,20 @@ def check_chunk_flags(a):
 def check_bank_flags(a):
     """several --input: what can be refused from the flags alone, before any device work"""
     if len(a.inputs) < 2:
+        if a.any_rate:
+            raise ValueError("--any_rate is for several --input, each session at its file's rate (one recording of any rate: --live_s)")
         return
     if a.window_s is None or a.chunk_s is None:
         raise ValueError("several --input are read side by side into a bank of live sessions: they need --window_s and --chunk_s")
+    if a.any_rate and (a.resample or a.sample_rate is not None or a.live_s is not None):
+        raise ValueError("--any_rate does not go with --resample / --sample_rate / --live_s: every .wav is read at the rate in its header")
     if a.resample or a.sample_rate is not None or a.live_s is not None:
         raise ValueError("several --input do not go with --resample / --sample_rate / --live_s: the bank reads 44.1 kHz input only")
     if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
         raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
     for path in a.inputs:
+        if a.any_rate and os.path.splitext(path)[1].lower() != ".wav":
+            raise ValueError(f"{path}: --any_rate reads 8-channel PCM .wav files, whose headers hold their rates (a .npy holds none)")
         if os.path.splitext(path)[1].lower() not in (".npy", ".wav"):
             raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
     if a.batch is not None and a.batch < 1:
@@ -354,6 +367,21 @@ def run_bank(det, sources: list, win_len: int, hop: int, batch: int, track):
     return bank.concat(parts)
 
 
+def run_bank_rounds(det, sources: list, rates: list, win_len: int, hop: int, batch: int, track):
+    """sources: the chunk iterators of `open_live`, one per session at rates[k] -> what the bank returns for the rounds over them:
+    one `push_all_pcm` per round with a chunk of every file that still has one; `flush` at the end"""
+    bank = det.open_bank(len(sources), win_len, hop, batch=batch, track=track, sample_rates=rates)
+    parts, live = [], list(enumerate(iter(src) for src in sources))
+    while live:
+        got = [(k, it, next(it, None)) for k, it in live]
+        live = [(k, it) for k, it, c in got if c is not None]
+        if live:
+            parts.append(bank.push_all_pcm({k: c[0] for k, _, c in got if c is not None}, {k: c[1] for k, _, c in got if c is not None}))
+    parts.append(bank.flush())
+    bank.close()
+    return bank.concat(parts)
+
+
 def parse_args(argv=None):
     """-> the arguments; a.input is the one --input (as it always was) or, with several, the first, and a.inputs lists them all.
     --batch: None when not given - 8 with one input, the number of inputs with several."""
@@ -374,6 +402,7 @@ def parse_args(argv=None):
     ap.add_argument("--resample", action="store_true", help="a .wav of any rate, 16/24/32-bit PCM: decode and resample to 44.1 kHz on the device")
     ap.add_argument("--sample_rate", type=int, default=None, help="the rate in Hz of a .npy input; resampled to 44.1 kHz on the device")
     ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
+    ap.add_argument("--any_rate", action="store_true", help="several .wav inputs, each at the rate in its header (with --window_s --chunk_s)")
     ap.add_argument("--live_s", type=float, default=None, help="read a recording of any rate this many seconds at a time into a live session that resamples (with --window_s)")
     a = ap.parse_args(argv)
     a.inputs, a.input = a.input, a.input[0]
@@ -387,8 +416,16 @@ def parse_args(argv=None):
 
 def main_bank(a, cfg, track):
     """several --input through one bank"""
-    chunk = int(round(a.chunk_s * SAMPLE_RATE))
-    opened = [open_chunked(path, chunk) for path in a.inputs]
+    if a.any_rate:
+        from mm_distillnet_amd.audio import resample_len, resample_ratio
+        opened = [open_live(path, a.chunk_s) for path in a.inputs]
+        rates = [rate for _, rate, _ in opened]
+        for rate in rates:
+            resample_ratio(rate)                  # an unsupported ratio is refused before any device work
+        opened = [(resample_len(n_frames, rate, SAMPLE_RATE), chunks) for n_frames, rate, chunks in opened]
+    else:
+        chunk = int(round(a.chunk_s * SAMPLE_RATE))
+        opened = [open_chunked(path, chunk) for path in a.inputs]
     sizes = [stream_sizes(a.window_s, a.hop_s, n_total) for n_total, _ in opened]
     win_len, hop, n_win = sizes[0][0], sizes[0][1], sum(z[2] for z in sizes)
     torch.cuda.set_device(0)
@@ -396,7 +433,11 @@ def main_bank(a, cfg, track):
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     det = AudioDetector.from_step_config(sspec, "cuda:0", T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
-    got = run_bank(det, [chunks for _, chunks in opened], win_len, hop, len(a.inputs) if a.batch is None else a.batch, track)
+    batch = len(a.inputs) if a.batch is None else a.batch
+    if a.any_rate:
+        got = run_bank_rounds(det, [chunks for _, chunks in opened], rates, win_len, hop, batch, track)
+    else:
+        got = run_bank(det, [chunks for _, chunks in opened], win_len, hop, batch, track)
     n = write_bank_csv(a.output, *got[:3], hop, got[3] if track is not None else None)
     print("%d sessions, %d windows, %d boxes -> %s" % (len(a.inputs), n_win, n, a.output))
     return got

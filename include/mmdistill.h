@@ -689,6 +689,41 @@ int mmd_ring_resample(const float* in_ring, long long in_cap, int channels, long
 // floats, so a small ring costs blocks, never bits.  Host only, no launch; -22 on L or M outside 1 .. 1024, taps odd or outside 2 .. 4096.
 int mmd_ring_resample_span(int L, int M, int taps);
 
+// ---- one round of chunks of a BANK of sessions (csrc/live.hip, LiveBank.push_all): the ring writers and the ring resampler above for
+// several rings in ONE launch each, driven by a table of descriptors in DEVICE memory (the number of entries varies per call).  The
+// caller builds the table on the host, uploads it - in the same copy as the chunks - and hands over both: h_desc, the host copy, which
+// the wrapper checks and sizes the grid from, and d_desc, the device copy, which the blocks read (that the two agree, and that the
+// upload is ordered in front of the launch on `stream`, is the caller's duty).  blockIdx.z names the entry, the grid covers the largest
+// entry, and a block outside its own entry's range returns before it touches memory.
+//
+// mmd_rings_push: entry e does what one mmd_ring_push / mmd_ring_push_pcm call does.  A descriptor is 64 bytes, eight int64:
+//   {src_off, src_stride, n, kind, ring, cap, p0, 0} - the chunk lies src_off BYTES behind src_base (float rows: a multiple of 4, and
+//   src_base 4-byte aligned); src_stride: floats between two channels' rows (float rows; >= n); n: samples per channel or frames, 1 .. cap;
+//   kind: 0 = float rows [channels, n], 2 / 3 / 4 = interleaved PCM frames of that width; ring: the DEVICE ADDRESS of the destination
+//   ring[channels, cap]; p0 = pos % cap, reduced on the host (0 <= p0 < cap).
+// Float entries run mmd_ring_push's blocks (1024 samples of one channel, wrap once), PCM entries mmd_ring_push_pcm's (pcm_tile.h: the
+// floats are mmd_pcm_to_float's), so ring[c, (pos + i) % cap] gets the bits the single calls give it.  Plain vector stores, no
+// atomics, no allocation, no host synchronisation; nothing outside each entry's n slots per channel is touched.  Entries must not
+// name overlapping slots of one ring.  -22 before any launch on a null src_base or table, n_desc or channels outside 1 .. 65535, and on
+// any entry with a null ring, src_off < 0, n < 1, n > cap, cap > 2^50, p0 outside 0 .. cap-1, another kind, src_stride < n or a
+// misaligned float chunk, channels * width above mmd_pcm_to_float's cap.
+int mmd_rings_push(const void* src_base, const void* h_desc, const void* d_desc, int n_desc, int channels, hipStream_t stream);
+
+// mmd_rings_resample: entry e does what one mmd_ring_resample call does - its own L, M, taps, bank, phase_off, rings and range, so
+// sessions at different rates share the launch.  Grid (max blocks, max phase tiles, channels * n_desc), dynamic LDS the largest span
+// among the entries; a block whose tile lies outside its own entry's grid returns before the first barrier.  Staging, tap loop and
+// the masked, wrapped stores are mmd_ring_resample's (one tile body), so every output has the bits that call gives it.  A descriptor
+// is 192 bytes and is written by mmd_rings_resample_plan alone: the arguments of mmd_ring_resample (addresses as int64) and behind
+// them the launch plan made of them.  The wrapper plans every entry of h_desc anew from its arguments and refuses (-22, nothing is
+// launched) an entry mmd_ring_resample would refuse - the range whose oldest input has left the ring included - or whose plan is not
+// the planner's; also null tables, n_desc < 1 and channels * n_desc > 65535.
+int mmd_rings_resample(const void* h_desc, const void* d_desc, int n_desc, int channels, hipStream_t stream);
+
+// Host only, no launch: fills entry `index` (0 .. 65534) of the HOST table h_desc (192 bytes per entry) for mmd_rings_resample from
+// the arguments of mmd_ring_resample; in_ring, bank, phase_off and out_ring are device addresses and are not read.  -22, the entry
+// untouched, on everything mmd_ring_resample refuses.
+int mmd_rings_resample_plan(void* h_desc, int index, const float* in_ring, long long in_cap, int channels, long long n_valid, const float* bank, const int* phase_off, int L, int M, int taps, float* out_ring, long long out_cap, long long t_lo, long long t_hi);
+
 // ---- device-side detection record (csrc/stream.hip): the rows mmd_nms_teacher leaves for a group of windows, appended behind every
 // group with one host copy at the end of the recording (the shape of mmd_eval_match's record).
 // rows[B, cap_img, 6] / cnt[B]: decode / NMS output (counts are clamped to 0 .. cap_img).  ctl[2] (DEVICE) = {n_valid, first_window}:

@@ -164,6 +164,63 @@ def bank_schedule(state, session: int, n: int, win_len: int, hop: int, batch: in
         w = hi
 
 
+def bank_round(state, pushes, win_len: int, hop: int, batch: int, cap: int):
+    """One ROUND of pushes to a bank (`LiveBank.push_all`): pushes = [(session, [n_0, n_1, ...]), ...] with the sessions ascending and
+    each at most once; n_i: the 44.1 kHz samples the i-th input piece of that session's chunk hands to `bank_schedule` (a 44.1 kHz
+    session: one piece, the chunk itself; a session at another rate: per piece of its input ring what `live_resample_ready` newly
+    allows, possibly 0).  -> (fast, steps, state', why): steps and state' are those of the SEQUENTIAL order - `bank_schedule` for every
+    piece of every session in turn - which the round's results are defined by; fast says whether all the round's ring writes may be
+    done first, in one batched launch, and its ticks afterwards; why names what forbids it ("pieces", "writes", "hoist") or is None.
+
+    The rule.  fast holds when every chunk is one piece, every session has at most one write step, and every write (s, lo, hi) has
+    hi <= first_s * hop + cap, first_s the first window of s that has not run AT THE START of the round (queued in the FIFO, or the
+    next to complete).  Then a write moved in front of the round's ticks overwrites only slots of samples below hi - cap <= first_s * hop,
+    which no window that any of those ticks runs still needs: every tick reads from the rings what it reads in the sequential order.
+    Without the third clause a tick early in the round could run a queued window of s whose first samples the hoisted write of s -
+    scheduled behind that tick, where it was allowed to pass them - has already replaced."""
+    hop, cap = int(hop), int(cap)
+    sessions = [int(s) for s, _ in pushes]
+    if sessions != sorted(set(sessions)):
+        raise ValueError(f"a round names every session at most once, in ascending order: {sessions}")
+    _, nxt0, fifo0 = state
+    steps, pieces_of = [], {}
+    for s, pieces in pushes:
+        pieces_of[int(s)] = len(pieces)
+        for n in pieces:
+            got, state = bank_schedule(state, s, n, win_len, hop, batch, cap)
+            steps += got
+    why = None
+    for s in sessions:
+        writes = [st for st in steps if st[0] == "write" and st[1] == s]
+        first = min([q[1] for q in fifo0 if q[0] == s], default=nxt0[s])
+        if pieces_of[s] != 1:
+            why = "pieces"
+        elif len(writes) > 1:
+            why = "writes"
+        elif writes and writes[0][3] > first * hop + cap:
+            why = "hoist"
+        if why is not None:
+            break
+    return why is None, steps, state, why
+
+
+def live_pieces(n_in: int, in_written: int, written: int, L: int, M: int, half: int, in_cap: int) -> list:
+    """How a push of n_in input-rate samples to a resampling session goes through its input ring of in_cap samples: [(samples of the
+    piece, 44.1 kHz samples it makes ready), ...] - pieces of at most in_cap - 2 * half - M samples (the oldest input a pending output
+    needs survives the piece), each followed by the outputs `live_resample_ready` newly allows.  in_written: input samples pushed so
+    far; written: outputs handed to the schedule so far."""
+    piece, out = int(in_cap) - 2 * int(half) - int(M), []
+    if piece < 1:
+        raise ValueError(f"an input ring of {in_cap} samples leaves no room for a piece behind {2 * half} taps + M = {M}")
+    for off in range(0, int(n_in), piece):
+        cnt = min(piece, int(n_in) - off)
+        in_written += cnt
+        ready = live_resample_ready(in_written, L, M, half)
+        out.append((cnt, ready - written))
+        written = ready
+    return out
+
+
 def bank_step(state):
     """The short tick: runs NOW whatever the FIFO holds (1 .. batch-1 windows; the control row pads the tick by repeating its last
     window, and the padding is not recorded).  -> (steps, state'): one ("run", windows) step, or none with an empty FIFO."""
@@ -273,6 +330,7 @@ class MelFrontEnd:
 RS_ZEROS, RS_ROLLOFF, RS_BETA = 64, 0.9475937167399596, 14.769656459379492
 RS_MAX_FACTOR = 1024                                 # cap of L and M in mmd_resample_poly
 RS_MAX_TAPS = 4096                                   # and of the taps per output: 2 * ceil(64 * max(1, M / L))
+RINGS_PUSH_DESC, RINGS_RS_DESC = 64, 192             # bytes per descriptor of mmd_rings_push / mmd_rings_resample (include/mmdistill.h)
 
 
 def resample_len(n_in: int, sr_in: int, sr_out: int = 44100) -> int:
@@ -390,6 +448,23 @@ class Resampler:
         self.call("mmd_ring_resample", in_ring, in_ring.shape[1], in_ring.shape[0], int(n_valid), bank, phase_off, L, M, taps, out_ring,
                   out_ring.shape[1], int(t_lo), int(t_hi))
 
+    def rings_resample_plan(self, h_desc: np.ndarray, k: int, in_ring: torch.Tensor, n_valid: int, sr_in: int, out_ring: torch.Tensor,
+                            t_lo: int, t_hi: int, sr_out: int = 44100):
+        """Entry k of a host table for `rings_resample_into` (`mmd_rings_resample_plan`, host only): what `ring_resample_into` takes.
+        h_desc: uint8 [>= (k + 1) * RINGS_RS_DESC] numpy memory (a view of the pinned buffer that is uploaded).  RuntimeError, the entry
+        untouched, on a range `ring_resample_into` refuses."""
+        if h_desc.dtype != np.uint8 or h_desc.ndim != 1 or h_desc.size < (int(k) + 1) * RINGS_RS_DESC or not h_desc.flags.c_contiguous:
+            raise ValueError(f"rings_resample_plan: entry {k} needs {(int(k) + 1) * RINGS_RS_DESC} contiguous uint8 bytes")
+        L, M, taps, bank, phase_off = self._bank(sr_in, sr_out)
+        self.call("mmd_rings_resample_plan", h_desc.ctypes.data, int(k), in_ring, in_ring.shape[1], in_ring.shape[0], int(n_valid), bank,
+                  phase_off, L, M, taps, out_ring, out_ring.shape[1], int(t_lo), int(t_hi))
+
+    def rings_resample_into(self, h_desc: np.ndarray, d_desc: torch.Tensor, n_desc: int, channels: int):
+        """`ring_resample_into` for the n_desc entries of a table in ONE launch (`mmd_rings_resample`; sessions at different rates
+        share it): h_desc as `rings_resample_plan` filled it, d_desc its copy on the device (uint8; the upload is queued on the
+        current stream in front of this call).  Every output has the bits `ring_resample_into` gives it."""
+        self.call("mmd_rings_resample", h_desc.ctypes.data, d_desc, int(n_desc), int(channels))
+
     def pcm_to_float(self, raw: torch.Tensor, frames: int, channels: int, width: int) -> torch.Tensor:
         """interleaved little-endian signed PCM, raw uint8 [frames * channels * width] on the device (a WAV's frames as read) ->
         float32 [channels, frames] in [-1, 1) (`mmd_pcm_to_float`): 16-bit / 2^15, 24-bit / 2^23, 32-bit rounded to float32 then / 2^31."""
@@ -399,3 +474,22 @@ class Resampler:
         out = torch.empty(int(channels), int(frames), device=self.device)
         self.call("mmd_pcm_to_float", raw, int(frames), int(channels), int(width), out)
         return out
+
+
+# ---- one round of ring writes in one launch (csrc/live.hip: `mmd_rings_push`), beside `Resampler.ring_resample_into` / `rings_resample_into`
+def rings_push_entry(h_desc: np.ndarray, k: int, src_off: int, src_stride: int, n: int, kind: int, ring: torch.Tensor, cap: int, pos: int):
+    """Entry k of a host table for `rings_push_into`: h_desc int64 [>= k + 1, 8].  The chunk lies src_off bytes behind the launch's base:
+    kind 0, float32 rows src_stride floats apart; kind 2 / 3 / 4, interleaved PCM frames of that width.  Its n samples per channel go
+    to ring (float32 [C, cap] on the device, or the address of one) at the absolute position pos, reduced modulo cap here."""
+    ptr = ring.data_ptr() if isinstance(ring, torch.Tensor) else int(ring)
+    h_desc[k] = (int(src_off), int(src_stride), int(n), int(kind), ptr, int(cap), int(pos) % int(cap), 0)
+
+
+def rings_push_into(src_base, h_desc: np.ndarray, d_desc, n_desc: int, channels: int):
+    """The n_desc ring writes of a host table in ONE launch (`mmd_rings_push`): src_base, a device tensor or address the entries'
+    src_off count from; h_desc int64 [>= n_desc, 8] as `rings_push_entry` filled it; d_desc its copy on the device (the upload is queued
+    on the current stream in front of this call).  Every ring gets the bits `mmd_ring_push` / `mmd_ring_push_pcm` give it."""
+    from . import _lib
+    if h_desc.dtype != np.int64 or h_desc.ndim != 2 or h_desc.shape[1] != 8 or h_desc.shape[0] < int(n_desc) or not h_desc.flags.c_contiguous:
+        raise ValueError("rings_push_into takes a contiguous int64 [>= n_desc, 8] host table")
+    _lib.call("mmd_rings_push", src_base, h_desc.ctypes.data, d_desc, int(n_desc), int(channels))

@@ -17,8 +17,8 @@
 
 __device__ __forceinline__ int pcm_lds(int byte) { return (((byte >> 2) + (byte >> 7)) << 2) | (byte & 3); }
 
-// frames per block, or 0 where channels * width is above the tile
-static inline int pcm_tile_frames(int channels, int width) {
+// frames per block, or 0 where channels * width is above the tile (host and device: mmd_rings_push's blocks work it out per entry)
+__host__ __device__ static inline int pcm_tile_frames(int channels, int width) {
   if (channels < 1 || channels > PCM_TILE_BYTES / width) return 0;
   const int F = PCM_TILE_BYTES / (channels * width);
   return F > PCM_FMAX ? PCM_FMAX : F;

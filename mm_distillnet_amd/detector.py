@@ -22,7 +22,10 @@ another rate than 44.1 kHz (`open_stream(sample_rate=R)`) goes through a second 
 
 `open_bank` is that chain for SEVERAL sources at once: a `LiveBank` keeps one ring and one tracker per session behind one captured
 graph, and each row of a group names the session and the window it is (`mmd_melspec_windows_rings`, `mmd_track_update_bank`,
-`mmd_det_record_append_bank`), so one forward pass serves one fresh window of every source."""
+`mmd_det_record_append_bank`), so one forward pass serves one fresh window of every source.  Every session of a bank may have a sample
+rate of its own (`open_bank(sample_rates=...)`: an input ring per such session, as `open_stream` keeps one), and `LiveBank.push_all`
+sends one round of chunks - one of every session - through one staging copy and one launch each of `mmd_rings_push` and
+`mmd_rings_resample`."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -33,8 +36,9 @@ import torch
 
 from .arch import NetSpec
 from . import _lib
-from .audio import (MelFrontEnd, Resampler, bank_reset, bank_schedule, bank_state, bank_step, live_group_span, live_in_ring_min,
-                    live_resample_ready, live_schedule, resample_ratio, stream_window_starts)
+from .audio import (RINGS_PUSH_DESC, RINGS_RS_DESC, MelFrontEnd, Resampler, bank_reset, bank_round, bank_schedule, bank_state, bank_step,
+                    live_group_span, live_in_ring_min, live_pieces, live_resample_ready, live_schedule, resample_ratio, rings_push_entry,
+                    rings_push_into, stream_window_starts)
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -299,18 +303,26 @@ class AudioDetector:
 
     @torch.no_grad()
     def open_bank(self, n_sessions: int, win_len: int, hop: int, batch: Optional[int] = None, track: Optional[TrackConfig] = None,
-                  ring_len: Optional[int] = None) -> "LiveBank":
+                  ring_len: Optional[int] = None, sample_rates: Optional[Sequence] = None, in_ring_len=None) -> "LiveBank":
         """Opens a bank of n_sessions live sessions behind one captured chain - see `LiveBank`: several microphone arrays (or files
         replayed side by side) push independently, and one forward pass serves `batch` ready windows of whichever sessions completed
         them.  win_len, hop, track as `open_stream`; batch: windows per tick, default n_sessions (one fresh window of each);
         ring_len: samples per channel EACH session keeps on the device, at least (batch - 1) * hop + win_len (ValueError below
-        that), default twice that.  The input is at 44.1 kHz: per-session resampling is not built (there is no sample_rate).  The
-        detector holds one stream, session or bank at a time: opening any of them closes the others."""
+        that), default twice that.  The detector holds one stream, session or bank at a time: opening any of them closes the others.
+
+        sample_rates: None - every session is pushed 44.1 kHz samples, the default - or one entry per session: None, 44100 or the
+        rate in Hz of the samples that session will be pushed.  With None, or no entry other than None / 44100, nothing below exists
+        and the bank is the 44.1 kHz bank.  A session at another rate R resamples as its chunks arrive, as `open_stream(sample_rate=R)`
+        does (`LiveBank`); win_len, hop, ring_len and the window indices stay in 44.1 kHz samples.  A ratio `audio.resample_ratio`
+        refuses raises its ValueError here, before any device work.  in_ring_len (only with such a session): input-rate samples
+        per channel that session keeps - one value for all of them, or one entry per session (None where the session is at 44.1
+        kHz) - at least `audio.live_in_ring_min`, default taps + M + ceil(ring_len * M / L), both as `open_stream`'s."""
         if track is not None and not isinstance(track, TrackConfig):
             raise ValueError("open_bank: track must be a TrackConfig or None")
         self._close_live()
         self._stream = None
-        self._bank = LiveBank(self, int(n_sessions), int(win_len), int(hop), int(n_sessions if batch is None else batch), track, ring_len)
+        self._bank = LiveBank(self, int(n_sessions), int(win_len), int(hop), int(n_sessions if batch is None else batch), track, ring_len,
+                              sample_rates, in_ring_len)
         return self._bank
 
 
@@ -471,23 +483,33 @@ class _ChunkInput:
         self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
         self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
         self._pushes = 0
+        self.launches = {"staging_copies": 0}     # H2D copies of host chunks through the staging buffers
 
-    def _to_device(self, host: torch.Tensor) -> torch.Tensor:
-        """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
+    def _stage_buffer(self, nbytes: int) -> torch.Tensor:
+        """the pinned staging buffer whose turn it is, at least nbytes long, free to be written; `_staged` follows its upload"""
         k = self._pushes & 1
-        self._pushes += 1
-        nbytes = host.numel() * host.element_size()
         self._stage_ev[k].synchronize()           # the copy that last read this buffer (two pushes back) is done
         if self._stage[k] is None or self._stage[k].numel() < nbytes:
             self._stage[k] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
-        pinned = self._stage[k][:nbytes].view(host.dtype).view(host.shape)
+        return self._stage[k]
+
+    def _staged(self):
+        """behind the copy out of `_stage_buffer`'s buffer: the event its next writer waits for, and the turn passes on"""
+        self._stage_ev[self._pushes & 1].record()
+        self._pushes += 1
+        self.launches["staging_copies"] += 1
+
+    def _to_device(self, host: torch.Tensor) -> torch.Tensor:
+        """a host tensor -> a contiguous device copy through the pinned staging buffer whose turn it is"""
+        nbytes = host.numel() * host.element_size()
+        pinned = self._stage_buffer(nbytes)[:nbytes].view(host.dtype).view(host.shape)
         pinned.copy_(host)
         dev = pinned.to(self.det.device, non_blocking=True)
-        self._stage_ev[k].record()
+        self._staged()
         return dev
 
-    def _float_chunk(self, chunk) -> torch.Tensor:
-        """push's argument -> float32 [C, n] on the device, rows at least n apart, unit stride along the samples"""
+    def _float_checked(self, chunk) -> torch.Tensor:
+        """push's argument, checked -> a float32 [C, n] tensor, where it is (host or device)"""
         if isinstance(chunk, np.ndarray):
             if chunk.dtype != np.float32:
                 raise ValueError("push takes float32 [%d, n] samples, found %s" % (self.C, chunk.dtype))
@@ -495,14 +517,19 @@ class _ChunkInput:
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 2 or chunk.dtype != torch.float32 or chunk.shape[0] != self.C or \
                 chunk.shape[1] < 1:
             raise ValueError("push takes float32 [%d, n] samples, n >= 1" % self.C)
+        return chunk
+
+    def _float_chunk(self, chunk) -> torch.Tensor:
+        """push's argument -> float32 [C, n] on the device, rows at least n apart, unit stride along the samples"""
+        chunk = self._float_checked(chunk)
         if not chunk.is_cuda:
             chunk = self._to_device(chunk)
         elif chunk.stride(1) != 1 or chunk.stride(0) < chunk.shape[1]:
             chunk = chunk.contiguous()
         return chunk
 
-    def _pcm_chunk(self, raw, width: int):
-        """push_pcm's arguments -> (uint8 frames on the device, bytes per frame)"""
+    def _pcm_checked(self, raw, width: int):
+        """push_pcm's arguments, checked -> (uint8 frames where they are - a host or device tensor - bytes per frame)"""
         width = int(width)
         if width not in (2, 3, 4):
             raise ValueError("push_pcm: width = %d (2, 3 or 4 bytes per sample)" % width)
@@ -513,6 +540,11 @@ class _ChunkInput:
         fb = self.C * width
         if raw.numel() < fb or raw.numel() % fb:
             raise ValueError("push_pcm: %d bytes are not whole frames of %d x %d bytes" % (raw.numel(), self.C, width))
+        return raw, fb
+
+    def _pcm_chunk(self, raw, width: int):
+        """push_pcm's arguments -> (uint8 frames on the device, bytes per frame)"""
+        raw, fb = self._pcm_checked(raw, width)
         return (raw.contiguous() if raw.is_cuda else self._to_device(raw)), fb
 
 
@@ -738,8 +770,8 @@ class LiveSession(_ChunkInput):
 class LiveBank(_ChunkInput):
     """Several recordings that arrive in chunks, side by side (`AudioDetector.open_bank`): n_sessions rings [n_sessions, 8, ring_len]
     and n_sessions trackers behind ONE chain and one captured graph.  `push(s, chunk)` / `push_pcm(s, raw, width)` write a chunk of
-    session s into its ring (the argument forms of `LiveSession`, 44.1 kHz only: per-session resampling is not built) and return the
-    results of the ticks the chunk completed; `step()` runs the pending windows now; `flush()` is `step()` and ends all recordings;
+    session s into its ring (the argument forms of `LiveSession`; at 44.1 kHz unless the session was opened at another rate, below)
+    and return the results of the ticks the chunk completed; `push_all` / `push_all_pcm` take one chunk of several sessions in one call; `step()` runs the pending windows now; `flush()` is `step()` and ends all recordings;
     `reset(s)` starts a new recording on session s; `close()` releases the bank.
 
     The schedule (`audio.bank_schedule`).  Window w of session s is ready once its last sample w * hop + win_len - 1 has been pushed;
@@ -771,10 +803,34 @@ class LiveBank(_ChunkInput):
 
     Synchronisation follows `LiveSession`: a push that completes no tick only queues its ring write; a push that completes ticks
     drains the record once per tick, behind one copy of the block (rows, windows, track ids, sessions, count) and the overflow
-    flags into pinned host memory; host chunks go through the two pinned staging buffers under the same event rule."""
+    flags into pinned host memory; host chunks go through the two pinned staging buffers under the same event rule.
+
+    Sessions at other rates (`open_bank(sample_rates=...)`; with none the bank has no input ring and no resampler, and nothing of
+    this runs).  A session s at rate R_s owns an input ring in_rings[s] [8, in_ring_len[s]] of input-rate samples, and its pushes are
+    `LiveSession`'s: the chunk goes into that ring in pieces of at most in_ring_len - taps - M samples; after each piece the
+    outputs whose last tap has arrived (`audio.live_resample_ready`) are handed to `audio.bank_schedule` exactly as a 44.1 kHz push of
+    that many samples; every "write" step becomes one resampling of that output range into the session's ring - what the schedule
+    skips is never computed - and the ticks are untouched.  `reset(s)` also resets the session's input position.  `flush()` first
+    produces, for every such session in ascending order, the outputs up to `audio.resample_len` of what it was pushed (the filter's
+    tail reads zeros), running the full ticks that completes, then runs the short tick and ends all recordings.
+    (d) The 44.1 kHz samples session s's ring receives are bit for bit `Resampler.resample(whole recording of s, R_s)`, and the
+        bank's ticks and bytes equal those of a 44.1 kHz bank that is fed those resampled recordings, cut where
+        `live_resample_ready` says the outputs become available.
+
+    A round of chunks (`push_all(chunks)` / `push_all_pcm(chunks, width)`: a mapping, or a sequence of pairs, from session to a chunk
+    in `push`'s / `push_pcm`'s forms; width: one int, or one per session - a mapping, or a sequence indexed by session).  Result,
+    ticks and bytes are EXACTLY those of `push(s, chunk_s)` for the sessions in ascending order.  The host works out that
+    sequential schedule first (`audio.bank_round`).  Where every chunk is one input piece, every session gets at most one ring write
+    and no write passes (first window of s not run at the start of the call) * hop + ring_len - so that a write moved in front of
+    the call's ticks overwrites nothing a pending window needs - the round takes the fast path: all host chunks and the two
+    descriptor tables are packed into the staging buffer whose turn it is (payloads aligned to 16 bytes, the same event rule), go
+    to the device in ONE copy, ONE `mmd_rings_push` writes the input rings of the sessions at other rates and the rings of the
+    44.1 kHz sessions, at most ONE `mmd_rings_resample` makes the 44.1 kHz samples of the others, and the ticks run in order with a
+    drain per tick.  Any other round - and any round with a device-tensor chunk - is the sequential pushes.  `launches` counts
+    "fast_rounds", "fallback_rounds", "rings_push", "rings_resample" (the batched launches) and "staging_copies"."""
 
     def __init__(self, det: AudioDetector, n_sessions: int, win_len: int, hop: int, batch: int, track: Optional[TrackConfig],
-                 ring_len: Optional[int]):
+                 ring_len: Optional[int], sample_rates: Optional[Sequence] = None, in_ring_len=None):
         C = det.net.spec.in_channels
         if n_sessions < 1 or n_sessions > 65535:
             raise ValueError("open_bank: n_sessions = %d (1 .. 65535)" % n_sessions)
@@ -790,9 +846,37 @@ class LiveBank(_ChunkInput):
         rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
         if rec_cap > 0x7fffffff // 9:
             raise ValueError("open_bank: a record of %d rows" % rec_cap)
+        # sessions at other rates than the front end's: (rate, L, M, half) and the input ring's size, settled before any device work
+        rates = [None] * n_sessions if sample_rates is None else list(sample_rates)
+        if len(rates) != n_sessions:
+            raise ValueError("open_bank: sample_rates has %d entries for %d sessions" % (len(rates), n_sessions))
+        in_lens = list(in_ring_len) if isinstance(in_ring_len, (list, tuple)) else [in_ring_len] * n_sessions
+        if len(in_lens) != n_sessions:
+            raise ValueError("open_bank: in_ring_len has %d entries for %d sessions" % (len(in_lens), n_sessions))
+        self.rs, self.in_ring_len, self.in_rings, self.in_written = [None] * n_sessions, [None] * n_sessions, [None] * n_sessions, [0] * n_sessions
+        for s, rate in enumerate(rates):
+            if rate is None or int(rate) == 44100:
+                continue
+            L, M, half = resample_ratio(int(rate))
+            least = live_in_ring_min(L, M, half)
+            in_cap = 2 * half + M - ((-cap * M) // L) if in_lens[s] is None else int(in_lens[s])      # taps + M + ceil(cap * M / L)
+            if in_cap < least:
+                raise ValueError("open_bank: in_ring_len = %d of session %d is shorter than the %d samples resampling %d Hz needs (%d taps "
+                                 "+ M = %d + 1, and no fewer than a block stages)" % (in_cap, s, least, int(rate), 2 * half, M))
+            self.rs[s], self.in_ring_len[s] = (int(rate), L, M, half), in_cap
+        if any(n is not None and self.rs[s] is None for s, n in enumerate(in_lens)) and \
+                (isinstance(in_ring_len, (list, tuple)) or not any(self.rs)):
+            raise ValueError("open_bank: in_ring_len goes with sessions at a sample rate other than 44100 (nothing else is resampled)")
         self.track, self.n_sessions, self.win_len, self.hop, self.batch, self.ring_len = track, n_sessions, win_len, hop, batch, cap
         self.state, self.ticks, self.ended, self.closed = bank_state(n_sessions), [], [False] * n_sessions, False
         self._init_staging(det, C)
+        self.launches.update(fast_rounds=0, fallback_rounds=0, rings_push=0, rings_resample=0)
+        for s, rs in enumerate(self.rs):
+            if rs is not None:
+                if det.resampler is None:
+                    det.resampler = Resampler(det.device)
+                det.resampler._bank(rs[0], 44100)         # the bank goes to the device now, not in the first push
+                self.in_rings[s] = torch.zeros(C, self.in_ring_len[s], device=det.device)
         self._h_blob = torch.zeros(9 * rec_cap + 2, dtype=torch.int32, pin_memory=True)      # the record's host copy
         self._h_flags = torch.zeros(1 + 2 * n_sessions, dtype=torch.int32, pin_memory=True)  # detector overflow; per session {next_id, overflow}
         self._h_ctl = torch.zeros(1, 2 * batch + 1, dtype=torch.int64, pin_memory=True)
@@ -810,10 +894,10 @@ class LiveBank(_ChunkInput):
 
     def reset(self, s: int):
         """Starts a new recording on session s: its position and window count back to 0, its tracker zeroed (ids start at 0 again),
-        its queued windows dropped; the other sessions, the graph, the rings and every buffer stay.  After a `flush` it reopens
-        session s alone for pushes."""
+        its queued windows dropped, its input position (a session at another rate) back to 0; the other sessions, the graph, the rings
+        and every buffer stay.  After a `flush` it reopens session s alone for pushes."""
         self._check_open(session=s)
-        self.state, self.ended[int(s)] = bank_reset(self.state, int(s)), False
+        self.state, self.ended[int(s)], self.in_written[int(s)] = bank_reset(self.state, int(s)), False, 0
         if self.track is not None:
             for t in self.chain.trk_state:
                 t[int(s)].zero_()
@@ -824,6 +908,7 @@ class LiveBank(_ChunkInput):
             torch.cuda.synchronize()
             self.closed = True
             self.chain = self._h_blob = self._stage = None
+            self.in_rings = [None] * self.n_sessions
             if self.det._bank is self:
                 self.det._bank = None
 
@@ -869,30 +954,148 @@ class LiveBank(_ChunkInput):
             parts.append(self._drain())
         return self.concat(parts)
 
+    def _produce(self, s: int, final: bool):
+        """session s at another rate: the 44.1 kHz samples its input so far allows (final: up to the recording's end), through the
+        schedule: every ring write is one `mmd_ring_resample` from its input ring"""
+        rate, L, M, half = self.rs[s]
+        ready = live_resample_ready(self.in_written[s], L, M, half, final)
+        steps, state = bank_schedule(self.state, s, ready - self.state[0][s], self.win_len, self.hop, self.batch, self.ring_len)
+        rs, in_ring, ring, n_valid = self.det.resampler, self.in_rings[s], self.chain.source[s], self.in_written[s]
+        out = self._run(steps, lambda lo, cnt, _, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
+        self.state = state
+        return out
+
     def _advance(self, s: int, n: int, write):
-        """one chunk of n samples for session s; write(offset into the chunk, samples, ring of s, absolute position)"""
-        base, ring = self.state[0][s], self.chain.source[s]
+        """one chunk of n samples for session s; write(offset into the chunk, samples, ring, its length, absolute position)"""
+        if self.rs[s] is not None:
+            _, L, M, half = self.rs[s]
+            parts, off = [], 0
+            for cnt, _ in live_pieces(n, self.in_written[s], self.state[0][s], L, M, half, self.in_ring_len[s]):
+                write(off, cnt, self.in_rings[s], self.in_ring_len[s], self.in_written[s])
+                self.in_written[s] += cnt
+                off += cnt
+                parts.append(self._produce(s, False))
+            return self.concat(parts)
+        base, ring, cap = self.state[0][s], self.chain.source[s], self.ring_len
         steps, state = bank_schedule(self.state, s, n, self.win_len, self.hop, self.batch, self.ring_len)
-        out = self._run(steps, lambda lo, cnt, _, pos: write(lo - base, cnt, ring, pos))
+        out = self._run(steps, lambda lo, cnt, _, pos: write(lo - base, cnt, ring, cap, pos))
         self.state = state
         return out
 
     # ---- chunks
     def push(self, s: int, chunk):
-        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of session s at 44.1 kHz"""
+        """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of session s (at 44.1 kHz, or at
+        the rate the session was opened with)"""
         self._check_open(pushing=True, session=s)
         chunk = self._float_chunk(chunk)
-        ptr, stride, cap = chunk.data_ptr(), chunk.stride(0), self.ring_len
-        return self._advance(int(s), chunk.shape[1], lambda off, cnt, ring, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt,
-                                                                                           ring, cap, pos))
+        ptr, stride = chunk.data_ptr(), chunk.stride(0)
+        return self._advance(int(s), chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C,
+                                                                                                cnt, ring, cap, pos))
 
     def push_pcm(self, s: int, raw, width: int):
         """raw: whole frames of interleaved little-endian signed PCM of session s, as `LiveSession.push_pcm` takes them"""
         self._check_open(pushing=True, session=s)
         raw, fb = self._pcm_chunk(raw, width)
-        width, ptr, cap = int(width), raw.data_ptr(), self.ring_len
-        return self._advance(int(s), raw.numel() // fb, lambda off, cnt, ring, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C,
-                                                                                              width, ring, cap, pos))
+        width, ptr = int(width), raw.data_ptr()
+        return self._advance(int(s), raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt,
+                                                                                                   self.C, width, ring, cap, pos))
+
+    # ---- a round of chunks
+    def _round_items(self, chunks) -> list:
+        """push_all's mapping or sequence of pairs -> [(session, chunk), ...] in ascending session order, every session open for pushes"""
+        items = sorted(chunks.items() if hasattr(chunks, "items") else [tuple(c) for c in chunks], key=lambda c: c[0])
+        for k, (s, _) in enumerate(items):
+            self._check_open(pushing=True, session=s)
+            if k and int(items[k - 1][0]) == int(s):
+                raise ValueError("push_all: session %d is named twice" % int(s))
+        return [(int(s), c) for s, c in items]
+
+    def push_all(self, chunks):
+        """One round: chunks maps sessions to chunks in `push`'s forms (a mapping, or a sequence of (session, chunk) pairs).  Returns
+        what `push(s, chunk)` for the sessions in ascending order returns, concatenated - see `LiveBank`."""
+        self._check_open()
+        return self._round([(s, 0, self._float_checked(c)) for s, c in self._round_items(chunks)])
+
+    def push_all_pcm(self, chunks, width):
+        """One round of PCM frames in `push_pcm`'s forms; width: bytes per sample, one int for all sessions, or one per session (a
+        mapping, or a sequence indexed by session).  Otherwise as `push_all`."""
+        self._check_open()
+        if isinstance(width, (int, np.integer)):
+            width_of = lambda s: width
+        elif hasattr(width, "items"):
+            width_of = lambda s: width[s]
+        else:
+            if len(width) != self.n_sessions:
+                raise ValueError("push_all_pcm: %d widths for %d sessions" % (len(width), self.n_sessions))
+            width_of = lambda s: width[s]
+        return self._round([(s, int(width_of(s)), self._pcm_checked(c, width_of(s))[0]) for s, c in self._round_items(chunks)])
+
+    def _sequential(self, items: list):
+        self.launches["fallback_rounds"] += 1
+        return self.concat([self.push(s, c) if kind == 0 else self.push_pcm(s, c, kind) for s, kind, c in items])
+
+    @torch.no_grad()
+    def _round(self, items: list):
+        """items: [(session, kind, checked chunk)], ascending; kind 0: float32 [C, n], else the PCM width of uint8 frames"""
+        if not items:
+            return self.concat([])
+        if any(c.is_cuda for _, _, c in items):
+            return self._sequential(items)            # device chunks are where they must be: nothing to pack
+        C = self.C
+        counts = [c.shape[1] if kind == 0 else c.numel() // (C * kind) for _, kind, c in items]
+        pushes = []
+        for (s, _, _), n in zip(items, counts):
+            if self.rs[s] is None:
+                pushes.append((s, [n]))
+            else:
+                _, L, M, half = self.rs[s]
+                pushes.append((s, [out for _, out in live_pieces(n, self.in_written[s], self.state[0][s], L, M, half, self.in_ring_len[s])]))
+        fast, steps, state, _ = bank_round(self.state, pushes, self.win_len, self.hop, self.batch, self.ring_len)
+        if not fast:
+            return self._sequential(items)
+        # ---- the fast path.  Layout of the staging buffer: push table | resample table | the chunks, each at a multiple of 16 bytes
+        write_of = {st[1]: (st[2], st[3]) for st in steps if st[0] == "write"}
+        sends = [(s, kind, c, n) for (s, kind, c), n in zip(items, counts) if self.rs[s] is not None or s in write_of]
+        n_rs = sum(1 for s in write_of if self.rs[s] is not None)
+        rs_at = len(sends) * RINGS_PUSH_DESC
+        at = -(-(rs_at + n_rs * RINGS_RS_DESC) // 16) * 16
+        offs = []
+        for s, kind, c, n in sends:
+            offs.append(at)
+            at += -(-(c.numel() * c.element_size()) // 16) * 16
+        if sends:
+            pinned = self._stage_buffer(at)
+            host = pinned.numpy()
+            push_tab, rs_tab = host[:rs_at].view(np.int64).reshape(-1, 8), host[rs_at:rs_at + n_rs * RINGS_RS_DESC]
+            k_rs = 0
+            for k, ((s, kind, c, n), off) in enumerate(zip(sends, offs)):
+                nbytes = c.numel() * c.element_size()
+                pinned[off:off + nbytes].view(c.dtype).view(c.shape).copy_(c)
+                fb = 4 if kind == 0 else C * kind                              # bytes per sample of a row / per frame
+                if self.rs[s] is None:                                         # the samples the schedule writes, into the session's ring
+                    lo, hi = write_of[s]
+                    rings_push_entry(push_tab, k, off + fb * (lo - self.state[0][s]), n, hi - lo, kind, self.chain.source[s], self.ring_len, lo)
+                    continue
+                rings_push_entry(push_tab, k, off, n, n, kind, self.in_rings[s], self.in_ring_len[s], self.in_written[s])
+                if s in write_of:                                              # and the outputs the schedule writes, out of the input ring
+                    lo, hi = write_of[s]
+                    self.det.resampler.rings_resample_plan(rs_tab, k_rs, self.in_rings[s], self.in_written[s] + n, self.rs[s][0],
+                                                           self.chain.source[s], lo, hi)
+                    k_rs += 1
+            dev = pinned[:at].to(self.det.device, non_blocking=True)
+            self._staged()
+            rings_push_into(dev, push_tab, dev, len(sends), C)
+            self.launches["rings_push"] += 1
+            if n_rs:
+                self.det.resampler.rings_resample_into(rs_tab, dev[rs_at:], n_rs, C)
+                self.launches["rings_resample"] += 1
+        for (s, _, _), n in zip(items, counts):
+            if self.rs[s] is not None:
+                self.in_written[s] += n
+        out = self._run([st for st in steps if st[0] == "run"])
+        self.state = state
+        self.launches["fast_rounds"] += 1
+        return out
 
     def step(self):
         """Runs the windows that are ready but wait for a full tick, now: one short tick (nothing with none waiting)."""
@@ -901,8 +1104,10 @@ class LiveBank(_ChunkInput):
         return self._run(steps)
 
     def flush(self):
-        """`step`, and ends all recordings: tails shorter than a window are dropped.  Afterwards a session takes pushes again only
-        behind its `reset`."""
+        """Ends all recordings: a session at another rate first produces its recording's last outputs (ascending sessions; the full
+        ticks they complete run), then `step` runs the short tick; tails shorter than a window are dropped.  Afterwards a session
+        takes pushes again only behind its `reset`."""
         self._check_open()
+        parts = [self._produce(s, True) for s in range(self.n_sessions) if self.rs[s] is not None and not self.ended[s]]
         self.ended = [True] * self.n_sessions
-        return self.step()
+        return self.concat(parts + [self.step()]) if parts else self.step()
