@@ -89,25 +89,17 @@ def live_schedule(written: int, group: int, n: int, win_len: int, hop: int, batc
     last sample is in, and a write never goes past S_g + cap for the next group g to run - the slot of sample p is that of p - cap, so
     nothing at or behind S_g, which a pending window may still need, is overwritten (cap >= span lets every group complete).  Samples
     in front of S_g are no window's any more (hop > win_len leaves such gaps between groups): they are skipped, not written.  The
-    groups and their order depend on the total pushed alone, never on how it was cut into chunks."""
-    written, group, n, hop, batch, cap = int(written), int(group), int(n), int(hop), int(batch), int(cap)
-    span = live_group_span(win_len, hop, batch)
-    if cap < span:
-        raise ValueError(f"a ring of {cap} samples is shorter than one group of {batch} windows ({span} samples)")
-    steps, end = [], written + n
-    while True:
-        start = group * batch * hop
-        while start + span <= written:
-            steps.append(("run", group))
-            group += 1
-            start += batch * hop
-        if written == end:
-            return steps, written, group
-        hi = min(end, start + cap)              # > written: the group at `start` has not run, so written < start + span <= start + cap
-        lo = max(written, start)
-        if lo < hi:
-            steps.append(("write", lo, hi))
-        written = hi
+    groups and their order depend on the total pushed alone, never on how it was cut into chunks.
+
+    This is `bank_schedule` for a bank of ONE session, whose ticks are the groups: with W complete windows at `written` the session's
+    state is (written, next window W, the FIFO of windows group * batch .. W - 1), a tick is windows w0 .. w0 + batch - 1 with w0 a
+    multiple of batch - group w0 // batch - and the first window not yet run is group * batch, so the write limit is S_g + cap."""
+    written, group, win_len, hop, batch = int(written), int(group), int(win_len), int(hop), int(batch)
+    W = 0 if written < win_len else 1 + (written - win_len) // hop
+    state = (written,), (W,), tuple((0, w) for w in range(group * batch, W))
+    steps, (done, nxt, fifo) = bank_schedule(state, 0, n, win_len, hop, batch, cap)
+    steps = [("write",) + st[2:] if st[0] == "write" else ("run", st[1][0][1] // batch) for st in steps]
+    return steps, done[0], (nxt[0] - len(fifo)) // batch
 
 
 def bank_state(n_sessions: int):

@@ -25,7 +25,10 @@ graph, and each row of a group names the session and the window it is (`mmd_mels
 `mmd_det_record_append_bank`), so one forward pass serves one fresh window of every source.  Every session of a bank may have a sample
 rate of its own (`open_bank(sample_rates=...)`: an input ring per such session, as `open_stream` keeps one), and `LiveBank.push_all`
 sends one round of chunks - one of every session - through one staging copy and one launch each of `mmd_rings_push` and
-`mmd_rings_resample`."""
+`mmd_rings_resample`.
+
+A session and a bank differ in their chains - the kernels inside the captured graph, the control row and the record's columns - and in
+nothing on the host: a session is the bank's schedule for one session, and `_LiveHost` holds the one path both push through."""
 from __future__ import annotations
 
 from types import SimpleNamespace
@@ -37,8 +40,8 @@ import torch
 from .arch import NetSpec
 from . import _lib
 from .audio import (RINGS_PUSH_DESC, RINGS_RS_DESC, MelFrontEnd, Resampler, bank_reset, bank_round, bank_schedule, bank_state, bank_step,
-                    live_group_span, live_in_ring_min, live_pieces, live_resample_ready, live_schedule, resample_ratio, rings_push_entry,
-                    rings_push_into, stream_window_starts)
+                    live_group_span, live_in_ring_min, live_pieces, live_resample_ready, resample_ratio, rings_push_entry, rings_push_into,
+                    stream_window_starts)
 from .engine import Net
 from .postproc import decode_nms, valid_class_mask
 from .store import Arena
@@ -70,10 +73,9 @@ class AudioDetector:
         self._stream: Optional["_GroupChain"] = None      # detect_stream's chain: ONE recording at a time (the graph bakes its address in)
         self.stream_captures = 0                  # graphs detect_stream captured
         self.stream_replays = 0                   # groups of windows detect_stream served by a captured graph
-        self._live: Optional["LiveSession"] = None     # open_stream's session; a stream and a session never coexist
+        self._held: Optional["_LiveHost"] = None       # open_stream's session or open_bank's bank; a stream, a session and a bank never coexist
         self.live_captures = 0                    # graphs open_stream's sessions captured
         self.live_replays = 0                     # groups of windows a session served by a captured graph
-        self._bank: Optional["LiveBank"] = None        # open_bank's bank; a stream, a session and a bank never coexist
         self.bank_captures = 0                    # graphs open_bank's banks captured
         self.bank_replays = 0                     # ticks a bank served by a captured graph
         self.resampler: Optional[Resampler] = None     # the filter banks of sessions at other rates than 44.1 kHz (made with the first)
@@ -292,14 +294,13 @@ class AudioDetector:
             raise ValueError("open_stream: track must be a TrackConfig or None")
         self._close_live()
         self._stream = None
-        self._live = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len, sample_rate, in_ring_len)
-        return self._live
+        self._held = LiveSession(self, int(win_len), int(hop), int(batch), track, ring_len, sample_rate, in_ring_len)
+        return self._held
 
     def _close_live(self):
         """closes the open session or bank, if any"""
-        for held in (self._live, self._bank):
-            if held is not None:
-                held.close()
+        if self._held is not None:
+            self._held.close()
 
     @torch.no_grad()
     def open_bank(self, n_sessions: int, win_len: int, hop: int, batch: Optional[int] = None, track: Optional[TrackConfig] = None,
@@ -321,9 +322,9 @@ class AudioDetector:
             raise ValueError("open_bank: track must be a TrackConfig or None")
         self._close_live()
         self._stream = None
-        self._bank = LiveBank(self, int(n_sessions), int(win_len), int(hop), int(n_sessions if batch is None else batch), track, ring_len,
+        self._held = LiveBank(self, int(n_sessions), int(win_len), int(hop), int(n_sessions if batch is None else batch), track, ring_len,
                               sample_rates, in_ring_len)
-        return self._bank
+        return self._held
 
 
 class _GroupChain:
@@ -339,13 +340,15 @@ class _GroupChain:
     The control row is int64 starts[batch] | int32 sess[batch] | int32 win[batch] | int32 {n_valid, pad} (`bank_control_table`), the
     tracker keeps one state per session, and the record grows by one column: rows | window | track | session | {count, overflow}."""
 
+    COLS = {"stream": 8, "live": 8, "bank": 9}        # int32 words per record row
+
     def __init__(self, det: AudioDetector, kind: str, source: torch.Tensor, ring: bool, win_len: int, batch: int, rec_cap: int,
                  track: Optional[TrackConfig], key=None):
         dev, C = det.device, det.net.spec.in_channels
         self.det, self.kind, self.source, self.ring, self.win_len, self.rec_cap, self.track, self.key = \
             det, kind, source, ring, win_len, rec_cap, track, key       # kind: "stream" / "live" / "bank", the detector's counters to bump
         self.bank = kind == "bank"
-        self.cols = 9 if self.bank else 8         # int32 words per record row
+        self.cols = self.COLS[kind]
         self.cur = torch.zeros(2 * batch + 1 if self.bank else batch + 1, dtype=torch.int64, device=dev)
         self.starts, self.ctl = self.cur[:batch], self.cur[-1:].view(torch.int32)
         if self.bank:
@@ -424,6 +427,13 @@ class _GroupChain:
             for t in self.trk_state:
                 t.zero_()
 
+    def zero_tracks(self, s: int):
+        """No tracks in session s (its ids start at 0 again), the other sessions' kept; the single-source chain has one session, its
+        whole state"""
+        if self.track is not None:
+            for t in self.trk_state:
+                (t[s] if self.bank else t).zero_()
+
     def read(self, fetch, det_overflow: int, trk_overflow: int):
         """fetch(lo, hi) -> a host copy (numpy int32 the caller does not reuse) of the record's words [lo, hi), made after the
         device finished; the two flags are the detector's and the tracker's overflow -> (rows [n, 6], window [n][, track [n]]); a
@@ -474,16 +484,95 @@ class _GroupChain:
         return table
 
 
-class _ChunkInput:
-    """What `LiveSession` and `LiveBank` share: the forms a chunk may arrive in, and the two pinned staging buffers host chunks go
-    through in turn (before a buffer is written again, the wait for the event behind the copy that last read it - two pushes back)."""
+def _plan_live(who: str, det, n_sessions: Optional[int], win_len: int, hop: int, batch: int, ring_len, sample_rates, in_ring_len):
+    """The geometry and the rates of `open_stream` (who = "open_stream", n_sessions None: ONE session, sample_rates and in_ring_len its
+    two scalars) or of `open_bank` (who = "open_bank"), checked in full before any device work.  -> (cap, rec_cap, rs, in_len): the
+    samples per ring, the rows of the record (one group), and per session (rate, L, M, half) and the samples of its input ring - None
+    for a session at 44.1 kHz."""
+    bank = n_sessions is not None
+    n = n_sessions if bank else 1
+    if n < 1 or n > 65535:
+        raise ValueError("%s: n_sessions = %d (1 .. 65535)" % (who, n))
+    if hop < 1:
+        raise ValueError("%s: hop = %d: the windows must advance by at least one sample" % (who, hop))
+    if batch < 1 or batch > 1024:
+        raise ValueError("%s: batch = %d (1 .. 1024)" % (who, batch))
+    det.front.n_frames(win_len)               # raises on a window too short for the reflect padding
+    span = live_group_span(win_len, hop, batch)
+    cap = 2 * span if ring_len is None else int(ring_len)
+    if cap < span:
+        raise ValueError("%s: ring_len = %d is shorter than one group of %d windows (%d samples)" % (who, cap, batch, span))
 
-    def _init_staging(self, det: AudioDetector, C: int):
-        self.det, self.C = det, C
+    def record():
+        rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
+        if rec_cap > 0x7fffffff // _GroupChain.COLS["bank" if bank else "live"]:
+            raise ValueError("%s: a record of %d rows" % (who, rec_cap))
+        return rec_cap
+    if bank:
+        rec_cap = record()                    # a bank sizes its record in front of its rates, a session behind them: which error wins stays
+    rates = list(sample_rates) if bank and sample_rates is not None else [sample_rates] * n
+    if len(rates) != n:
+        raise ValueError("%s: sample_rates has %d entries for %d sessions" % (who, len(rates), n))
+    listed = bank and isinstance(in_ring_len, (list, tuple))
+    in_lens = list(in_ring_len) if listed else [in_ring_len] * n
+    if len(in_lens) != n:
+        raise ValueError("%s: in_ring_len has %d entries for %d sessions" % (who, len(in_lens), n))
+    rs, in_len = [None] * n, [None] * n
+    for s, rate in enumerate(rates):
+        if rate is None or int(rate) == 44100:
+            continue
+        L, M, half = resample_ratio(int(rate))
+        least = live_in_ring_min(L, M, half)
+        in_cap = 2 * half + M - ((-cap * M) // L) if in_lens[s] is None else int(in_lens[s])      # taps + M + ceil(cap * M / L)
+        if in_cap < least:
+            raise ValueError("%s: in_ring_len = %d%s is shorter than the %d samples resampling %d Hz needs (%d taps + M = %d + 1, and no "
+                             "fewer than a block stages)" % (who, in_cap, " of session %d" % s if bank else "", least, int(rate), 2 * half, M))
+        rs[s], in_len[s] = (int(rate), L, M, half), in_cap
+    if any(k is not None and rs[s] is None for s, k in enumerate(in_lens)) and (listed or not any(rs)):
+        raise ValueError(who + (": in_ring_len goes with sessions at a sample rate other than 44100 (nothing else is resampled)" if bank else
+                                ": in_ring_len goes with a sample_rate other than 44100 (nothing is resampled)"))
+    return cap, rec_cap if bank else record(), rs, in_len
+
+
+class _LiveHost:
+    """The host side of a `LiveSession` and of a `LiveBank`, which is ONE path: a session is the bank's schedule for one session
+    (`audio.live_schedule`), on a chain of its own kind.  Here: the forms a chunk may arrive in and the two pinned staging buffers
+    host chunks go through in turn (before a buffer is written again, the wait for the event behind the copy that last read it - two
+    pushes back); the rings and, per session at another rate, the input ring and its resampling; the schedule's state
+    (`audio.bank_state`); the step loop - ring writes, and per tick one control row out of a pinned table, one replay and one drain of
+    the record.
+
+    A subclass names its chain (`kind`: "live" / "bank", `_GroupChain`'s), the int32 columns its results carry in front of the track
+    ids (`index_cols`), and turns ticks into control rows of that chain (`_control_table`)."""
+    kind, index_cols = None, 0
+
+    def _open(self, who: str, det: AudioDetector, n_sessions: Optional[int], win_len: int, hop: int, batch: int,
+              track: Optional[TrackConfig], ring_len, sample_rates, in_ring_len):
+        cap, rec_cap, rs, in_len = _plan_live(who, det, n_sessions, win_len, hop, batch, ring_len, sample_rates, in_ring_len)
+        n, C, dev = len(rs), det.net.spec.in_channels, det.device
+        self.det, self.C, self.track, self.n_sessions = det, C, track, n
+        self.win_len, self.hop, self.batch, self.ring_len = win_len, hop, batch, cap
+        self.state, self.ended, self.closed = bank_state(n), [False] * n, False       # per session: flushed, no pushes until its reset
+        self._rs, self._in_len, self._in_rings, self._in_written = rs, in_len, [None] * n, [0] * n
         self._stage = [None, None]                # pinned uint8 staging buffers of host chunks, used in turn
         self._stage_ev = [torch.cuda.Event(), torch.cuda.Event()]
         self._pushes = 0
         self.launches = {"staging_copies": 0}     # H2D copies of host chunks through the staging buffers
+        for s, r in enumerate(rs):
+            if r is not None:
+                if det.resampler is None:
+                    det.resampler = Resampler(dev)
+                det.resampler._bank(r[0], 44100)          # the filter bank goes to the device now, not in the first push
+                self._in_rings[s] = torch.zeros(C, in_len[s], device=dev)
+        # the record's host copy goes in front of the chain's buffers: allocated behind them, a push that completes a group at batch = 1
+        # took some 15 us longer in the median (profiles/live_host_path_notes.md)
+        self._h_blob = torch.zeros(_GroupChain.COLS[self.kind] * rec_cap + 2, dtype=torch.int32, pin_memory=True)
+        self._h_flags = torch.zeros(1 + 2 * n, dtype=torch.int32, pin_memory=True)       # detector overflow; per session {next_id, overflow}
+        source = torch.zeros((n, C, cap) if self.kind == "bank" else (C, cap), device=dev)
+        self._rings = list(source.unbind(0)) if self.kind == "bank" else [source]        # session s's ring
+        self.chain = chain = _GroupChain(det, self.kind, source, True, win_len, batch, rec_cap, track)
+        self._h_ctl = torch.zeros(1, chain.cur.numel(), dtype=torch.int64, pin_memory=True)
+        chain.prepare()                           # the warm-up group reads the zeroed rings: window 0 (of session 0), nothing recorded
 
     def _stage_buffer(self, nbytes: int) -> torch.Tensor:
         """the pinned staging buffer whose turn it is, at least nbytes long, free to be written; `_staged` follows its upload"""
@@ -547,8 +636,133 @@ class _ChunkInput:
         raw, fb = self._pcm_checked(raw, width)
         return (raw.contiguous() if raw.is_cuda else self._to_device(raw)), fb
 
+    # ---- state
+    def _reset(self, s: int):
+        """a new recording on session s: position, window count and input position back to 0, its queued windows dropped, its tracker
+        zeroed; open for pushes again"""
+        self.state, self.ended[s], self._in_written[s] = bank_reset(self.state, s), False, 0
+        self.chain.zero_tracks(s)
 
-class LiveSession(_ChunkInput):
+    def close(self):
+        """Releases the buffers and the graph."""
+        if not self.closed:
+            torch.cuda.synchronize()
+            self.closed = True
+            self.chain = self._h_blob = self._stage = self._rings = None
+            self._in_rings = [None] * self.n_sessions
+            if self.det._held is self:
+                self.det._held = None
+
+    # ---- ticks
+    def _drain(self):
+        """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
+        det, chain = self.det, self.chain
+        self._h_blob.copy_(chain.blob, non_blocking=True)
+        self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
+        if self.track is not None:
+            self._h_flags[1:].copy_(chain.trk_state[1].view(-1), non_blocking=True)
+        chain.rec_state.zero_()
+        torch.cuda.synchronize()
+        det.last_cls, det.last_reg = chain.cls, chain.reg
+        h = self._h_blob.numpy()
+        return chain.read(lambda lo, hi: h[lo:hi].copy(), int(self._h_flags[0]), int(self._h_flags[2::2].max()) if self.track is not None else 0)
+
+    def concat(self, parts: list):
+        """what several calls returned -> one result of the same form; no parts: the empty one"""
+        if not parts:
+            return (np.zeros((0, 6), np.float32),) + tuple(np.zeros(0, np.int32) for _ in range(self.index_cols + (self.track is not None)))
+        return tuple(parts[0]) if len(parts) == 1 else tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
+
+    def _control_table(self, runs: list, out: np.ndarray):
+        """runs: [(session, window), ...] per tick -> the control rows of this chain's kind, written into out"""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def _run(self, steps: list, write=None):
+        """the steps of `bank_schedule` / `bank_step`; write(offset into the chunk, samples, session, absolute position) queues one ring
+        write.  The control rows of a call's ticks lie in one pinned table that is only rewritten after that call's final wait."""
+        runs = [st[1] for st in steps if st[0] == "run"]
+        if self._h_ctl.shape[0] < len(runs):
+            self._h_ctl = torch.zeros(len(runs), self._h_ctl.shape[1], dtype=torch.int64, pin_memory=True)
+        table = self._h_ctl
+        if runs:                                  # most pushes complete no tick: nothing to lay out
+            self._control_table(runs, table.numpy())
+        parts, k = [], 0
+        for st in steps:
+            if st[0] == "write":
+                write(st[2], st[3] - st[2], st[1], st[2])
+            else:
+                if k:
+                    parts.append(self._drain())   # the record holds one tick
+                self.chain.run(table[k])
+                if self.kind == "bank":
+                    self.ticks.append(list(st[1]))       # a session's ticks are its groups: it keeps no list
+                k += 1
+        if k:
+            parts.append(self._drain())
+        return self.concat(parts)
+
+    def _produce(self, s: int, final: bool):
+        """session s at another rate: the 44.1 kHz samples its input so far allows (final: up to the recording's end), through the
+        schedule: every ring write is one `mmd_ring_resample` from its input ring"""
+        rate, L, M, half = self._rs[s]
+        ready = live_resample_ready(self._in_written[s], L, M, half, final)
+        steps, state = bank_schedule(self.state, s, ready - self.state[0][s], self.win_len, self.hop, self.batch, self.ring_len)
+        rs, in_ring, ring, n_valid = self.det.resampler, self._in_rings[s], self._rings[s], self._in_written[s]
+        out = self._run(steps, lambda lo, cnt, _, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
+        self.state = state
+        return out
+
+    def _advance(self, s: int, n: int, write):
+        """one chunk of n samples for session s; write(offset into the chunk, samples, ring, its length, absolute position)"""
+        if self._rs[s] is not None:
+            _, L, M, half = self._rs[s]
+            parts, off = [], 0
+            for cnt, _ in live_pieces(n, self._in_written[s], self.state[0][s], L, M, half, self._in_len[s]):
+                write(off, cnt, self._in_rings[s], self._in_len[s], self._in_written[s])
+                self._in_written[s] += cnt
+                off += cnt
+                parts.append(self._produce(s, False))
+            return self.concat(parts)
+        base, ring, cap = self.state[0][s], self._rings[s], self.ring_len
+        steps, state = bank_schedule(self.state, s, n, self.win_len, self.hop, self.batch, self.ring_len)
+        out = self._run(steps, lambda lo, cnt, _, pos: write(lo - base, cnt, ring, cap, pos))
+        self.state = state
+        return out
+
+    def _step(self):
+        """the windows that are ready but wait for a full tick, now: one short tick (nothing with none waiting)"""
+        steps, self.state = bank_step(self.state)
+        return self._run(steps)
+
+    # ---- chunks
+    def _push(self, s: int, chunk):
+        self._check_open(pushing=True, session=s)
+        chunk = self._float_chunk(chunk)
+        ptr, stride = chunk.data_ptr(), chunk.stride(0)
+        return self._advance(int(s), chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C,
+                                                                                                cnt, ring, cap, pos))
+
+    def _push_pcm(self, s: int, raw, width: int):
+        self._check_open(pushing=True, session=s)
+        raw, fb = self._pcm_chunk(raw, width)
+        width, ptr = int(width), raw.data_ptr()
+        return self._advance(int(s), raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt,
+                                                                                                   self.C, width, ring, cap, pos))
+
+    @torch.no_grad()
+    def flush(self):
+        """Ends the recording - a bank: all of them.  A session at another rate first produces its recording's last outputs (ascending
+        sessions; the full ticks they complete run); then the short last tick runs - the complete windows no full tick took, padded by
+        repeating the last one - and its results are returned; a tail shorter than a window is dropped, as `detect_stream` drops it.
+        Afterwards a session takes pushes again only behind its `reset`."""
+        self._check_open()
+        parts = [self._produce(s, True) for s in range(self.n_sessions) if self._rs[s] is not None and not self.ended[s]]
+        self.ended = [True] * self.n_sessions
+        return self.concat(parts + [self._step()]) if parts else self._step()
+
+
+class LiveSession(_LiveHost):
     """A recording that arrives in chunks (`AudioDetector.open_stream`).  `push` / `push_pcm` write a chunk into a ring of samples on the
     device and return the results of the windows the chunk COMPLETED - (rows float32 [R, 6], window int32 [R]), with tracking also
     track int32 [R], in the dtypes and order of `detect_stream` / `track_stream`; window indices count from the start of the recording
@@ -564,7 +778,9 @@ class LiveSession(_ChunkInput):
 
     The ring (`audio.live_schedule`) holds absolute sample p at slot p % ring_len.  A push alternates ring writes and group runs, and
     a write never passes the first sample of the next group to run plus ring_len, so no sample a pending window needs is overwritten
-    whatever the chunk's length - also one longer than the ring.  With hop > win_len the samples between groups are skipped.
+    whatever the chunk's length - also one longer than the ring.  With hop > win_len the samples between groups are skipped.  On the
+    host this is a `LiveBank`'s path for one session (`_LiveHost`): the groups are the ticks of `audio.bank_schedule`, the short last
+    group is `audio.bank_step`'s tick; only the chain - its kernels, its control row, its 8-word record - is the session's own.
 
     One graph of the chain ring front end -> resize -> forward -> decode -> NMS [-> track update] -> record append is captured when
     the session opens (`AudioDetector.live_captures`; with use_graph = False the chain runs eagerly); the ring, the control row and the record keep their addresses, so it serves
@@ -591,183 +807,52 @@ class LiveSession(_ChunkInput):
     `Resampler.resample(whole recording, R)` at the same settings - `mmd_ring_resample` forms the sums of `mmd_resample_poly`, and an
     output depends on its 2 * half inputs alone.  Results come `half` input samples later (1.5 ms at 48 kHz)."""
 
+    kind, index_cols = "live", 1              # the single-source chain; results (rows, window[, track])
+
     def __init__(self, det: AudioDetector, win_len: int, hop: int, batch: int, track: Optional[TrackConfig], ring_len: Optional[int],
                  sample_rate: Optional[int] = None, in_ring_len: Optional[int] = None):
-        C = det.net.spec.in_channels
-        if hop < 1:
-            raise ValueError("open_stream: hop = %d: the windows must advance by at least one sample" % hop)
-        if batch < 1 or batch > 1024:
-            raise ValueError("open_stream: batch = %d (1 .. 1024)" % batch)
-        det.front.n_frames(win_len)               # raises on a window too short for the reflect padding
-        span = live_group_span(win_len, hop, batch)
-        cap = 2 * span if ring_len is None else int(ring_len)
-        if cap < span:
-            raise ValueError("open_stream: ring_len = %d is shorter than one group of %d windows (%d samples)" % (cap, batch, span))
-        # another rate than the front end's: (rate, L, M, half) and the input ring's size, both settled before any device work
-        self.rs, self.in_ring, self.in_ring_len, self.in_written = None, None, None, 0
-        if sample_rate is not None and int(sample_rate) != 44100:
-            L, M, half = resample_ratio(int(sample_rate))
-            least = live_in_ring_min(L, M, half)
-            in_cap = 2 * half + M - ((-cap * M) // L) if in_ring_len is None else int(in_ring_len)       # taps + M + ceil(cap * M / L)
-            if in_cap < least:
-                raise ValueError("open_stream: in_ring_len = %d is shorter than the %d samples resampling %d Hz needs (%d taps + M = %d + 1, "
-                                 "and no fewer than a block stages)" % (in_cap, least, int(sample_rate), 2 * half, M))
-            self.rs, self.in_ring_len = (int(sample_rate), L, M, half), in_cap
-        elif in_ring_len is not None:
-            raise ValueError("open_stream: in_ring_len goes with a sample_rate other than 44100 (nothing is resampled)")
-        self.det, self.track, self.C, self.win_len, self.hop, self.batch, self.ring_len = det, track, C, win_len, hop, batch, cap
-        self.written, self.group, self.flushed, self.closed = 0, 0, False, False
-        dev = det.device
-        if self.rs is not None:
-            if det.resampler is None:
-                det.resampler = Resampler(dev)
-            det.resampler._bank(self.rs[0], 44100)       # the bank goes to the device now, not in the first push
-            self.in_ring = torch.zeros(C, self.in_ring_len, device=dev)
-        rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
-        if rec_cap > 0x7fffffff // 8:
-            raise ValueError("open_stream: a record of %d rows" % rec_cap)
-        self._h_blob = torch.zeros(8 * rec_cap + 2, dtype=torch.int32, pin_memory=True)      # the record's host copy
-        self._h_flags = torch.zeros(3, dtype=torch.int32, pin_memory=True)       # detector overflow; tracker {next_id, overflow}
-        self.chain = _GroupChain(det, "live", torch.zeros(C, cap, device=dev), True, win_len, batch, rec_cap, track)
-        self._h_ctl = torch.zeros(1, batch + 1, dtype=torch.int64, pin_memory=True)
-        self._init_staging(det, C)
-        self.chain.prepare()                      # the warm-up group reads the zeroed ring
+        self._open("open_stream", det, None, win_len, hop, batch, track, ring_len, sample_rate, in_ring_len)
 
-    # ---- state
-    def _check_open(self, pushing: bool = False):
+    # ---- the one session's state, as scalars: samples written, the next group to run, and what a session at another rate keeps
+    written = property(lambda self: self.state[0][0])
+    group = property(lambda self: self.state[1][0] // self.batch)     # fewer than batch windows wait: next window // batch
+    flushed = property(lambda self: self.ended[0])
+    rs = property(lambda self: self._rs[0])
+    in_ring = property(lambda self: self._in_rings[0])
+    in_ring_len = property(lambda self: self._in_len[0])
+    in_written = property(lambda self: self._in_written[0])
+
+    def _check_open(self, pushing: bool = False, session: int = 0):
         if self.closed:
             raise RuntimeError("this live session is closed (the detector holds one stream or session at a time)")
         if pushing and self.flushed:
             raise RuntimeError("the recording was flushed: reset() starts the next one")
 
+    def _control_table(self, runs: list, out: np.ndarray):
+        """a tick [(0, w0), ...] is the group of those windows: its starts, and its first window"""
+        _GroupChain.control_table([([w * self.hop for _, w in tick], tick[0][1]) for tick in runs], self.batch, out)
+
     def reset(self):
         """Starts a new recording on the same session: position 0 (the input position too), window 0, the tracker zeroed (ids start at
-        0 again); the graph, the rings and every buffer stay (they need no clearing: no window reads a slot this recording has not
-        written, and the resampler reads zeros for whatever this recording has not pushed)."""
+        0 again), the record emptied; the graph, the rings and every buffer stay (they need no clearing: no window reads a slot this
+        recording has not written, and the resampler reads zeros for whatever this recording has not pushed)."""
         self._check_open()
-        self.written, self.group, self.flushed, self.in_written = 0, 0, False, 0
-        self.chain.zero()
+        self.chain.rec_state.zero_()
+        self._reset(0)
 
-    def close(self):
-        """Releases the session's buffers and graph."""
-        if not self.closed:
-            torch.cuda.synchronize()
-            self.closed = True
-            self.chain = self._h_blob = self._stage = self.in_ring = None
-            if self.det._live is self:
-                self.det._live = None
-
-    # ---- one group
-    def _control_rows(self, rows: list) -> torch.Tensor:
-        """rows: (starts [<= batch], first_window) per group -> the pinned table, one control row per group"""
-        if self._h_ctl.shape[0] < len(rows):
-            self._h_ctl = torch.zeros(len(rows), self.batch + 1, dtype=torch.int64, pin_memory=True)
-        _GroupChain.control_table(rows, self.batch, self._h_ctl.numpy())
-        return self._h_ctl
-
-    def _drain(self):
-        """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
-        det, chain = self.det, self.chain
-        self._h_blob.copy_(chain.blob, non_blocking=True)
-        self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
-        if self.track is not None:
-            self._h_flags[1:3].copy_(chain.trk_state[1], non_blocking=True)
-        chain.rec_state.zero_()
-        torch.cuda.synchronize()
-        det.last_cls, det.last_reg = chain.cls, chain.reg
-        h = self._h_blob.numpy()
-        return chain.read(lambda lo, hi: h[lo:hi].copy(), int(self._h_flags[0]), int(self._h_flags[2]))
-
-    def concat(self, parts: list):
-        """what several pushes (and `flush`) returned -> one result of the same form; no parts: the empty one"""
-        if not parts:
-            parts = [(np.zeros((0, 6), np.float32), np.zeros(0, np.int32)) + ((np.zeros(0, np.int32),) if self.track is not None else ())]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
-
-    @torch.no_grad()
-    def _advance(self, n: int, write):
-        """the schedule of one push of n samples; write(offset into the chunk, samples, absolute position) queues one ring write"""
-        steps, written, group = live_schedule(self.written, self.group, n, self.win_len, self.hop, self.batch, self.ring_len)
-        runs = [s[1] for s in steps if s[0] == "run"]
-        table = self._control_rows([([(gi * self.batch + i) * self.hop for i in range(self.batch)], gi * self.batch) for gi in runs])
-        parts, k = [], 0
-        for st in steps:
-            if st[0] == "write":
-                write(st[1] - self.written, st[2] - st[1], st[1])
-            else:
-                if k:
-                    parts.append(self._drain())   # the record holds one group
-                self.chain.run(table[k])
-                k += 1
-        self.written, self.group = written, group
-        if k:
-            parts.append(self._drain())
-        return self.concat(parts)
-
-    def _produce(self, final: bool):
-        """the 44.1 kHz samples the input pushed so far allows (final: up to the recording's end), through the schedule: every ring write
-        is one `mmd_ring_resample` from the input ring"""
-        rate, L, M, half = self.rs
-        ready = live_resample_ready(self.in_written, L, M, half, final)
-        if ready == self.written:
-            return self.concat([])
-        rs, in_ring, ring, n_valid = self.det.resampler, self.in_ring, self.chain.source, self.in_written
-        return self._advance(ready - self.written, lambda off, cnt, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
-
-    def _feed(self, n: int, write):
-        """one chunk of n samples; write(offset into the chunk, samples, ring, its length, absolute position) queues one ring write"""
-        if self.rs is None:
-            ring, cap = self.chain.source, self.ring_len
-            return self._advance(n, lambda off, cnt, pos: write(off, cnt, ring, cap, pos))
-        _, L, M, half = self.rs
-        piece, parts = self.in_ring_len - 2 * half - M, []       # the oldest input a pending output needs survives the piece
-        for off in range(0, n, piece):
-            cnt = min(piece, n - off)
-            write(off, cnt, self.in_ring, self.in_ring_len, self.in_written)
-            self.in_written += cnt
-            parts.append(self._produce(False))
-        return self.concat(parts)
-
-    # ---- chunks
     def push(self, chunk):
         """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of every microphone (at the
         session's sample_rate)"""
-        self._check_open(pushing=True)
-        chunk = self._float_chunk(chunk)
-        ptr, stride = chunk.data_ptr(), chunk.stride(0)
-        return self._feed(chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C, cnt,
-                                                                                     ring, cap, pos))
+        return self._push(0, chunk)
 
     def push_pcm(self, raw, width: int):
         """raw: bytes, a bytearray or a uint8 tensor (host or device) of whole frames of interleaved little-endian signed PCM, 8 channels
         of `width` = 2, 3 or 4 bytes, as `wave.readframes` returns them; decoded on the device exactly as `Resampler.pcm_to_float`
         decodes (`mmd_ring_push_pcm`).  Otherwise as `push`."""
-        self._check_open(pushing=True)
-        raw, fb = self._pcm_chunk(raw, width)
-        width, ptr = int(width), raw.data_ptr()
-        return self._feed(raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt, self.C,
-                                                                                        width, ring, cap, pos))
-
-    @torch.no_grad()
-    def flush(self):
-        """Ends the recording: runs the last, shorter group - the complete windows no full group took, padded by repeating the last one
-        - and returns its results; a tail shorter than a window is dropped, as `detect_stream` drops it.  A resampling session first
-        produces the recording's last outputs (and runs the full groups they complete).  Afterwards only `reset` or `close`."""
-        self._check_open()
-        if self.flushed:
-            return self.concat([])
-        self.flushed = True
-        parts = [self._produce(True)] if self.rs is not None else []
-        W = 0 if self.written < self.win_len else 1 + (self.written - self.win_len) // self.hop
-        first = self.group * self.batch
-        if W > first:
-            table = self._control_rows([([w * self.hop for w in range(first, W)], first)])
-            self.chain.run(table[0])
-            parts.append(self._drain())
-        return self.concat(parts)
+        return self._push_pcm(0, raw, width)
 
 
-class LiveBank(_ChunkInput):
+class LiveBank(_LiveHost):
     """Several recordings that arrive in chunks, side by side (`AudioDetector.open_bank`): n_sessions rings [n_sessions, 8, ring_len]
     and n_sessions trackers behind ONE chain and one captured graph.  `push(s, chunk)` / `push_pcm(s, raw, width)` write a chunk of
     session s into its ring (the argument forms of `LiveSession`; at 44.1 kHz unless the session was opened at another rate, below)
@@ -829,61 +914,20 @@ class LiveBank(_ChunkInput):
     drain per tick.  Any other round - and any round with a device-tensor chunk - is the sequential pushes.  `launches` counts
     "fast_rounds", "fallback_rounds", "rings_push", "rings_resample" (the batched launches) and "staging_copies"."""
 
+    kind, index_cols = "bank", 2              # the chain of several sources; results (rows, session, window[, track])
+
     def __init__(self, det: AudioDetector, n_sessions: int, win_len: int, hop: int, batch: int, track: Optional[TrackConfig],
                  ring_len: Optional[int], sample_rates: Optional[Sequence] = None, in_ring_len=None):
-        C = det.net.spec.in_channels
-        if n_sessions < 1 or n_sessions > 65535:
-            raise ValueError("open_bank: n_sessions = %d (1 .. 65535)" % n_sessions)
-        if hop < 1:
-            raise ValueError("open_bank: hop = %d: the windows must advance by at least one sample" % hop)
-        if batch < 1 or batch > 1024:
-            raise ValueError("open_bank: batch = %d (1 .. 1024)" % batch)
-        det.front.n_frames(win_len)               # raises on a window too short for the reflect padding
-        span = live_group_span(win_len, hop, batch)
-        cap = 2 * span if ring_len is None else int(ring_len)
-        if cap < span:
-            raise ValueError("open_bank: ring_len = %d is shorter than one group of %d windows (%d samples)" % (cap, batch, span))
-        rec_cap = batch * (det.cand_cap if det.cand_cap > 0 else det.STREAM_ROWS_PER_WINDOW)
-        if rec_cap > 0x7fffffff // 9:
-            raise ValueError("open_bank: a record of %d rows" % rec_cap)
-        # sessions at other rates than the front end's: (rate, L, M, half) and the input ring's size, settled before any device work
-        rates = [None] * n_sessions if sample_rates is None else list(sample_rates)
-        if len(rates) != n_sessions:
-            raise ValueError("open_bank: sample_rates has %d entries for %d sessions" % (len(rates), n_sessions))
-        in_lens = list(in_ring_len) if isinstance(in_ring_len, (list, tuple)) else [in_ring_len] * n_sessions
-        if len(in_lens) != n_sessions:
-            raise ValueError("open_bank: in_ring_len has %d entries for %d sessions" % (len(in_lens), n_sessions))
-        self.rs, self.in_ring_len, self.in_rings, self.in_written = [None] * n_sessions, [None] * n_sessions, [None] * n_sessions, [0] * n_sessions
-        for s, rate in enumerate(rates):
-            if rate is None or int(rate) == 44100:
-                continue
-            L, M, half = resample_ratio(int(rate))
-            least = live_in_ring_min(L, M, half)
-            in_cap = 2 * half + M - ((-cap * M) // L) if in_lens[s] is None else int(in_lens[s])      # taps + M + ceil(cap * M / L)
-            if in_cap < least:
-                raise ValueError("open_bank: in_ring_len = %d of session %d is shorter than the %d samples resampling %d Hz needs (%d taps "
-                                 "+ M = %d + 1, and no fewer than a block stages)" % (in_cap, s, least, int(rate), 2 * half, M))
-            self.rs[s], self.in_ring_len[s] = (int(rate), L, M, half), in_cap
-        if any(n is not None and self.rs[s] is None for s, n in enumerate(in_lens)) and \
-                (isinstance(in_ring_len, (list, tuple)) or not any(self.rs)):
-            raise ValueError("open_bank: in_ring_len goes with sessions at a sample rate other than 44100 (nothing else is resampled)")
-        self.track, self.n_sessions, self.win_len, self.hop, self.batch, self.ring_len = track, n_sessions, win_len, hop, batch, cap
-        self.state, self.ticks, self.ended, self.closed = bank_state(n_sessions), [], [False] * n_sessions, False
-        self._init_staging(det, C)
+        self.ticks = []
+        self._open("open_bank", det, n_sessions, win_len, hop, batch, track, ring_len, sample_rates, in_ring_len)
         self.launches.update(fast_rounds=0, fallback_rounds=0, rings_push=0, rings_resample=0)
-        for s, rs in enumerate(self.rs):
-            if rs is not None:
-                if det.resampler is None:
-                    det.resampler = Resampler(det.device)
-                det.resampler._bank(rs[0], 44100)         # the bank goes to the device now, not in the first push
-                self.in_rings[s] = torch.zeros(C, self.in_ring_len[s], device=det.device)
-        self._h_blob = torch.zeros(9 * rec_cap + 2, dtype=torch.int32, pin_memory=True)      # the record's host copy
-        self._h_flags = torch.zeros(1 + 2 * n_sessions, dtype=torch.int32, pin_memory=True)  # detector overflow; per session {next_id, overflow}
-        self._h_ctl = torch.zeros(1, 2 * batch + 1, dtype=torch.int64, pin_memory=True)
-        self.chain = _GroupChain(det, "bank", torch.zeros(n_sessions, C, cap, device=det.device), True, win_len, batch, rec_cap, track)
-        self.chain.prepare()                      # the warm-up tick reads the zeroed rings: session 0, window 0, nothing recorded
 
-    # ---- state
+    # ---- per session: (rate, L, M, half), the input ring, its length - None at 44.1 kHz - and the input samples pushed so far
+    rs = property(lambda self: self._rs)
+    in_rings = property(lambda self: self._in_rings)
+    in_ring_len = property(lambda self: self._in_len)
+    in_written = property(lambda self: self._in_written)
+
     def _check_open(self, pushing: bool = False, session: Optional[int] = None):
         if self.closed:
             raise RuntimeError("this live bank is closed (the detector holds one stream, session or bank at a time)")
@@ -892,113 +936,30 @@ class LiveBank(_ChunkInput):
         if pushing and self.ended[session]:
             raise RuntimeError("the recordings were flushed: reset(%d) starts the next one on this session" % session)
 
+    def _control_table(self, runs: list, out: np.ndarray):
+        _GroupChain.bank_control_table(runs, self.batch, self.hop, out)
+
     def reset(self, s: int):
         """Starts a new recording on session s: its position and window count back to 0, its tracker zeroed (ids start at 0 again),
         its queued windows dropped, its input position (a session at another rate) back to 0; the other sessions, the graph, the rings
         and every buffer stay.  After a `flush` it reopens session s alone for pushes."""
         self._check_open(session=s)
-        self.state, self.ended[int(s)], self.in_written[int(s)] = bank_reset(self.state, int(s)), False, 0
-        if self.track is not None:
-            for t in self.chain.trk_state:
-                t[int(s)].zero_()
+        self._reset(int(s))
 
-    def close(self):
-        """Releases the bank's buffers and graph."""
-        if not self.closed:
-            torch.cuda.synchronize()
-            self.closed = True
-            self.chain = self._h_blob = self._stage = None
-            self.in_rings = [None] * self.n_sessions
-            if self.det._bank is self:
-                self.det._bank = None
-
-    # ---- ticks
-    def _drain(self):
-        """Waits for the device once, behind one copy of the record and the overflow flags; -> the record's arrays, the record emptied"""
-        det, chain = self.det, self.chain
-        self._h_blob.copy_(chain.blob, non_blocking=True)
-        self._h_flags[0:1].copy_(det.overflow, non_blocking=True)
-        if self.track is not None:
-            self._h_flags[1:].copy_(chain.trk_state[1].view(-1), non_blocking=True)
-        chain.rec_state.zero_()
-        torch.cuda.synchronize()
-        det.last_cls, det.last_reg = chain.cls, chain.reg
-        h = self._h_blob.numpy()
-        return chain.read(lambda lo, hi: h[lo:hi].copy(), int(self._h_flags[0]), int(self._h_flags[2::2].max()) if self.track is not None else 0)
-
-    def concat(self, parts: list):
-        """what several calls returned -> one result of the same form; no parts: the empty one"""
-        if not parts:
-            parts = [(np.zeros((0, 6), np.float32),) + (np.zeros(0, np.int32),) * (3 if self.track is not None else 2)]
-        return tuple(np.concatenate([p[i] for p in parts]) for i in range(len(parts[0])))
-
-    @torch.no_grad()
-    def _run(self, steps: list, write=None):
-        """the steps of `bank_schedule` / `bank_step`; write(offset into the chunk, samples, session, absolute position) queues one ring write"""
-        runs = [st[1] for st in steps if st[0] == "run"]
-        if self._h_ctl.shape[0] < len(runs):
-            self._h_ctl = torch.zeros(len(runs), 2 * self.batch + 1, dtype=torch.int64, pin_memory=True)
-        table = self._h_ctl
-        _GroupChain.bank_control_table(runs, self.batch, self.hop, table.numpy())
-        parts, k = [], 0
-        for st in steps:
-            if st[0] == "write":
-                write(st[2], st[3] - st[2], st[1], st[2])
-            else:
-                if k:
-                    parts.append(self._drain())   # the record holds one tick
-                self.chain.run(table[k])
-                self.ticks.append(list(st[1]))
-                k += 1
-        if k:
-            parts.append(self._drain())
-        return self.concat(parts)
-
-    def _produce(self, s: int, final: bool):
-        """session s at another rate: the 44.1 kHz samples its input so far allows (final: up to the recording's end), through the
-        schedule: every ring write is one `mmd_ring_resample` from its input ring"""
-        rate, L, M, half = self.rs[s]
-        ready = live_resample_ready(self.in_written[s], L, M, half, final)
-        steps, state = bank_schedule(self.state, s, ready - self.state[0][s], self.win_len, self.hop, self.batch, self.ring_len)
-        rs, in_ring, ring, n_valid = self.det.resampler, self.in_rings[s], self.chain.source[s], self.in_written[s]
-        out = self._run(steps, lambda lo, cnt, _, pos: rs.ring_resample_into(in_ring, n_valid, rate, ring, pos, pos + cnt))
-        self.state = state
-        return out
-
-    def _advance(self, s: int, n: int, write):
-        """one chunk of n samples for session s; write(offset into the chunk, samples, ring, its length, absolute position)"""
-        if self.rs[s] is not None:
-            _, L, M, half = self.rs[s]
-            parts, off = [], 0
-            for cnt, _ in live_pieces(n, self.in_written[s], self.state[0][s], L, M, half, self.in_ring_len[s]):
-                write(off, cnt, self.in_rings[s], self.in_ring_len[s], self.in_written[s])
-                self.in_written[s] += cnt
-                off += cnt
-                parts.append(self._produce(s, False))
-            return self.concat(parts)
-        base, ring, cap = self.state[0][s], self.chain.source[s], self.ring_len
-        steps, state = bank_schedule(self.state, s, n, self.win_len, self.hop, self.batch, self.ring_len)
-        out = self._run(steps, lambda lo, cnt, _, pos: write(lo - base, cnt, ring, cap, pos))
-        self.state = state
-        return out
+    def step(self):
+        """Runs the windows that are ready but wait for a full tick, now: one short tick (nothing with none waiting)."""
+        self._check_open()
+        return self._step()
 
     # ---- chunks
     def push(self, s: int, chunk):
         """chunk: float32 [8, n], n >= 1, a device or host tensor or a numpy array: the next n samples of session s (at 44.1 kHz, or at
         the rate the session was opened with)"""
-        self._check_open(pushing=True, session=s)
-        chunk = self._float_chunk(chunk)
-        ptr, stride = chunk.data_ptr(), chunk.stride(0)
-        return self._advance(int(s), chunk.shape[1], lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push", ptr + 4 * off, stride, self.C,
-                                                                                                cnt, ring, cap, pos))
+        return self._push(s, chunk)
 
     def push_pcm(self, s: int, raw, width: int):
         """raw: whole frames of interleaved little-endian signed PCM of session s, as `LiveSession.push_pcm` takes them"""
-        self._check_open(pushing=True, session=s)
-        raw, fb = self._pcm_chunk(raw, width)
-        width, ptr = int(width), raw.data_ptr()
-        return self._advance(int(s), raw.numel() // fb, lambda off, cnt, ring, cap, pos: _lib.call("mmd_ring_push_pcm", ptr + fb * off, cnt,
-                                                                                                   self.C, width, ring, cap, pos))
+        return self._push_pcm(s, raw, width)
 
     # ---- a round of chunks
     def _round_items(self, chunks) -> list:
@@ -1097,17 +1058,3 @@ class LiveBank(_ChunkInput):
         self.launches["fast_rounds"] += 1
         return out
 
-    def step(self):
-        """Runs the windows that are ready but wait for a full tick, now: one short tick (nothing with none waiting)."""
-        self._check_open()
-        steps, self.state = bank_step(self.state)
-        return self._run(steps)
-
-    def flush(self):
-        """Ends all recordings: a session at another rate first produces its recording's last outputs (ascending sessions; the full
-        ticks they complete run), then `step` runs the short tick; tails shorter than a window are dropped.  Afterwards a session
-        takes pushes again only behind its `reset`."""
-        self._check_open()
-        parts = [self._produce(s, True) for s in range(self.n_sessions) if self.rs[s] is not None and not self.ended[s]]
-        self.ended = [True] * self.n_sessions
-        return self.concat(parts + [self.step()]) if parts else self.step()

@@ -358,7 +358,7 @@ def test_a_group_runs_with_its_last_sample():
     _same(session.push(w[:, SPAN - 1:SPAN]), first)                               # the next sample brings them
     assert all(len(x) == 0 for x in session.push(w[:, SPAN:SPAN + 1]))
     session.close()
-    assert det._live is None
+    assert det._held is None
     with pytest.raises(ValueError, match="ring_len = %d is shorter" % (SPAN - 1)):
         det.open_stream(WIN, HOP, batch=BATCH, ring_len=SPAN - 1)
 
@@ -377,7 +377,7 @@ def test_session_without_a_graph_runs_the_same_chain():
     # a stream on the same detector closes the session
     w = _recording(11).to(DEV)
     _same(det.track_stream(w, WIN, HOP, batch=BATCH, track=_track_config()), want)
-    assert session.closed and det._live is None
+    assert session.closed and det._held is None
 
 
 # ---------------------------------------------------------------------------------------------- detect.py --chunk_s

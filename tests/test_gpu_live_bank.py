@@ -252,17 +252,17 @@ def test_one_stream_session_or_bank_at_a_time_and_a_record_too_small():
     det = _detector()
     bank = det.open_bank(NS, WIN, HOP)
     session = det.open_stream(WIN, HOP, batch=BATCH)
-    assert bank.closed and det._bank is None and det._live is session
+    assert bank.closed and det._held is session
     with pytest.raises(RuntimeError, match="closed"):
         bank.push(0, _quantised(0)[1][:, :100])
     bank = det.open_bank(NS, WIN, HOP, batch=2)
-    assert session.closed and det._live is None and det._bank is bank and bank.batch == 2
+    assert session.closed and det._held is bank and bank.batch == 2
     with pytest.raises(RuntimeError, match="closed"):
         session.push(_quantised(0)[1][:, :100])
     with pytest.raises(ValueError, match="session 3"):
         bank.push(3, _quantised(0)[1][:, :100])
     det.detect_stream(_quantised(0)[1].to(DEV), WIN, HOP, batch=BATCH)
-    assert bank.closed and det._bank is None
+    assert bank.closed and det._held is None
     with pytest.raises(ValueError, match="ring_len = %d is shorter" % (SPAN - 1)):
         det.open_bank(NS, WIN, HOP, ring_len=SPAN - 1)
     with pytest.raises(ValueError, match="n_sessions"):

@@ -207,3 +207,115 @@ def test_schedule_over_random_chunkings():
             p = np.arange(w * hop, w * hop + win_len)
             assert np.array_equal(slot[p % cap], p), (trial, "flush", w)
     assert ran_any > 300 and gaps > 20 and long_chunks > 50                           # the cases were really met
+
+
+# ---------------------------------------------------------------------------------------------- one scheduler, one planning function
+def _live_schedule_model(written, group, n, win_len, hop, batch, cap):
+    """the loop `audio.live_schedule` was before it became `audio.bank_schedule` for one session, kept here as the model"""
+    span = (batch - 1) * hop + win_len
+    steps, end = [], written + n
+    while True:
+        start = group * batch * hop
+        while start + span <= written:
+            steps.append(("run", group))
+            group += 1
+            start += batch * hop
+        if written == end:
+            return steps, written, group
+        hi = min(end, start + cap)
+        lo = max(written, start)
+        if lo < hi:
+            steps.append(("write", lo, hi))
+        written = hi
+
+
+def test_live_schedule_is_the_bank_schedule_of_one_session():
+    """The whole lattice of geometries - win_len x hop (also > win_len) x batch (also 1) x ring (also exactly one span) - each with a
+    seeded chain of up to 8 pushes of 1 .. 3 * cap + 5 samples: `live_schedule` gives the model's steps and (written, group); a bank
+    of one session, chained on its own state, gives the same steps read as the session's; its state after every push is the one
+    `live_schedule` rebuilds from (written, group) - the FIFO is windows group * batch .. W - 1 - and `bank_step` runs exactly those."""
+    from mm_distillnet_amd.audio import bank_schedule, bank_state, bank_step, live_group_span, live_schedule
+    rng = np.random.default_rng(18165)
+    pushes = tight = gapped = single = long_chunks = short_groups = 0
+    for win_len in (5, 8, 13, 40):
+        for hop in (1, 3, 8, 13, 50, 97):
+            for batch in (1, 2, 3, 5):
+                span = live_group_span(win_len, hop, batch)
+                for extra in (0, 1, 7, span, 3 * span):
+                    cap = span + extra
+                    written, group, state = 0, 0, bank_state(1)
+                    for k in range(int(rng.integers(2, 9))):
+                        # every other push anywhere in 1 .. 3 * cap + 5, the others short: they end inside a group, or bring no window
+                        n = int(rng.integers(1, 3 * cap + 6)) if k % 2 else int(rng.integers(1, 2 * hop + win_len + 1))
+                        want = _live_schedule_model(written, group, n, win_len, hop, batch, cap)
+                        assert live_schedule(written, group, n, win_len, hop, batch, cap) == want, (win_len, hop, batch, cap, written, group, n)
+                        steps, state = bank_schedule(state, 0, n, win_len, hop, batch, cap)
+                        for st in steps:
+                            if st[0] == "run":            # a tick is one group: batch consecutive windows from a multiple of batch
+                                w0 = st[1][0][1]
+                                assert w0 % batch == 0 and list(st[1]) == [(0, w0 + i) for i in range(batch)]
+                        read = [("write", st[2], st[3]) if st[0] == "write" else ("run", st[1][0][1] // batch) for st in steps]
+                        assert read == want[0]
+                        _, written, group = want
+                        W = 0 if written < win_len else 1 + (written - win_len) // hop
+                        waiting = [(0, w) for w in range(group * batch, W)]
+                        assert state == ((written,), (W,), tuple(waiting)) and len(waiting) < batch
+                        last, after = bank_step(state)
+                        assert last == ([("run", waiting)] if waiting else []) and after == ((written,), (W,), ())
+                        pushes += 1
+                        tight += extra == 0
+                        gapped += hop > win_len
+                        single += batch == 1
+                        long_chunks += n > cap
+                        short_groups += bool(waiting)
+    assert pushes > 2000 and min(tight, gapped, single, long_chunks, short_groups) > 100       # no case was left out
+
+
+def test_one_planning_function_words_both_openings():
+    """`_plan_live` refuses for `open_stream` and for `open_bank` in the words each had when it checked for itself (the strings below
+    are copied from those two constructors), and plans the same geometry for a session as for a bank of that one session."""
+    from types import SimpleNamespace as NS
+    from mm_distillnet_amd.detector import _plan_live
+    det = NS(net=NS(spec=NS(in_channels=8)), front=NS(n_frames=lambda n: 1 + n // 256), cand_cap=0, STREAM_ROWS_PER_WINDOW=256)
+
+    def refused(text, who, n_sessions, hop=1531, batch=3, ring_len=None, rates=None, in_ring_len=None):
+        with pytest.raises(ValueError) as e:
+            _plan_live(who, det, n_sessions, 4096, hop, batch, ring_len, rates, in_ring_len)
+        assert str(e.value) == text
+
+    for who, n in (("open_stream", None), ("open_bank", 3)):
+        refused(who + ": hop = 0: the windows must advance by at least one sample", who, n, hop=0)
+        refused(who + ": batch = 0 (1 .. 1024)", who, n, batch=0)
+        refused(who + ": batch = 1025 (1 .. 1024)", who, n, batch=1025)
+        refused(who + ": ring_len = 7157 is shorter than one group of 3 windows (7158 samples)", who, n, ring_len=7157)
+    refused("open_bank: n_sessions = 0 (1 .. 65535)", "open_bank", 0)
+    refused("open_bank: n_sessions = 65536 (1 .. 65535)", "open_bank", 65536)
+    # an input ring too short
+    refused("open_stream: in_ring_len = 300 is shorter than the 301 samples resampling 48000 Hz needs (140 taps + M = 160 + 1, and no fewer "
+            "than a block stages)", "open_stream", None, rates=48000, in_ring_len=300)
+    refused("open_bank: in_ring_len = 300 of session 2 is shorter than the 301 samples resampling 48000 Hz needs (140 taps + M = 160 + 1, and "
+            "no fewer than a block stages)", "open_bank", 3, rates=[16000, None, 48000], in_ring_len=[5000, None, 300])
+    refused("open_bank: in_ring_len = 1198 of session 0 is shorter than the 1199 samples resampling 192000 Hz needs (558 taps + M = 640 + 1, and "
+            "no fewer than a block stages)", "open_bank", 3, rates=[192000, None, None], in_ring_len=1198)
+    # an input ring where nothing is resampled
+    refused("open_stream: in_ring_len goes with a sample_rate other than 44100 (nothing is resampled)", "open_stream", None, in_ring_len=5000)
+    refused("open_stream: in_ring_len goes with a sample_rate other than 44100 (nothing is resampled)", "open_stream", None, rates=44100,
+            in_ring_len=5000)
+    bank_text = "open_bank: in_ring_len goes with sessions at a sample rate other than 44100 (nothing else is resampled)"
+    refused(bank_text, "open_bank", 3, in_ring_len=5000)
+    refused(bank_text, "open_bank", 3, rates=[44100, None, 44100], in_ring_len=5000)
+    refused(bank_text, "open_bank", 3, rates=[48000, None, 44100], in_ring_len=[5000, 5000, None])
+    # lists of another length than the bank
+    refused("open_bank: sample_rates has 2 entries for 3 sessions", "open_bank", 3, rates=[48000, None])
+    refused("open_bank: in_ring_len has 2 entries for 3 sessions", "open_bank", 3, rates=[48000, None, 44100], in_ring_len=[5000, None])
+    # which error wins: the ring in front of the rates, the rates' lengths in front of the ratio, the ratio in front of the input ring
+    refused("open_bank: ring_len = 7157 is shorter than one group of 3 windows (7158 samples)", "open_bank", 3, ring_len=7157, rates=[48000])
+    refused("open_stream: ring_len = 7157 is shorter than one group of 3 windows (7158 samples)", "open_stream", None, ring_len=7157,
+            rates=48000, in_ring_len=300)
+    with pytest.raises(ValueError, match="44100 / 44101"):
+        _plan_live("open_bank", det, 3, 4096, 1531, 3, None, [44101, None, 48000], 300)
+    # and what is planned: a session is the bank of that one session, but for its 8-word record's limit
+    one = _plan_live("open_stream", det, None, 4096, 1531, 3, None, 48000, None)
+    assert one == _plan_live("open_bank", det, 1, 4096, 1531, 3, None, [48000], None)
+    assert one == (2 * 7158, 3 * 256, [(48000, 147, 160, 70)], [140 + 160 - ((-2 * 7158 * 160) // 147)])
+    assert _plan_live("open_bank", det, 2, 4096, 1531, 3, 7158, [None, 44100], None) == (7158, 768, [None, None], [None, None])
