@@ -528,6 +528,22 @@ int mmd_image_minmax(const void* src, int dtype, long long n, float lo, float hi
 // dst[C,S,S] = letterbox(bilinear((pre(src)*scale - mean)/std)); pre = clamp + round((v-min)*255/(max-min)) when minmax != 0.
 int mmd_image_letterbox(const void* src, int dtype, int H, int W, int C, float scale, const float* mean, const float* stdv, int minmax, float lo, float hi, const float* mm, int common_size, float* dst, hipStream_t stream);
 
+// The training-time augmentations in front of mmd_image_letterbox, for a stacked batch of one modality in ONE launch (the sample index in
+// the grid): the 2-pixel column shift (src/datasets/MultimodalDetection.py:236-242,320-327) and HSVAdjust (src/datasets/transformations.py:133-190).
+// src[B,H,W,C]: C = 3 uint8, or C = 1 uint16 (thermal: minmax / lo / hi as in mmd_image_letterbox, mm[B,2] = every sample's
+// mmd_image_minmax of its UNSHIFTED frame) -> dst[B,C,S,S].  Row b of aug[B,5] (device) = (on, hue_deg, sat, val, shift_px):
+//   shift_px > 0: source pixel (y, x) reads (y, x + shift_px) for x < W - shift_px and is 0 otherwise (0 in the stretched frame, as
+//                 upstream shifts after the thermal stretch); index math, no shifted frame is written.
+//   hsv != 0 and on != 0 (C = 3 only): per source pixel, before the bilinear taps: rgb/255 -> HSV, h += hue_deg wrapped into [0, 360),
+//                 s = clip(sat*s, 0, 1), v = clip(val*v, 0, 1), HSV -> RGB, *255 without rounding; then (v*scale - mean)/std and the letterbox.
+//   hsv == 0: the `on` column is ignored, so ONE table serves all modalities of a sample (as one HSVAdjust.__call__ draws once) and the
+//                 thermal launch takes its shift from it.  hsv != 0 with C = 1: -22 (upstream's HSVAdjust fails on the 2-D thermal frame).
+// cv2.cvtColor is restated from OpenCV's documented float formulas: parity with cv2 itself is UNPINNED, the kernel is held to
+// tests/hsv_ref.py.  A sample whose row has on == 0 (or hsv == 0) and shift_px == 0 gets exactly the bits of mmd_image_letterbox.
+// -22 before any launch: null src / aug / dst (mm with minmax), B, H, W or common_size < 1 (B, common_size > 65535), C not in {1, 3},
+// minmax with C = 3.
+int mmd_image_letterbox_aug_batch(const void* src, int B, int H, int W, int C, float scale, const float* mean, const float* stdv, int minmax, float lo, float hi, const float* mm, const float* aug, int hsv, int common_size, float* dst, hipStream_t stream);
+
 // Resizer's audio branch: cv2.resize(INTER_CUBIC) of an [h,w,C] spectrogram stack to [C,S,S] (transformations.py:435-441).
 int mmd_resize_cubic(const float* src, int h, int w, int C, int common_size, float* dst, hipStream_t stream);
 

@@ -6,6 +6,8 @@ label, id).  The real corpus and its cv2/librosa pipeline are outside the hot pa
 this dataset produces tensors with the same shapes / statistics so train.py and evaluate.py run end to end."""
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 from torch.utils.data import Dataset
 
@@ -181,17 +183,63 @@ def collate_raw(batch):
     return batch
 
 
+@dataclass(frozen=True)
+class AugmentSettings:
+    """What DeviceInputPipeline augments with: `hsv` = the reference's HSVAdjust (cfg train_transformations), `shift` = its 2-pixel column
+    shift (cfg data_augment_shift), `seed` = the seed of the pipeline's own numpy Generator (train.py: cfg seed + rank)."""
+    hsv: bool = False
+    shift: bool = False
+    seed: int = 0
+
+
+def draw_augment(rng, n: int, hsv: bool, shift: bool):
+    """The augmentation table of n samples, float32 numpy [n, 5] with rows (on, hue_deg, sat, val, shift_px), drawn on the host from the
+    numpy.random.Generator `rng` by the reference's rules (HSVAdjust.__call__, src/datasets/transformations.py:151-157;
+    MultimodalDetection.__getitem__, src/datasets/MultimodalDetection.py:236).  Per sample, in this fixed order:
+      with hsv:    hue ~ U(-30, 30); sat ~ U(1, 1.5); sat's coin ~ U(0, 1), >= 0.5 -> sat = 1/sat; val ~ U(1, 1.5); val's coin, the same rule
+      with shift:  shift's coin ~ U(0, 1), > 0.5 -> shift_px = 2, else 0
+    A transform that is off draws nothing and leaves its columns neutral (on = 0, hue = 0, sat = val = 1; shift_px = 0).  One row serves
+    all modalities of its sample, as one HSVAdjust.__call__ draws once for rgb, thermal and depth."""
+    import numpy as np
+    tab = np.zeros((n, 5), dtype=np.float32)
+    tab[:, 2:4] = 1.0
+    for i in range(n):
+        if hsv:
+            hue = rng.uniform(-30.0, 30.0)
+            sat = rng.uniform(1.0, 1.5)
+            if rng.uniform(0.0, 1.0) >= 0.5:
+                sat = 1.0 / sat
+            val = rng.uniform(1.0, 1.5)
+            if rng.uniform(0.0, 1.0) >= 0.5:
+                val = 1.0 / val
+            tab[i, :4] = (1.0, hue, sat, val)
+        if shift and rng.uniform(0.0, 1.0) > 0.5:
+            tab[i, 4] = 2.0
+    return tab
+
+
 class DeviceInputPipeline:
     """The reference's Normalizer + Resizer + HWC->CHW (+ thermal clamp/stretch) on the GPU (csrc/input.hip): raw frames are
     staged in pinned memory, copied on a dedicated stream and transformed there, so H2D and preprocessing of batch n+1
     overlap the step of batch n; `wait()` orders the compute stream after the batch is ready.  Replaces the per-sample
-    cv2 work of `MultimodalDetection.__getitem__` + `Resizer` (src/datasets/transformations.py:407-467)."""
+    cv2 work of `MultimodalDetection.__getitem__` + `Resizer` (src/datasets/transformations.py:407-467).
+
+    `augment` (an AugmentSettings; None = no augmentation, and submit issues exactly the launches it issues without the argument): every
+    submit draws one table row per sample (`draw_augment`), uploads it with the batch's staging copies and sends rgb, depth and thermal
+    through mmd_image_letterbox_aug_batch - one launch per modality for a stacked batch, B = 1 launches for a list of per-sample dicts.
+    HSVAdjust applies to the 3-channel modalities (rgb, depth) only; thermal takes the shift alone: the reference's HSVAdjust hands
+    cv2.cvtColor the 2-D thermal frame and fails there, so it has no thermal behaviour to restate.  Audio is never augmented here."""
 
     MEAN = (0.485, 0.456, 0.406)
     STD = (0.229, 0.224, 0.225)
 
-    def __init__(self, image_size: int, device, ir_min: float = 20800.0, ir_max: float = 27000.0, audio_db: bool = False):
+    def __init__(self, image_size: int, device, ir_min: float = 20800.0, ir_max: float = 27000.0, audio_db: bool = False,
+                 augment: AugmentSettings | None = None):
         from . import _lib
+        self.augment = augment
+        if augment is not None:
+            import numpy as np
+            self._rng = np.random.default_rng(int(augment.seed))
         self.audio_db = bool(audio_db)      # cfg audio_db: "audio_wave" samples become dB maps before the resize; "audio" stacks are untouched
         self.call = _lib.call
         self.S = int(image_size)
@@ -219,12 +267,38 @@ class DeviceInputPipeline:
         p.copy_(t)         # (a host copy on the calling thread: ~0.6 ms per 0.5 MB frame - 20 ms for a batch of 8 x 4 pageable tensors)
         return p.to(self.device, non_blocking=True)
 
-    def submit(self, samples):
+    def _augmented(self, tab, B, rgb, depth, thermal, mm, out, b=None):
+        """rgb / depth / thermal of a stacked batch (b None: [B,H,W,C] frames, rows 0..B of the device table `tab`) or of sample b of a list
+        (B = 1) through mmd_image_letterbox_aug_batch: HSV + shift for the colour frames, shift alone for thermal (hsv = 0 ignores `on`)."""
+        S, call = self.S, self.call
+        sel = (lambda t: t) if b is None else (lambda t: t[b:b + 1])
+        H, W = rgb.shape[-3:-1]
+        call("mmd_image_letterbox_aug_batch", rgb, B, H, W, 3, 1.0 / 255.0, self.mean, self.std, 0, 0.0, 0.0, None, sel(tab), 1, S,
+             sel(out["rgb"]))
+        H, W = depth.shape[-3:-1]
+        call("mmd_image_letterbox_aug_batch", depth, B, H, W, 3, 1.0 / 255.0, None, None, 0, 0.0, 0.0, None, sel(tab), 1, S,
+             sel(out["depth"]))
+        H, W = thermal.shape[-2:]
+        for i in range(B):          # the stretch's (min, max) is per frame, of the UNSHIFTED frame (upstream stretches, then shifts)
+            call("mmd_image_minmax", thermal if b is not None else thermal[i], 1, H * W, self.ir[0], self.ir[1], sel(mm)[i])
+        call("mmd_image_letterbox_aug_batch", thermal, B, H, W, 1, 1.0 / 255.0, None, None, 1, self.ir[0], self.ir[1], sel(mm), sel(tab),
+             0, S, sel(out["thermal"]))
+
+    def submit(self, samples, aug=None):
         """samples: list of per-sample dicts from RawSyntheticMultimodalDetection (or a real decoder with the same raw formats), or the
         stacked dict `collate_raw` makes of them.  A sample's audio is either "audio" [h,w,8] (ready-made mel stack: resized) or
-        "audio_wave" [8,N] (waveforms: mel spectrogram - in dB with audio_db -, then resized: `Audio2Spectogram` + `Resizer` on this stream)."""
+        "audio_wave" [8,N] (waveforms: mel spectrogram - in dB with audio_db -, then resized: `Audio2Spectogram` + `Resizer` on this stream).
+        aug: a caller-supplied augmentation table (float32 [B, 5], rows as `draw_augment` makes them) instead of this submit's draw, for
+        tests and reproducible runs; it is honoured with or without the constructor's `augment`."""
         stacked = isinstance(samples, dict)
         B, S, call = (samples["rgb"].shape[0] if stacked else len(samples)), self.S, self.call
+        table = None
+        if aug is not None:
+            table = torch.as_tensor(aug, dtype=torch.float32).contiguous()
+            if tuple(table.shape) != (B, 5):
+                raise ValueError(f"aug must be [{B}, 5] (on, hue_deg, sat, val, shift_px), got {tuple(table.shape)}")
+        elif self.augment is not None:
+            table = torch.from_numpy(draw_augment(self._rng, B, self.augment.hsv, self.augment.shift))
         if self._front is None and ("audio_wave" in samples if stacked else any("audio_wave" in smp for smp in samples)):
             from .audio import MelFrontEnd
             self._front = MelFrontEnd(self.device)
@@ -241,19 +315,26 @@ class DeviceInputPipeline:
             if stacked:
                 keys = raw_keys(samples)
                 whole = {k: self._stage((k, "batch"), samples[k]) for k in keys}
+            tab = self._stage(("aug", "batch"), table) if table is not None else None      # travels with the batch's staging copies
+            if tab is not None and stacked:
+                self._augmented(tab, B, whole["rgb"], whole["depth"], whole["thermal"], mm, out)      # one launch per modality
             for b in range(B):
                 if stacked:
                     smp, stage = {k: whole[k][b] for k in keys}, (lambda key, t: t)
                 else:
                     smp, stage = samples[b], self._stage
-                rgb = stage(("rgb", b), smp["rgb"]); H, W = rgb.shape[:2]
-                call("mmd_image_letterbox", rgb, 0, H, W, 3, 1.0 / 255.0, self.mean, self.std, 0, 0.0, 0.0, None, S, out["rgb"][b])
-                d = stage(("depth", b), smp["depth"]); H, W = d.shape[:2]
-                call("mmd_image_letterbox", d, 0, H, W, 3, 1.0 / 255.0, None, None, 0, 0.0, 0.0, None, S, out["depth"][b])
-                t = stage(("thermal", b), smp["thermal"]); H, W = t.shape[:2]
-                call("mmd_image_minmax", t, 1, H * W, self.ir[0], self.ir[1], mm[b])
-                call("mmd_image_letterbox", t, 1, H, W, 1, 1.0 / 255.0, None, None, 1, self.ir[0], self.ir[1], mm[b], S,
-                     out["thermal"][b])
+                if tab is None:
+                    rgb = stage(("rgb", b), smp["rgb"]); H, W = rgb.shape[:2]
+                    call("mmd_image_letterbox", rgb, 0, H, W, 3, 1.0 / 255.0, self.mean, self.std, 0, 0.0, 0.0, None, S, out["rgb"][b])
+                    d = stage(("depth", b), smp["depth"]); H, W = d.shape[:2]
+                    call("mmd_image_letterbox", d, 0, H, W, 3, 1.0 / 255.0, None, None, 0, 0.0, 0.0, None, S, out["depth"][b])
+                    t = stage(("thermal", b), smp["thermal"]); H, W = t.shape[:2]
+                    call("mmd_image_minmax", t, 1, H * W, self.ir[0], self.ir[1], mm[b])
+                    call("mmd_image_letterbox", t, 1, H, W, 1, 1.0 / 255.0, None, None, 1, self.ir[0], self.ir[1], mm[b], S,
+                         out["thermal"][b])
+                elif not stacked:       # mixed frame sizes: the same entry point, one sample per launch
+                    self._augmented(tab, 1, stage(("rgb", b), smp["rgb"]), stage(("depth", b), smp["depth"]),
+                                    stage(("thermal", b), smp["thermal"]), mm, out, b)
                 if "audio_wave" in smp:
                     a = self._front.melspec(stage(("audio_wave", b), smp["audio_wave"])[None], db=self.audio_db)[0]
                 else:

@@ -36,7 +36,7 @@ sys.path.insert(0, ROOT)
 
 from mm_distillnet_amd.arch import make_spec  # noqa: E402
 from mm_distillnet_amd.data import (SyntheticMultimodalDetection, RawSyntheticMultimodalDetection, DeviceInputPipeline, TensorInputPipeline,  # noqa: E402
-                                    CachedBatches, collate, collate_raw, valid_classes_dict)
+                                    AugmentSettings, CachedBatches, cfg_bool, collate, collate_raw, valid_classes_dict)
 from mm_distillnet_amd import _lib  # noqa: E402
 from mm_distillnet_amd import trainer as TR  # noqa: E402
 from mm_distillnet_amd.model import filter_state_dict, loss_names_from_config  # noqa: E402
@@ -99,6 +99,36 @@ def step_config(cfg) -> StepConfig:
                       # extension key (absent from the reference's cfg files -> fp32): "bf16" = 1x1 convs on the bf16 MFMA
                       precision=cfg.get("precision", "fp32"), seed=cfg.getint("seed", 24),
                       **TR.optimizer_settings(cfg))
+
+
+def augment_from_config(cfg, raw: bool, rank: int = 0):
+    """cfg train_transformations / data_augment_shift -> the AugmentSettings of the training DeviceInputPipeline, or None (both keys absent:
+    `Normalizer,Resizer` and no shift, which is what the pipeline does without them).  The names are split and matched as upstream's
+    facade does (src/utils/utils.py:1449-1471: split(','), no stripping, `No valid transformation {trans} provided` for anything else).
+    Of upstream's names the raw pipeline runs HSVAdjust, Normalizer and Resizer; the draw seed is the cfg seed + rank."""
+    names = cfg.get("train_transformations", "Normalizer,Resizer").split(",")
+    for trans in names:
+        if trans in ("HSVAdjust", "Resizer", "Normalizer"):
+            continue
+        if trans == "Resize":
+            raise Exception("train_transformations: Resize (fixed per-modality sizes) is not available; the shipped recipe uses Resizer")
+        if trans == "ThermalAugmenter":
+            raise Exception("train_transformations: ThermalAugmenter is not available (it needs albumentations)")
+        if trans == "AudioAugmenter":
+            raise Exception("train_transformations: AudioAugmenter is not available (upstream's only live choice in it is None)")
+        raise Exception(f"No valid transformation {trans} provided")
+    hsv = "HSVAdjust" in names
+    if [t for t in names if t != "HSVAdjust"] != ["Normalizer", "Resizer"] or names.count("HSVAdjust") > 1 or (hsv and names[0] != "HSVAdjust"):
+        raise Exception(f"Unsupported train_transformations {','.join(names)} provided: the input pipeline applies "
+                        "[HSVAdjust,]Normalizer,Resizer, in this order")
+    shift = cfg_bool(cfg, "data_augment_shift", False)
+    if (hsv or shift) and not raw:
+        raise Exception("%s needs input_pipeline = raw: the augmentations run on the GPU in DeviceInputPipeline, and the tensor path "
+                        "receives ready-made tensors" % " and ".join(n for n, on in (("train_transformations = HSVAdjust", hsv),
+                                                                                      ("data_augment_shift = True", shift)) if on))
+    if not (hsv or shift):
+        return None
+    return AugmentSettings(hsv=hsv, shift=shift, seed=int(cfg.get("seed", 24)) + int(rank))
 
 
 def load_states(cfg, coef=2):
@@ -181,6 +211,10 @@ def main(argv=None):
         dist.init_process_group("nccl", rank=rank, world_size=world)
     torch.manual_seed(cfg.getint("seed", 24))
     scfg = step_config(cfg)                      # raises on an unsupported train_method / optimizer, like upstream
+    # train_transformations / data_augment_shift (upstream keys, absent -> Normalizer,Resizer / off): HSVAdjust and the 2-pixel column shift
+    # of the TRAINING pipeline (input_pipeline = raw); the validation pipeline never augments (upstream's val_transformations carry neither).
+    # Read here, before any weights load, so that a name the pipeline cannot run ends the job at once
+    augment = augment_from_config(cfg, cfg.get("input_pipeline", "tensor") == "raw", rank)
     sspec, sstate, tspecs, tstates = load_states(cfg, int(cfg.get("compound_coef", 2)))
     if cfg.getint("synthetic_teacher_candidates", 0) > 0:
         # extension key (synthetic stand-in teachers only): shift each teacher's classifier bias so that about this many candidates per
@@ -210,7 +244,7 @@ def main(argv=None):
     train_set, val_set = Set(cfg, "train"), Set(cfg, "val")
     # audio_db (extension key, absent -> False; with audio_format = waveform): the pipeline hands the student dB mel maps, not power
     audio_db = cfg.getboolean("audio_db", False)
-    pipe = DeviceInputPipeline(cfg.getint("image_size"), dev, audio_db=audio_db) if raw else TensorInputPipeline(dev)
+    pipe = DeviceInputPipeline(cfg.getint("image_size"), dev, audio_db=audio_db, augment=augment) if raw else TensorInputPipeline(dev)
     vpipe = DeviceInputPipeline(cfg.getint("image_size"), dev, audio_db=audio_db) if raw else None
     collate_fn = collate_raw if raw else collate
     sampler = torch.utils.data.distributed.DistributedSampler(train_set, num_replicas=world, rank=rank) if world > 1 else None
