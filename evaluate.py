@@ -54,9 +54,10 @@ def main(argv=None):
     mods = [m for m in ("rgb", "depth", "thermal") if cfg.getboolean(f"use_{m}", True)]
     modality = "ALL" if len(mods) == 3 else ",".join(mods)
     mode = cfg.get("eval_metrics", "host")      # host until the device path is timed against it: profiles/eval_metrics_notes.md
-    if mode not in ("device", "host"):
-        raise Exception(f"Unsupported eval_metrics {mode} (device | host)")
-    if mode == "device":
+    if mode not in ("device", "device_table", "host"):
+        raise Exception(f"Unsupported eval_metrics {mode} (device | device_table | host)")
+    per_class = None
+    if mode in ("device", "device_table"):
         # the matching and the central distances run on the device behind every batch (csrc/evalstats.hip): no per-batch synchronize,
         # the record is copied once, at the end.  Record capacity: cfg eval_record_rows (predictions of images with ground truth, and
         # ground-truth boxes, over the whole test set); exceeded -> end_eval raises, nothing is truncated silently
@@ -66,7 +67,13 @@ def main(argv=None):
             eng.eval_batch({"rgb": rgb.to(dev), "thermal": thermal.to(dev), "depth": depth.to(dev), "audio": audio.to(dev)})
             if i % 64 == 63:
                 eng.check_overflow()      # a record that is too small ends the run here, not after the last batch
-        table = table_from_stats(eng.end_eval(), cfg.getint("image_size"))
+        if mode == "device_table":
+            # the table too is computed on the device, on the record where it lies (csrc/evaltable.hip): what comes back is the row below
+            # and the per-class table upstream logs at IoU 0.5 (src/utils/utils.py:1393-1401); equal scores rank in record order
+            table = eng.end_eval_table(cfg.getint("image_size"))
+            per_class = table.pop("per_class")
+        else:
+            table = table_from_stats(eng.end_eval(), cfg.getint("image_size"))
     else:
         # get_predictions_multiteacher (src/utils/utils.py:1720-1830): per batch the student's detections and the merged teacher
         # pseudo ground truth, plus the flat list of ground-truth class ids
@@ -79,6 +86,10 @@ def main(argv=None):
         eng.check_overflow()
         table = evaluate_table(all_pred, all_lab, labels, cfg.getint("image_size"))
     print({k: round(v, 3) for k, v in table.items()})
+    if per_class is not None:
+        print("%8s %10s %10s %10s %10s" % ("class", "precision", "recal", "AP", "F1"))
+        for c, _, _, p, r, ap, f1 in per_class:
+            print("%8d %10.4f %10.4f %10.4f %10.4f" % (int(c), p, r, ap, f1))
     if os.path.exists(cfg["exp_name"]):
         import pandas as pd
         pd.DataFrame([dict(exp_name=cfg["exp_name"], modality=modality, **table)]).to_csv(

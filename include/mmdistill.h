@@ -359,6 +359,48 @@ int mmd_eval_ws_floats(int cap, int G);
 // Counts up to which mmd_eval_match keeps an image in LDS: which = 0 predictions, 1 boxes.
 int mmd_eval_lds_cap(int which);
 
+// ---- stable device-wide sort and the AP / CD table of an evaluation record (csrc/evaltable.hip)
+// Items one block of the sort handles (a multiple of 64); block boundaries fall at its multiples.
+int mmd_sort_tile(void);
+
+// Bytes of mmd_sort_desc_f32's `ws` for n keys (monotone in n, never 0).  -22 for n < 0, n >= 2^31 or a size that does not fit an int.
+int mmd_sort_desc_ws_bytes(long long n);
+
+// Stable descending sort of n float32 keys, optionally grouped by a small integer class: perm_out[0..n) = the input indices ordered by
+// class ascending (when cls is given), then key descending, then index ascending - np.lexsort((arange(n), -key, cls)) with -0.0 equal
+// to +0.0, +-inf as numbers and every NaN key behind all others of its class, in input order.  key and cls are not modified.
+// cls [n] (or NULL): integers 0 .. 255 stored as float; any other value -> *status |= 1 (sticky; the caller zeroes it) and the order of
+// perm_out is unspecified (it still holds in-range indices).
+// LSD radix sort, 8-bit digits, four passes over the key and one over the class, three launches per pass (per-block counts, a one-block
+// scan, a stable scatter); every dependency between blocks is a kernel boundary.  ws: mmd_sort_desc_ws_bytes(n) bytes, 16-byte aligned,
+// needs no zeroing.
+// Null ws / status, null key / perm_out with n > 0, a misaligned pointer, n < 0 or n >= 2^31 -> -22, nothing is launched; n == 0
+// succeeds without a launch.
+int mmd_sort_desc_f32(const float* key, const float* cls, long long n, int* perm_out, void* ws, int* status, hipStream_t stream);
+
+// Bytes of mmd_eval_table's `ws` (monotone in n_rows, never 0).  -22 for a negative count, a count >= 2^31 or a size that does not fit an int.
+int mmd_eval_table_ws_bytes(long long n_rows, long long n_gt);
+
+// The AP / CD table of an evaluation record (mmd_eval_match's layout; the counts are the cursor values the host has read):
+// metrics.table_from_stats with predictions of equal score ranked in record order (the stable order of mmd_sort_desc_f32, cls = class).
+// In: score_label [n_rows, 2] (score, class), tp [n_rows] (bit k: true positive at threshold k), cd [n_img, 3] (sum dx, sum dy,
+// n_boxes), gt [n_gt] ground-truth classes.  Per ground-truth class c with n_c boxes and IoU threshold k, over the class's predictions
+// by rank i: hits_i = true positives up to i, p_i = hits_i / (i + 1), r_i = hits_i / (n_c + 1e-16),
+// AP = sum over the true positives of (r_i - r_(i-1)) * max_(j >= i) p_j, all in float64; a ground-truth class without predictions
+// scores 0, a predicted class without ground truth is ignored.
+// out double[16 + 256 * 8], every element written:
+//   [0..8] mean AP over the ground-truth classes per threshold (fractions); [9..13] AP@Ave, AP@0.5, AP@0.75, CDx, CDy in percent;
+//   [14] number of ground-truth classes; [15] 0;
+//   [16 + 8 c ..] class c = 0 .. 255: present (0 / 1), n_gt, n_pred, precision, recall, AP, F1 at threshold 0, and a spare 0; all
+//   zero for a class the ground truth does not hold.
+// CDx / CDy: over the images with n_boxes > 0 the float32 quotient sum / n_boxes / image_size, averaged in float64.
+// n_rows == 0: the ten APs are 0 and CDx = CDy = 100 * 100 (the reference's sentinel row).  n_rows > 0 without ground truth: NaN APs,
+// as the host's empty mean.
+// A class in gt or score_label that is not an integer 0 .. 255 -> *status |= 1 (sticky; the caller zeroes it), out is then unspecified.
+// ws: mmd_eval_table_ws_bytes bytes, 16-byte aligned, needs no zeroing.  Null out / ws / status, a null array with a count > 0, a
+// misaligned pointer or a negative count -> -22, nothing is launched.
+int mmd_eval_table(const float* score_label, const int* tp, long long n_rows, const float* cd, long long n_img, const float* gt, long long n_gt, float image_size, double* out, void* ws, int* status, hipStream_t stream);
+
 // Profiling hooks for bench.py (hipEvents on the launch stream).
 int mmd_prof_is_on(int family);
 

@@ -222,6 +222,64 @@ def table_from_stats(stats: dict, image_size: int) -> dict:
     return out
 
 
+# ---- the table on the device (csrc/evaltable.hip) --------------------------------------------------------------------------------------
+TABLE_OUT = 16 + 256 * 8          # doubles of mmd_eval_table's `out`
+
+
+def sort_desc_device(key, cls=None):
+    """mmd_sort_desc_f32: key float32 [n] (device), cls float32 [n] of integers 0 .. 255 or None -> int32 [n] (device), the indices by
+    class ascending, key descending (-0 = +0, NaN last), index ascending.  Raises on a class outside 0 .. 255."""
+    import torch
+    from . import _lib
+    n = int(key.numel())
+    nb = int(_lib.LIB.load().mmd_sort_desc_ws_bytes(n))
+    if nb < 0:
+        raise RuntimeError(f"mmd_sort_desc_ws_bytes({n}) failed with status {nb}")
+    ws = torch.empty(nb, dtype=torch.uint8, device=key.device)
+    status = torch.zeros(1, dtype=torch.int32, device=key.device)
+    perm = torch.empty(n, dtype=torch.int32, device=key.device)
+    _lib.call("mmd_sort_desc_f32", key, cls, n, perm, ws, status)
+    if int(status.item()):
+        raise RuntimeError("mmd_sort_desc_f32: a class is not an integer in 0 .. 255")
+    return perm
+
+
+def table_on_device(rows, tp, n_rows: int, cd, n_img: int, gt, n_gt: int, image_size) -> dict:
+    """mmd_eval_table on record buffers that lie on the device (rows float32 [>= n_rows, 2] (score, class), tp int32, cd float32
+    [>= n_img, 3], gt float32): table_from_stats's dict, predictions of equal score ranked in record order, plus "per_class": float64
+    [n_classes, 7] rows (class, n_gt, n_pred, precision, recall, AP, F1) at IoU 0.5 in rising class order.  One launch sequence, one
+    copy of 2064 doubles."""
+    import torch
+    from . import _lib
+    nb = int(_lib.LIB.load().mmd_eval_table_ws_bytes(n_rows, n_gt))
+    if nb < 0:
+        raise RuntimeError(f"mmd_eval_table_ws_bytes({n_rows}, {n_gt}) failed with status {nb}")
+    dev = rows.device
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(TABLE_OUT, dtype=torch.float64, device=dev)
+    _lib.call("mmd_eval_table", rows if n_rows else None, tp if n_rows else None, n_rows, cd if n_img else None, n_img,
+              gt if n_gt else None, n_gt, float(image_size), out, ws, status)
+    o = out.cpu().numpy()
+    if int(status.item()):
+        raise RuntimeError("mmd_eval_table: a class label of the record is not an integer in the label range 0 .. 255")
+    per = o[16:].reshape(256, 8)
+    ids = np.flatnonzero(per[:, 0] > 0)
+    return {"AP@Ave": float(o[9]), "AP@0.5": float(o[10]), "AP@0.75": float(o[11]), "CDx": float(o[12]), "CDy": float(o[13]),
+            "per_class": np.concatenate([ids[:, None].astype(np.float64), per[ids, 1:7]], axis=1)}
+
+
+def table_from_record_device(stats: dict, image_size: int, device="cuda") -> dict:
+    """table_on_device for a record that lies on the host (DistillEngine.end_eval's dict, or stats_from_lists): upload, launch, read."""
+    import torch
+    sc, lb = np.asarray(stats["score"], np.float32).reshape(-1), np.asarray(stats["label"], np.float32).reshape(-1)
+    rows = torch.from_numpy(np.ascontiguousarray(np.stack([sc, lb], axis=1))).to(device)
+    tp = torch.from_numpy(np.ascontiguousarray(np.asarray(stats["tp"]).reshape(-1).astype(np.int32))).to(device)
+    cd = torch.from_numpy(np.ascontiguousarray(np.asarray(stats["cd"], np.float32).reshape(-1, 3))).to(device)
+    gt = torch.from_numpy(np.ascontiguousarray(np.asarray(stats["gt"], np.float32).reshape(-1))).to(device)
+    return table_on_device(rows, tp, rows.shape[0], cd, cd.shape[0], gt, gt.shape[0], image_size)
+
+
 def ap_table(all_predictions: List, all_labels: List, image_size: int = 512) -> dict:
     """Flat per-image lists -> evaluate_table (one batch)."""
     labels = [float(r[4]) for t in all_labels for r in _rows(t, 5)]

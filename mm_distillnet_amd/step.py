@@ -698,20 +698,39 @@ class DistillEngine:
         predictions in image order, cd float32 [images, 3] (sum dx, sum dy, n_boxes), gt float32 [m] ground-truth classes.  The 4-int
         header is read first (the one synchronize of the evaluation), then only the rows in front of the cursor are copied: the
         traffic follows the data, not the capacity.  Raises when the record (or a pseudo-label array, check_overflow) was too small."""
+        return self._record_to_host(*self._close_eval("end_eval"))
+
+    def _close_eval(self, who: str):
+        """Ends the evaluation: -> (record, rows, images, classes) behind the cursor, after the overflow checks."""
         ev = self._eval
         if ev is None:
-            raise RuntimeError("end_eval without begin_eval")
+            raise RuntimeError(f"{who} without begin_eval")
         self._eval = None
         if int(ev["overflow"].item()):
             raise RuntimeError("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
                                % (ev["max_images"], ev["max_rows"], ev["max_gt"]))
         self.check_overflow()
         nr, ni, ng = (int(v) for v in ev["cursor"].cpu().tolist())
+        return ev, nr, ni, ng
+
+    @staticmethod
+    def _record_to_host(ev, nr, ni, ng) -> dict:
         tp = ev["tp"][:nr].cpu().numpy()
         rows = ev["rows"][:2 * nr].cpu().numpy().reshape(-1, 2)
         cd = ev["cd"][:3 * ni].cpu().numpy().reshape(-1, 3)
         gt = ev["gt"][:ng].cpu().numpy()
         return {"score": rows[:, 0].copy(), "label": rows[:, 1].copy(), "tp": tp, "cd": cd, "gt": gt}
+
+    def end_eval_table(self, image_size, with_record: bool = False):
+        """end_eval + metrics.table_from_stats without the bulk copy: the same header read and the same raises, then the AP / CD table is
+        computed on the record where it lies (csrc/evaltable.hip, metrics.table_on_device) and 2064 doubles come back.  -> the table's
+        dict plus "per_class" [n_classes, 7] (class, n_gt, n_pred, precision, recall, AP, F1 at IoU 0.5); predictions of equal score
+        rank in record order.  with_record: -> (table, the dict end_eval would have returned).  Raises RuntimeError on a class label
+        outside the label range 0 .. 255."""
+        from .metrics import table_on_device
+        ev, nr, ni, ng = self._close_eval("end_eval_table")
+        table = table_on_device(ev["rows"], ev["tp"], nr, ev["cd"], ni, ev["gt"], ng, image_size)
+        return (table, self._record_to_host(ev, nr, ni, ng)) if with_record else table
 
     @torch.no_grad()
     def eval_losses(self, batch: Dict[str, torch.Tensor], teacher_labels: Optional[List[tuple]] = None):
