@@ -58,12 +58,13 @@ as its chunks arrive).  The files are read round by round, round(chunk_s * R) fr
 round is ONE `LiveBank.push_all_pcm`: one staging copy and one launch for the ring writes of all sessions, one for their resampling.  The
 CSV has the same columns; window counts and times are those of the ceil(N * 44100 / R) resampled samples, in seconds of the recording.
 A `.npy` is refused under --any_rate (it holds no rate).
+
+The files are read by `mm_distillnet_amd.recording`: `read_input` and `read_recording` a whole file, `open_chunks` a chunk at a time.
 """
 import argparse
 import csv
 import os
 import sys
-import wave
 
 import numpy as np
 
@@ -76,310 +77,79 @@ sys.path.insert(0, ROOT)
 
 import train as T  # noqa: E402
 from mm_distillnet_amd.detector import AudioDetector  # noqa: E402
+from mm_distillnet_amd.recording import CHANNELS, SAMPLE_RATE, open_chunks, read_input, read_npy, read_recording  # noqa: E402
 
-CHANNELS, SAMPLE_RATE = 8, 44100
+DEVICE = "cuda:0"
 COLUMNS = ("clip", "x1", "y1", "x2", "y2", "score", "label")
 STREAM_COLUMNS = ("window", "t_start_s", "x1", "y1", "x2", "y2", "score", "label")
-TRACK_COLUMNS = STREAM_COLUMNS + ("track",)
 BANK_COLUMNS = ("session",) + STREAM_COLUMNS
+INPUT_44K = "a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz"
+LIVE_FEED = "feeds a live session that slides a window over the recording"
 
 
-def read_npy(path: str) -> np.ndarray:
-    a = np.load(path, allow_pickle=False)
-    if a.dtype != np.float32:
-        raise ValueError(f"{path}: waveforms must be float32, found {a.dtype}")
-    if a.ndim == 2:
-        a = a[None]
-    if a.ndim != 3 or a.shape[1] != CHANNELS:
-        raise ValueError(f"{path}: expected [{CHANNELS}, N] or [B, {CHANNELS}, N] waveforms, found shape {a.shape}")
-    return np.ascontiguousarray(a)
+# ---------------------------------------------------------------------------------------------- flags
+def check_flags(a):
+    """Every refusal that the flags alone decide, before a file is opened or the device touched.  Where several apply, the first one
+    below wins."""
+    several = len(a.inputs) > 1
 
+    def ext(path):
+        return os.path.splitext(path)[1].lower()
 
-def _check_wav(path: str, w, any_rate: bool):
-    """The header rules of an open `wave` reader -> (bytes per sample, rate in Hz).  any_rate False: 8 channels of 16-bit PCM at 44.1 kHz,
-    what the front end takes as it is; True: 8 channels of 16-, 24- or 32-bit PCM at any rate, what the device decodes and resamples."""
-    width, rate, channels = w.getsampwidth(), w.getframerate(), w.getnchannels()
-    if not any_rate and rate != SAMPLE_RATE:
-        raise ValueError(f"{path}: sample rate {rate} Hz is not supported (the front end is built for {SAMPLE_RATE} Hz; resample first)")
-    if w.getcomptype() != "NONE" or width not in ((2, 3, 4) if any_rate else (2,)):
-        bits = "16-, 24- or 32-bit" if any_rate else "16-bit"
-        raise ValueError(f"{path}: only {bits} PCM is supported, found {8 * width}-bit {w.getcomptype()}")
-    if channels != CHANNELS:
-        raise ValueError(f"{path}: expected {CHANNELS} microphone channels, found {channels}")
-    if rate < 1:
-        raise ValueError(f"{path}: sample rate {rate} Hz")
-    return width, rate
+    def needs_window(flag, why):
+        if a.window_s is None:
+            raise ValueError(f"{flag} {why}: it needs --window_s")
 
+    def not_with_rates(who, why, live_too=True):
+        if a.resample or a.sample_rate is not None or (live_too and a.live_s is not None):
+            raise ValueError(f"{who} not go with --resample / --sample_rate{' / --live_s' if live_too else ''}: {why}")
 
-def _wav_chunks(w, chunk: int, width: int):
-    """(raw whole frames, bytes per sample) of an open `wave` reader, `chunk` frames at a time; closes the reader behind the last"""
-    with w:
-        while True:
-            raw = w.readframes(chunk)
-            if len(raw) < width * CHANNELS:
-                return
-            yield raw[:len(raw) - len(raw) % (width * CHANNELS)], width
+    def positive_seconds(flag, seconds, rate, unit):
+        """rate: Hz, at which `seconds` must hold one sample at least; None: only the sign is known yet"""
+        if not seconds > 0 or (rate is not None and int(round(seconds * rate)) < 1):
+            raise ValueError(f"{flag} {seconds}: a positive number of seconds (at least one {unit})")
 
+    def supported(path, what):
+        if ext(path) not in (".npy", ".wav"):
+            raise ValueError(f"{path}: unsupported input ({what})")
 
-def read_wav(path: str) -> np.ndarray:
-    with wave.open(path, "rb") as w:
-        _check_wav(path, w, any_rate=False)
-        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, CHANNELS)
-    return np.ascontiguousarray((pcm.astype(np.float32) / np.float32(32768.0)).T)[None]
-
-
-def read_input(path: str) -> np.ndarray:
-    """-> float32 [B, 8, N]"""
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".npy":
-        return read_npy(path)
-    if ext == ".wav":
-        return read_wav(path)
-    raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
-
-
-def read_recording(path: str):
-    """A PCM `.wav` of 8 channels at ANY rate, 16-, 24- or 32-bit -> (its frames as a uint8 array, just as they are in the file:
-    interleaved little-endian signed samples; frames; channels; bytes per sample; rate in Hz).  Nothing is decoded on the host:
-    `Resampler.pcm_to_float` and `Resampler.resample` take it from there (--resample)."""
-    with wave.open(path, "rb") as w:
-        width, rate = _check_wav(path, w, any_rate=True)
-        raw = np.frombuffer(w.readframes(w.getnframes()), dtype=np.uint8)
-    frames = raw.size // (CHANNELS * width)
-    if frames < 1:
-        raise ValueError(f"{path}: no frames")
-    return raw[:frames * CHANNELS * width].copy(), frames, CHANNELS, width, rate
-
-
-def load_resampled(a, dev):
-    """--resample / --sample_rate: -> float32 DEVICE waveforms [B, 8, N] at 44.1 kHz"""
-    from mm_distillnet_amd.audio import Resampler
-    ext = os.path.splitext(a.input)[1].lower()
-    if a.resample:
-        if ext != ".wav" or a.sample_rate is not None:
-            raise ValueError(f"{a.input}: --resample reads a .wav, whose header holds the rate (for a .npy give --sample_rate R alone)")
-        raw, frames, channels, width, rate = read_recording(a.input)
-        rs = Resampler(dev)
-        wav = rs.pcm_to_float(torch.from_numpy(raw).to(dev), frames, channels, width)[None]
-    else:
-        if ext != ".npy":
-            raise ValueError(f"{a.input}: --sample_rate R says at which rate a .npy was recorded (a .wav holds its rate: --resample)")
-        if a.sample_rate < 1:
-            raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
-        rs = Resampler(dev)
-        wav, rate = torch.from_numpy(read_npy(a.input)).to(dev), a.sample_rate
-    return rs.resample(wav, rate, SAMPLE_RATE)
-
-
-def write_csv(path: str, rows_per_clip) -> int:
-    n = 0
-    with open(path, "w", newline="") as f:
-        out = csv.writer(f)
-        out.writerow(COLUMNS)
-        for clip, rows in enumerate(rows_per_clip):
-            for r in np.asarray(rows, np.float32).reshape(-1, 6):
-                out.writerow([clip] + ["%.9g" % float(v) for v in r])      # 9 digits: float32 round-trips
-                n += 1
-    return n
-
-
-def _write_windows_csv(path: str, columns, rows, window, hop: int, track=None) -> int:
-    """one row per box: window, its start in seconds, the box[, its track id]"""
-    rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
-    last = [[]] * len(rows)
-    if track is not None:
-        track = np.asarray(track).reshape(-1)
-        if len(track) != len(rows) or len(window) != len(rows):
-            raise ValueError("write_track_csv: %d rows, %d windows, %d track ids" % (len(rows), len(window), len(track)))
-        last = [[t] for t in track.tolist()]
-    with open(path, "w", newline="") as f:
-        out = csv.writer(f)
-        out.writerow(columns)
-        for w, r, t in zip(window.tolist(), rows, last):
-            out.writerow([w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + t)
-    return len(rows)
-
-
-def write_stream_csv(path: str, rows, window, hop: int) -> int:
-    """rows [R, 6] / window [R] of `AudioDetector.detect_stream` at a hop of `hop` samples"""
-    return _write_windows_csv(path, STREAM_COLUMNS, rows, window, hop)
-
-
-def write_track_csv(path: str, rows, window, track, hop: int) -> int:
-    """rows [R, 6] / window [R] / track [R] of `AudioDetector.track_stream` at a hop of `hop` samples"""
-    return _write_windows_csv(path, TRACK_COLUMNS, rows, window, hop, track)
-
-
-def write_bank_csv(path: str, rows, session, window, hop: int, track=None) -> int:
-    """rows [R, 6] / session [R] / window [R][ / track [R]] of a `LiveBank` at a hop of `hop` samples"""
-    rows, session, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(session).reshape(-1), np.asarray(window).reshape(-1)
-    last = [[]] * len(rows) if track is None else [[t] for t in np.asarray(track).reshape(-1).tolist()]
-    if not (len(session) == len(window) == len(last) == len(rows)):
-        raise ValueError("write_bank_csv: %d rows, %d sessions, %d windows, %d track ids" % (len(rows), len(session), len(window), len(last)))
-    with open(path, "w", newline="") as f:
-        out = csv.writer(f)
-        out.writerow(BANK_COLUMNS + (("track",) if track is not None else ()))
-        for q, w, r, t in zip(session.tolist(), window.tolist(), rows, last):
-            out.writerow([q, w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + t)
-    return len(rows)
-
-
-def stream_sizes(window_s: float, hop_s, n_total: int):
-    """-> (win_len, hop, number of windows) in samples; raises ValueError as `stream_window_starts` does"""
-    from mm_distillnet_amd.audio import stream_window_starts
-    win_len = int(round(window_s * SAMPLE_RATE))
-    hop = win_len if hop_s is None else int(round(hop_s * SAMPLE_RATE))
-    return win_len, hop, len(stream_window_starts(n_total, win_len, hop))
-
-
-def check_chunk_flags(a):
-    """--chunk_s: what can be refused from the flags alone, before any device work"""
-    if a.chunk_s is None:
-        return
-    if a.window_s is None:
-        raise ValueError("--chunk_s feeds a live session that slides a window over the recording: it needs --window_s")
-    if a.resample or a.sample_rate is not None:
-        raise ValueError("--chunk_s does not go with --resample / --sample_rate: it reads 44.1 kHz input only "
-                         "(--live_s reads a recording of any rate a chunk at a time and resamples it as it arrives)")
-    if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
-        raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
-    if os.path.splitext(a.input)[1].lower() not in (".npy", ".wav"):
-        raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
-
-
-def check_bank_flags(a):
-    """several --input: what can be refused from the flags alone, before any device work"""
-    if len(a.inputs) < 2:
+    if a.any_rate and not several:
+        raise ValueError("--any_rate is for several --input, each session at its file's rate (one recording of any rate: --live_s)")
+    if several:
+        if a.window_s is None or a.chunk_s is None:
+            raise ValueError("several --input are read side by side into a bank of live sessions: they need --window_s and --chunk_s")
         if a.any_rate:
-            raise ValueError("--any_rate is for several --input, each session at its file's rate (one recording of any rate: --live_s)")
-        return
-    if a.window_s is None or a.chunk_s is None:
-        raise ValueError("several --input are read side by side into a bank of live sessions: they need --window_s and --chunk_s")
-    if a.any_rate and (a.resample or a.sample_rate is not None or a.live_s is not None):
-        raise ValueError("--any_rate does not go with --resample / --sample_rate / --live_s: every .wav is read at the rate in its header")
-    if a.resample or a.sample_rate is not None or a.live_s is not None:
-        raise ValueError("several --input do not go with --resample / --sample_rate / --live_s: the bank reads 44.1 kHz input only")
-    if not a.chunk_s > 0 or int(round(a.chunk_s * SAMPLE_RATE)) < 1:
-        raise ValueError(f"--chunk_s {a.chunk_s}: a positive number of seconds (at least one sample)")
-    for path in a.inputs:
-        if a.any_rate and os.path.splitext(path)[1].lower() != ".wav":
-            raise ValueError(f"{path}: --any_rate reads 8-channel PCM .wav files, whose headers hold their rates (a .npy holds none)")
-        if os.path.splitext(path)[1].lower() not in (".npy", ".wav"):
-            raise ValueError(f"{path}: unsupported input (a .npy of float32 waveforms or an 8-channel 16-bit PCM .wav at 44.1 kHz)")
-    if a.batch is not None and a.batch < 1:
-        raise ValueError(f"--batch {a.batch}")
-
-
-def check_live_flags(a):
-    """--live_s: what can be refused from the flags alone, before any device work"""
-    if a.live_s is None:
-        return
-    if a.window_s is None:
-        raise ValueError("--live_s feeds a live session that slides a window over the recording: it needs --window_s")
+            not_with_rates("--any_rate does", "every .wav is read at the rate in its header")
+        not_with_rates("several --input do", "the bank reads 44.1 kHz input only")
+    elif a.chunk_s is not None:
+        needs_window("--chunk_s", LIVE_FEED)
+        not_with_rates("--chunk_s does", "it reads 44.1 kHz input only (--live_s reads a recording of any rate a chunk at a time and "
+                       "resamples it as it arrives)", live_too=False)
     if a.chunk_s is not None:
-        raise ValueError("--live_s does not go with --chunk_s: one of the two says how the recording is cut into chunks")
-    if not a.live_s > 0:
-        raise ValueError(f"--live_s {a.live_s}: a positive number of seconds (at least one frame)")
-    ext = os.path.splitext(a.input)[1].lower()
-    if ext not in (".npy", ".wav"):
-        raise ValueError(f"{a.input}: unsupported input (a .npy of float32 waveforms at --sample_rate, or an 8-channel PCM .wav of any rate)")
-    if ext == ".wav" and a.sample_rate is not None:
-        raise ValueError(f"{a.input}: a .wav holds its rate: --live_s reads it from the header (--sample_rate R is for a .npy)")
-    if ext == ".npy" and a.resample:
-        raise ValueError(f"{a.input}: --resample reads a .wav; --live_s takes a .npy at --sample_rate R")
-    rate = SAMPLE_RATE if a.sample_rate is None else a.sample_rate
-    if rate < 1:
-        raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
-    if ext == ".npy" and int(round(a.live_s * rate)) < 1:
-        raise ValueError(f"--live_s {a.live_s}: a positive number of seconds (at least one frame)")
-
-
-def open_live(path: str, live_s: float, sample_rate=None):
-    """-> (n_frames, rate, chunks): the recording's length in frames at its own rate in Hz and an iterator over it round(live_s * rate)
-    frames at a time - (raw frames, bytes per sample) of a 16-, 24- or 32-bit PCM `.wav` of any rate (for `LiveSession.push_pcm`; the
-    checks are `read_recording`'s), (float32 [8, n], None) of a `.npy` taken to be at sample_rate (default 44100; for `push`).  Only
-    one chunk is in host memory at a time."""
-    if os.path.splitext(path)[1].lower() == ".wav":
-        w = wave.open(path, "rb")
-        try:
-            width, rate = _check_wav(path, w, any_rate=True)
-            chunk = int(round(live_s * rate))
-            if chunk < 1:
-                raise ValueError(f"--live_s {live_s}: a positive number of seconds (at least one frame at {rate} Hz)")
-        except ValueError:
-            w.close()
-            raise
-        return w.getnframes(), rate, _wav_chunks(w, chunk, width)
-    rate = SAMPLE_RATE if sample_rate is None else int(sample_rate)
-    n_total, chunks = open_chunked(path, int(round(live_s * rate)))
-    return n_total, rate, chunks
-
-
-def open_chunked(path: str, chunk: int):
-    """-> (n_total, chunks): the recording's length in samples and an iterator over it `chunk` samples at a time - (raw frames, 2) of a
-    16-bit `.wav` (for `LiveSession.push_pcm`), (float32 [8, n], None) of a `.npy` (for `push`).  The checks are `read_wav`'s and
-    `read_npy`'s; only one chunk is in host memory at a time."""
-    if os.path.splitext(path)[1].lower() == ".wav":
-        w = wave.open(path, "rb")
-        try:
-            width, _ = _check_wav(path, w, any_rate=False)
-        except ValueError:
-            w.close()
-            raise
-        return w.getnframes(), _wav_chunks(w, chunk, width)
-    m = np.load(path, mmap_mode="r", allow_pickle=False)
-    if m.dtype != np.float32:
-        raise ValueError(f"{path}: waveforms must be float32, found {m.dtype}")
-    if m.ndim == 3 and m.shape[0] == 1:
-        m = m[0]
-    if m.ndim != 2 or m.shape[0] != CHANNELS:
-        raise ValueError(f"{path}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), found shape {m.shape}")
-    return m.shape[1], ((np.ascontiguousarray(m[:, i:i + chunk]), None) for i in range(0, m.shape[1], chunk))
-
-
-def run_chunked(det, chunks, win_len: int, hop: int, batch: int, track, sample_rate=None):
-    """Feeds the chunks of `open_chunked` / `open_live` (those at sample_rate) to a live session -> what `detect_stream` /
-    `track_stream` return for the whole recording (resampled to 44.1 kHz)"""
-    session = det.open_stream(win_len, hop, batch=batch, track=track, sample_rate=sample_rate)
-    parts = [session.push(c) if width is None else session.push_pcm(c, width) for c, width in chunks]
-    parts.append(session.flush())
-    session.close()
-    return session.concat(parts)
-
-
-def run_bank(det, sources: list, win_len: int, hop: int, batch: int, track):
-    """sources: the chunk iterators of `open_chunked`, one per session -> what the bank returns for the round robin over them: one chunk
-    of every file that still has one, in file order, again and again; `flush` at the end"""
-    bank = det.open_bank(len(sources), win_len, hop, batch=batch, track=track)
-    parts, live = [], list(enumerate(iter(src) for src in sources))
-    while live:
-        still = []
-        for k, it in live:
-            got = next(it, None)
-            if got is None:
-                continue
-            c, width = got
-            parts.append(bank.push(k, c) if width is None else bank.push_pcm(k, c, width))
-            still.append((k, it))
-        live = still
-    parts.append(bank.flush())
-    bank.close()
-    return bank.concat(parts)
-
-
-def run_bank_rounds(det, sources: list, rates: list, win_len: int, hop: int, batch: int, track):
-    """sources: the chunk iterators of `open_live`, one per session at rates[k] -> what the bank returns for the rounds over them:
-    one `push_all_pcm` per round with a chunk of every file that still has one; `flush` at the end"""
-    bank = det.open_bank(len(sources), win_len, hop, batch=batch, track=track, sample_rates=rates)
-    parts, live = [], list(enumerate(iter(src) for src in sources))
-    while live:
-        got = [(k, it, next(it, None)) for k, it in live]
-        live = [(k, it) for k, it, c in got if c is not None]
-        if live:
-            parts.append(bank.push_all_pcm({k: c[0] for k, _, c in got if c is not None}, {k: c[1] for k, _, c in got if c is not None}))
-    parts.append(bank.flush())
-    bank.close()
-    return bank.concat(parts)
+        positive_seconds("--chunk_s", a.chunk_s, SAMPLE_RATE, "sample")
+        for path in a.inputs:
+            if a.any_rate and ext(path) != ".wav":
+                raise ValueError(f"{path}: --any_rate reads 8-channel PCM .wav files, whose headers hold their rates (a .npy holds none)")
+            supported(path, INPUT_44K)
+    if several and a.batch is not None and a.batch < 1:
+        raise ValueError(f"--batch {a.batch}")
+    if a.live_s is not None:                  # one --input: several were refused above
+        needs_window("--live_s", LIVE_FEED)
+        if a.chunk_s is not None:
+            raise ValueError("--live_s does not go with --chunk_s: one of the two says how the recording is cut into chunks")
+        positive_seconds("--live_s", a.live_s, None, "frame")
+        supported(a.input, "a .npy of float32 waveforms at --sample_rate, or an 8-channel PCM .wav of any rate")
+        if ext(a.input) == ".wav" and a.sample_rate is not None:
+            raise ValueError(f"{a.input}: a .wav holds its rate: --live_s reads it from the header (--sample_rate R is for a .npy)")
+        if ext(a.input) == ".npy" and a.resample:
+            raise ValueError(f"{a.input}: --resample reads a .wav; --live_s takes a .npy at --sample_rate R")
+        rate = SAMPLE_RATE if a.sample_rate is None else a.sample_rate
+        if rate < 1:
+            raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
+        if ext(a.input) == ".npy":
+            positive_seconds("--live_s", a.live_s, rate, "frame")
+    if a.track:
+        needs_window("--track", "links the boxes of consecutive windows")
 
 
 def parse_args(argv=None):
@@ -406,98 +176,229 @@ def parse_args(argv=None):
     ap.add_argument("--live_s", type=float, default=None, help="read a recording of any rate this many seconds at a time into a live session that resamples (with --window_s)")
     a = ap.parse_args(argv)
     a.inputs, a.input = a.input, a.input[0]
-    check_bank_flags(a)
+    check_flags(a)
     if len(a.inputs) == 1 and a.batch is None:
         a.batch = 8
-    check_chunk_flags(a)
-    check_live_flags(a)
     return a
 
 
-def main_bank(a, cfg, track):
-    """several --input through one bank"""
-    if a.any_rate:
-        from mm_distillnet_amd.audio import resample_len, resample_ratio
-        opened = [open_live(path, a.chunk_s) for path in a.inputs]
-        rates = [rate for _, rate, _ in opened]
-        for rate in rates:
-            resample_ratio(rate)                  # an unsupported ratio is refused before any device work
-        opened = [(resample_len(n_frames, rate, SAMPLE_RATE), chunks) for n_frames, rate, chunks in opened]
+# ---------------------------------------------------------------------------------------------- output
+def write_csv(path: str, rows_per_clip) -> int:
+    n = 0
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow(COLUMNS)
+        for clip, rows in enumerate(rows_per_clip):
+            for r in np.asarray(rows, np.float32).reshape(-1, 6):
+                out.writerow([clip] + ["%.9g" % float(v) for v in r])      # 9 digits: float32 round-trips
+                n += 1
+    return n
+
+
+def write_windows_csv(path: str, rows, window, hop: int, track=None, session=None) -> int:
+    """One row per box: [its session,] its window, the window's start in seconds at a hop of `hop` samples, the box[, its track id].
+    rows [R, 6] / window [R][ / track [R]] of `detect_stream` / `track_stream` or a `LiveSession`; with session [R], of a `LiveBank`."""
+    rows, window = np.asarray(rows, np.float32).reshape(-1, 6), np.asarray(window).reshape(-1)
+
+    def column(ids):
+        return [[]] * len(rows) if ids is None else [[i] for i in np.asarray(ids).reshape(-1).tolist()]
+
+    first, last = column(session), column(track)
+    if (session is not None or track is not None) and not (len(first) == len(window) == len(last) == len(rows)):
+        if session is None:               # (both texts name the writer this one replaced: they are what callers match)
+            raise ValueError("write_track_csv: %d rows, %d windows, %d track ids" % (len(rows), len(window), len(last)))
+        raise ValueError("write_bank_csv: %d rows, %d sessions, %d windows, %d track ids" % (len(rows), len(first), len(window), len(last)))
+    with open(path, "w", newline="") as f:
+        out = csv.writer(f)
+        out.writerow((STREAM_COLUMNS if session is None else BANK_COLUMNS) + (("track",) if track is not None else ()))
+        for q, w, r, t in zip(first, window.tolist(), rows, last):
+            out.writerow(q + [w, "%.9g" % (w * hop / SAMPLE_RATE)] + ["%.9g" % float(v) for v in r] + t)
+    return len(rows)
+
+
+def report_windows(a, got, hop: int, n_win: int, track):
+    """CSV and summary line of ONE recording's windows -> (rows, window[, track ids])"""
+    ids = got[2] if track is not None else None
+    n = write_windows_csv(a.output, got[0], got[1], hop, ids)
+    tracks = "" if ids is None else ", %d tracks" % len(np.unique(ids[ids >= 0]))
+    print("%d windows, %d boxes%s -> %s" % (n_win, n, tracks, a.output))
+    return tuple(got)
+
+
+# ---------------------------------------------------------------------------------------------- input and detector
+def load_resampled(a, dev):
+    """--resample / --sample_rate: -> float32 DEVICE waveforms [B, 8, N] at 44.1 kHz"""
+    from mm_distillnet_amd.audio import Resampler
+    ext = os.path.splitext(a.input)[1].lower()
+    if a.resample:
+        if ext != ".wav" or a.sample_rate is not None:
+            raise ValueError(f"{a.input}: --resample reads a .wav, whose header holds the rate (for a .npy give --sample_rate R alone)")
+        raw, frames, channels, width, rate = read_recording(a.input)
+        rs = Resampler(dev)
+        wav = rs.pcm_to_float(torch.from_numpy(raw).to(dev), frames, channels, width)[None]
     else:
-        chunk = int(round(a.chunk_s * SAMPLE_RATE))
-        opened = [open_chunked(path, chunk) for path in a.inputs]
-    sizes = [stream_sizes(a.window_s, a.hop_s, n_total) for n_total, _ in opened]
-    win_len, hop, n_win = sizes[0][0], sizes[0][1], sum(z[2] for z in sizes)
+        if ext != ".npy":
+            raise ValueError(f"{a.input}: --sample_rate R says at which rate a .npy was recorded (a .wav holds its rate: --resample)")
+        if a.sample_rate < 1:
+            raise ValueError(f"--sample_rate {a.sample_rate}: a positive number of Hz")
+        rs = Resampler(dev)
+        wav, rate = torch.from_numpy(read_npy(a.input)).to(dev), a.sample_rate
+    return rs.resample(wav, rate, SAMPLE_RATE)
+
+
+def read_waves(a):
+    """-> the waveforms [B, 8, N] at 44.1 kHz: a numpy array, or with --resample / --sample_rate a device tensor (they are made on the
+    device: it is needed before the sizes are known)"""
+    if a.resample or a.sample_rate is not None:
+        torch.cuda.set_device(0)
+        return load_resampled(a, DEVICE)
+    return read_input(a.input)
+
+
+def stream_sizes(window_s: float, hop_s, n_total: int):
+    """-> (win_len, hop, number of windows) in samples; raises ValueError as `stream_window_starts` does"""
+    from mm_distillnet_amd.audio import stream_window_starts
+    win_len = int(round(window_s * SAMPLE_RATE))
+    hop = win_len if hop_s is None else int(round(hop_s * SAMPLE_RATE))
+    return win_len, hop, len(stream_window_starts(n_total, win_len, hop))
+
+
+def load_detector(a, cfg) -> AudioDetector:
+    """The student of the cfg file with the checkpoint's weights, on the device.  Every mode calls it behind its last host-side refusal."""
     torch.cuda.set_device(0)
     sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
     c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
-    det = AudioDetector.from_step_config(sspec, "cuda:0", T.step_config(cfg))
+    det = AudioDetector.from_step_config(sspec, DEVICE, T.step_config(cfg))
     det.load(c["state_dict"] if "state_dict" in c else c)
-    batch = len(a.inputs) if a.batch is None else a.batch
-    if a.any_rate:
-        got = run_bank_rounds(det, [chunks for _, chunks in opened], rates, win_len, hop, batch, track)
-    else:
-        got = run_bank(det, [chunks for _, chunks in opened], win_len, hop, batch, track)
-    n = write_bank_csv(a.output, *got[:3], hop, got[3] if track is not None else None)
+    return det
+
+
+# ---------------------------------------------------------------------------------------------- the feed loop
+def push_session(session, k: int, chunk, width):
+    return session.push(chunk) if width is None else session.push_pcm(chunk, width)
+
+
+def push_bank(bank, k: int, chunk, width):
+    return bank.push(k, chunk) if width is None else bank.push_pcm(k, chunk, width)
+
+
+def feed(target, sources: list, push=None):
+    """sources: the chunk iterators of `open_chunks`, source k for session k of `target`, a `LiveSession` (one source) or a `LiveBank`.
+    Walks them in round robin - one chunk of every source that still has one, in source order, again and again; exhausted sources drop
+    out - then `flush` and `close` -> what the target returns for the whole recordings.  push(target, k, chunk, width) hands a chunk
+    over as soon as it is read, before the next source is touched: one chunk in host memory.  push None: a round is collected and goes
+    over as ONE `push_all_pcm`."""
+    parts, live = [], list(enumerate(iter(src) for src in sources))
+    while live:
+        still, chunks, widths = [], {}, {}
+        for k, it in live:
+            got = next(it, None)
+            if got is None:
+                continue
+            still.append((k, it))
+            if push is not None:
+                parts.append(push(target, k, *got))
+            else:
+                chunks[k], widths[k] = got
+        if chunks:
+            parts.append(target.push_all_pcm(chunks, widths))
+        live = still
+    parts.append(target.flush())
+    target.close()
+    return target.concat(parts)
+
+
+# ---------------------------------------------------------------------------------------------- the modes
+def run_clips(a, cfg, track):
+    """every clip of the input on its own"""
+    waves = read_waves(a)
+    det = load_detector(a, cfg)
+    rows = det.detect(torch.as_tensor(waves).to(DEVICE))
+    det.check_overflow()
+    n = write_csv(a.output, rows)
+    print("%d clips, %d boxes -> %s" % (len(rows), n, a.output))
+    return rows
+
+
+def run_stream(a, cfg, track):
+    """--window_s: ONE recording, whole on the device"""
+    waves = read_waves(a)
+    if waves.shape[0] != 1:
+        raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
+                         f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
+    win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, waves.shape[2])
+    det = load_detector(a, cfg)
+    rec = torch.as_tensor(waves).to(DEVICE)[0]
+    got = det.detect_stream(rec, win_len, hop, batch=a.batch) if track is None else det.track_stream(rec, win_len, hop, batch=a.batch, track=track)
+    return report_windows(a, got, hop, n_win, track)
+
+
+def run_session(a, cfg, track, n_total: int, chunks, sample_rate):
+    """one recording of n_total samples at 44.1 kHz, its chunks pushed at sample_rate into a live session"""
+    win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, n_total)
+    session = load_detector(a, cfg).open_stream(win_len, hop, batch=a.batch, track=track, sample_rate=sample_rate)
+    return report_windows(a, feed(session, [chunks], push_session), hop, n_win, track)
+
+
+def run_chunked(a, cfg, track):
+    """--chunk_s: a 44.1 kHz recording, a chunk at a time"""
+    n_total, _, chunks = open_chunks(a.input, a.chunk_s, any_rate=False)
+    return run_session(a, cfg, track, n_total, chunks, None)
+
+
+def run_live(a, cfg, track):
+    """--live_s: a recording of any rate, a chunk at a time into a session that resamples"""
+    from mm_distillnet_amd.audio import resample_len
+    n_frames, rate, chunks = open_chunks(a.input, a.live_s, True, a.sample_rate)
+    return run_session(a, cfg, track, resample_len(n_frames, rate, SAMPLE_RATE), chunks, rate)
+
+
+def run_sessions(a, cfg, track, n_totals: list, sources: list, rates, push):
+    """several recordings of n_totals[k] samples at 44.1 kHz, their chunks pushed at rates[k] into one bank"""
+    sizes = [stream_sizes(a.window_s, a.hop_s, n_total) for n_total in n_totals]
+    win_len, hop, n_win = sizes[0][0], sizes[0][1], sum(z[2] for z in sizes)
+    det = load_detector(a, cfg)
+    bank = det.open_bank(len(sources), win_len, hop, batch=len(a.inputs) if a.batch is None else a.batch, track=track, sample_rates=rates)
+    got = feed(bank, sources, push)
+    n = write_windows_csv(a.output, got[0], got[2], hop, got[3] if track is not None else None, got[1])
     print("%d sessions, %d windows, %d boxes -> %s" % (len(a.inputs), n_win, n, a.output))
     return got
+
+
+def run_bank(a, cfg, track):
+    """several --input at 44.1 kHz: every chunk is pushed as it is read"""
+    opened = [open_chunks(path, a.chunk_s, any_rate=False) for path in a.inputs]
+    return run_sessions(a, cfg, track, [n for n, _, _ in opened], [chunks for _, _, chunks in opened], None, push_bank)
+
+
+def run_bank_any_rate(a, cfg, track):
+    """--any_rate: every file at its own rate, one `push_all_pcm` per round"""
+    from mm_distillnet_amd.audio import resample_len, resample_ratio
+    opened = [open_chunks(path, a.chunk_s, any_rate=True) for path in a.inputs]
+    rates = [rate for _, rate, _ in opened]
+    for rate in rates:
+        resample_ratio(rate)                  # an unsupported ratio is refused before any device work
+    return run_sessions(a, cfg, track, [resample_len(n, rate, SAMPLE_RATE) for n, rate, _ in opened], [chunks for _, _, chunks in opened], rates, None)
 
 
 def main(argv=None):
     a = parse_args(argv)
     track = None
     if a.track:
-        if a.window_s is None:
-            raise ValueError("--track links the boxes of consecutive windows: it needs --window_s")
         from mm_distillnet_amd.tracker import TrackConfig
         track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     if len(a.inputs) > 1:
-        return main_bank(a, cfg, track)
-    dev = "cuda:0"
-    resampled = a.resample or a.sample_rate is not None
-    chunked, rate = a.chunk_s is not None or a.live_s is not None, None
-    if a.live_s is not None:
-        from mm_distillnet_amd.audio import resample_len
-        n_frames, rate, chunks = open_live(a.input, a.live_s, a.sample_rate)
-        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, resample_len(n_frames, rate, SAMPLE_RATE))
+        mode = run_bank_any_rate if a.any_rate else run_bank
+    elif a.live_s is not None:
+        mode = run_live
     elif a.chunk_s is not None:
-        n_total, chunks = open_chunked(a.input, int(round(a.chunk_s * SAMPLE_RATE)))
-        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, n_total)
-    elif resampled:                           # the waveforms are made on the device: it is needed before the sizes are known
-        torch.cuda.set_device(0)
-        waves = load_resampled(a, dev)
+        mode = run_chunked
+    elif a.window_s is not None:
+        mode = run_stream
     else:
-        waves = read_input(a.input)
-    if a.window_s is not None and not chunked:
-        if waves.shape[0] != 1:
-            raise ValueError(f"{a.input}: --window_s takes ONE recording (a .wav, or a .npy of shape [{CHANNELS}, N]), "
-                             f"found {waves.shape[0]} clips of shape {tuple(waves.shape)}")
-        win_len, hop, n_win = stream_sizes(a.window_s, a.hop_s, waves.shape[2])
-    torch.cuda.set_device(0)
-    sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
-    c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
-    det = AudioDetector.from_step_config(sspec, dev, T.step_config(cfg))
-    det.load(c["state_dict"] if "state_dict" in c else c)
-    if chunked:
-        streamed = run_chunked(det, chunks, win_len, hop, a.batch, track, rate)
-    elif not resampled:
-        waves = torch.from_numpy(waves).to(dev)
-    if track is not None:
-        rows, window, ids = streamed if chunked else det.track_stream(waves[0], win_len, hop, batch=a.batch, track=track)
-        n = write_track_csv(a.output, rows, window, ids, hop)
-        print("%d windows, %d boxes, %d tracks -> %s" % (n_win, n, len(np.unique(ids[ids >= 0])), a.output))
-        return rows, window, ids
-    if a.window_s is not None:
-        rows, window = streamed if chunked else det.detect_stream(waves[0], win_len, hop, batch=a.batch)
-        n = write_stream_csv(a.output, rows, window, hop)
-        print("%d windows, %d boxes -> %s" % (n_win, n, a.output))
-        return rows, window
-    rows = det.detect(waves)
-    det.check_overflow()
-    n = write_csv(a.output, rows)
-    print("%d clips, %d boxes -> %s" % (len(rows), n, a.output))
-    return rows
+        mode = run_clips
+    return mode(a, cfg, track)
 
 
 if __name__ == "__main__":

@@ -211,7 +211,7 @@ def test_several_inputs_make_a_bank_or_are_refused():
     d = _detect()
     three = ["--input", "a.wav", "--input", "b.npy", "--input", "c.wav"]
     a = d.parse_args(BASE + three + ["--window_s", "1", "--hop_s", "0.1", "--chunk_s", "0.1"])
-    assert a.inputs == ["a.wav", "b.npy", "c.wav"] and a.batch is None            # main_bank: the number of files
+    assert a.inputs == ["a.wav", "b.npy", "c.wav"] and a.batch is None            # the bank: the number of files
     assert d.parse_args(BASE + three + ["--window_s", "1", "--chunk_s", "0.1", "--batch", "2", "--track"]).batch == 2
     for extra, what in ((["--window_s", "1"], "--window_s and --chunk_s"), (["--chunk_s", "0.1"], "--window_s and --chunk_s"),
                         ([], "--window_s and --chunk_s"),
@@ -230,9 +230,9 @@ def test_several_inputs_make_a_bank_or_are_refused():
 def test_bank_csv_has_the_session_column(tmp_path):
     d = _detect()
     rows = np.arange(12, dtype=np.float32).reshape(2, 6) / 7
-    n = d.write_bank_csv(str(tmp_path / "b.csv"), rows, np.array([2, 0], np.int32), np.array([5, 1], np.int32), HOP, np.array([3, -1], np.int32))
+    n = d.write_windows_csv(str(tmp_path / "b.csv"), rows, np.array([5, 1], np.int32), HOP, np.array([3, -1], np.int32), np.array([2, 0], np.int32))
     lines = open(tmp_path / "b.csv").read().splitlines()
     assert n == 2 and lines[0] == "session,window,t_start_s,x1,y1,x2,y2,score,label,track"
     assert lines[1].startswith("2,5,%.9g," % (5 * HOP / 44100)) and lines[1].endswith(",3") and lines[2].startswith("0,1,")
-    d.write_bank_csv(str(tmp_path / "c.csv"), rows, np.array([2, 0], np.int32), np.array([5, 1], np.int32), HOP)
+    d.write_windows_csv(str(tmp_path / "c.csv"), rows, np.array([5, 1], np.int32), HOP, session=np.array([2, 0], np.int32))
     assert open(tmp_path / "c.csv").read().splitlines()[0] == "session,window,t_start_s,x1,y1,x2,y2,score,label"

@@ -104,25 +104,25 @@ def test_chunk_flags_are_refused_before_any_device_work(tmp_path, monkeypatch):
 
 
 def test_open_chunked_reads_a_chunk_at_a_time(tmp_path):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     rng = np.random.default_rng(0)
     pcm = rng.integers(-32768, 32768, (1000, 8)).astype("<i2")
     with wave.open(str(tmp_path / "a.wav"), "wb") as w:
         w.setnchannels(8); w.setsampwidth(2); w.setframerate(44100)
         w.writeframes(pcm.tobytes())
-    n, chunks = det.open_chunked(str(tmp_path / "a.wav"), 300)
+    n, _, chunks = det.open_chunks(str(tmp_path / "a.wav"), 300 / 44100, any_rate=False)
     chunks = list(chunks)
     assert n == 1000 and [len(c) // 16 for c, _ in chunks] == [300, 300, 300, 100] and all(wd == 2 for _, wd in chunks)
     assert b"".join(c for c, _ in chunks) == pcm.tobytes()
     wav = rng.standard_normal((8, 1000)).astype(np.float32)
     np.save(tmp_path / "a.npy", wav)
-    n, chunks = det.open_chunked(str(tmp_path / "a.npy"), 300)
+    n, _, chunks = det.open_chunks(str(tmp_path / "a.npy"), 300 / 44100, any_rate=False)
     chunks = list(chunks)
     assert n == 1000 and [c.shape for c, _ in chunks] == [(8, 300)] * 3 + [(8, 100)] and all(wd is None for _, wd in chunks)
     assert np.array_equal(np.concatenate([c for c, _ in chunks], axis=1), wav)
     np.save(tmp_path / "b.npy", np.zeros((2, 8, 1000), np.float32))
     with pytest.raises(ValueError, match="ONE recording"):
-        det.open_chunked(str(tmp_path / "b.npy"), 300)
+        det.open_chunks(str(tmp_path / "b.npy"), 300 / 44100, any_rate=False)
 
 
 # ---------------------------------------------------------------------------------------------- the schedule

@@ -216,26 +216,26 @@ def test_live_flags_are_refused_before_any_device_work(tmp_path, monkeypatch):
 
 
 def test_open_live_reads_a_chunk_at_a_time_at_the_files_rate(tmp_path):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     rng = np.random.default_rng(0)
     frames = 1000
     raw = rng.integers(0, 256, frames * 8 * 3, dtype=np.uint8).tobytes()              # 24-bit frames, any bytes
     with wave.open(str(tmp_path / "a.wav"), "wb") as w:
         w.setnchannels(8); w.setsampwidth(3); w.setframerate(48000)
         w.writeframes(raw)
-    n, rate, chunks = det.open_live(str(tmp_path / "a.wav"), 0.00625)                 # round(0.00625 * 48000) = 300 frames
+    n, rate, chunks = det.open_chunks(str(tmp_path / "a.wav"), 0.00625, any_rate=True)                 # round(0.00625 * 48000) = 300 frames
     chunks = list(chunks)
     assert (n, rate) == (1000, 48000) and [len(c) // 24 for c, _ in chunks] == [300, 300, 300, 100] and all(wd == 3 for _, wd in chunks)
     assert b"".join(c for c, _ in chunks) == raw
     wav = rng.standard_normal((8, 1000)).astype(np.float32)
     np.save(tmp_path / "a.npy", wav)
-    n, rate, chunks = det.open_live(str(tmp_path / "a.npy"), 0.00625, 48000)
+    n, rate, chunks = det.open_chunks(str(tmp_path / "a.npy"), 0.00625, True, 48000)
     chunks = list(chunks)
     assert (n, rate) == (1000, 48000) and [c.shape for c, _ in chunks] == [(8, 300)] * 3 + [(8, 100)] and all(wd is None for _, wd in chunks)
     assert np.array_equal(np.concatenate([c for c, _ in chunks], axis=1), wav)
-    assert det.open_live(str(tmp_path / "a.npy"), 0.01)[1] == 44100
+    assert det.open_chunks(str(tmp_path / "a.npy"), 0.01, any_rate=True)[1] == 44100
     with wave.open(str(tmp_path / "b.wav"), "wb") as w:
         w.setnchannels(2); w.setsampwidth(2); w.setframerate(48000)
         w.writeframes(b"\0" * 400)
     with pytest.raises(ValueError, match="expected 8 microphone channels"):
-        det.open_live(str(tmp_path / "b.wav"), 0.01)
+        det.open_chunks(str(tmp_path / "b.wav"), 0.01, any_rate=True)

@@ -112,7 +112,7 @@ def _write_wav(path, pcm, rate=44100, width=2):
 
 
 def test_detect_reads_npy_waveforms(tmp_path):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     rng = np.random.default_rng(3)
     one, two = rng.standard_normal((8, 700)).astype(np.float32), rng.standard_normal((2, 8, 700)).astype(np.float32)
     np.save(tmp_path / "one.npy", one); np.save(tmp_path / "two.npy", two)
@@ -129,7 +129,7 @@ def test_detect_reads_npy_waveforms(tmp_path):
 
 
 def test_detect_reads_pcm16_wav_and_refuses_other_formats(tmp_path):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     pcm = np.random.default_rng(4).integers(-32768, 32768, (900, 8)).astype(np.int16)
     pcm[0, 0], pcm[1, 0] = -32768, 32767
     _write_wav(tmp_path / "ok.wav", pcm)

@@ -188,7 +188,7 @@ def _write_wav(path, samples, rate, width, channels=8):
 @pytest.mark.parametrize("rate", [22050, 48000])
 @pytest.mark.parametrize("width", [2, 3, 4])
 def test_read_recording_hands_over_the_raw_frames(tmp_path, rate, width):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     top = 1 << (8 * width - 1)
     s = np.random.default_rng(width).integers(-top, top, (333, 8))
     s[0, 0], s[1, 0], s[2, 0] = -top, top - 1, -1
@@ -207,7 +207,7 @@ def test_read_recording_hands_over_the_raw_frames(tmp_path, rate, width):
 
 
 def test_read_recording_refuses_other_formats_and_read_input_is_untouched(tmp_path):
-    det = _detect()
+    from mm_distillnet_amd import recording as det
     s = np.random.default_rng(0).integers(-32768, 32768, (900, 8))
     _write_wav(tmp_path / "narrow.wav", (s >> 8) + 128, 48000, 1)
     with pytest.raises(ValueError, match="16-, 24- or 32-bit PCM"):

@@ -99,7 +99,7 @@ def test_stream_csv_writer(tmp_path):
     det = _detect()
     rows = np.array([[1, 2, 30, 40, 0.1 + 0.2, 6], [0, 0, 128, 127, np.float32(1) / 3, 6], [5, 6, 7, 8, 0.999999, 14]], np.float32)
     window = np.array([0, 0, 7], np.int32)
-    assert det.write_stream_csv(str(tmp_path / "s.csv"), rows, window, 1531) == 3
+    assert det.write_windows_csv(str(tmp_path / "s.csv"), rows, window, 1531) == 3
     lines = open(tmp_path / "s.csv").read().strip().split("\n")
     assert lines[0] == "window,t_start_s,x1,y1,x2,y2,score,label" and len(lines) == 4
     assert [ln.split(",")[0] for ln in lines[1:]] == ["0", "0", "7"]
@@ -107,7 +107,7 @@ def test_stream_csv_writer(tmp_path):
     got = np.array([[float(v) for v in ln.split(",")[2:]] for ln in lines[1:]])
     assert np.array_equal(got.astype(np.float32), rows)
     # no boxes: the header alone
-    assert det.write_stream_csv(str(tmp_path / "e.csv"), np.zeros((0, 6), np.float32), np.zeros(0, np.int32), 100) == 0
+    assert det.write_windows_csv(str(tmp_path / "e.csv"), np.zeros((0, 6), np.float32), np.zeros(0, np.int32), 100) == 0
     assert open(tmp_path / "e.csv", "rb").read() == b"window,t_start_s,x1,y1,x2,y2,score,label\r\n"
 
 

@@ -206,18 +206,18 @@ def test_track_csv_writer(tmp_path):
     det = _detect()
     rows = np.array([[1, 2, 30, 40, 0.1 + 0.2, 6], [0, 0, 128, 127, np.float32(1) / 3, 6], [5, 6, 7, 8, 0.999999, 14]], np.float32)
     window, track = np.array([0, 0, 7], np.int32), np.array([0, -1, 12], np.int32)
-    assert det.write_track_csv(str(tmp_path / "t.csv"), rows, window, track, 1531) == 3
+    assert det.write_windows_csv(str(tmp_path / "t.csv"), rows, window, 1531, track) == 3
     assert open(tmp_path / "t.csv", "rb").read() == (b"window,t_start_s,x1,y1,x2,y2,score,label,track\r\n"
                                                      b"0,0,1,2,30,40,0.300000012,6,0\r\n"
                                                      b"0,0,0,0,128,127,0.333333343,6,-1\r\n"
                                                      b"7,0.243015873,5,6,7,8,0.999998987,14,12\r\n")
-    assert det.write_track_csv(str(tmp_path / "e.csv"), np.zeros((0, 6), np.float32), np.zeros(0, np.int32), np.zeros(0, np.int32), 100) == 0
+    assert det.write_windows_csv(str(tmp_path / "e.csv"), np.zeros((0, 6), np.float32), np.zeros(0, np.int32), 100, np.zeros(0, np.int32)) == 0
     assert open(tmp_path / "e.csv", "rb").read() == b"window,t_start_s,x1,y1,x2,y2,score,label,track\r\n"
     with pytest.raises(ValueError):
-        det.write_track_csv(str(tmp_path / "x.csv"), rows, window, track[:2], 1531)
+        det.write_windows_csv(str(tmp_path / "x.csv"), rows, window, 1531, track[:2])
     # the stream writer keeps its eight columns
     assert det.STREAM_COLUMNS == ("window", "t_start_s", "x1", "y1", "x2", "y2", "score", "label")
-    assert det.write_stream_csv(str(tmp_path / "s.csv"), rows, window, 1531) == 3
+    assert det.write_windows_csv(str(tmp_path / "s.csv"), rows, window, 1531) == 3
     assert open(tmp_path / "s.csv", "rb").read().split(b"\r\n")[:2] == [b"window,t_start_s,x1,y1,x2,y2,score,label", b"0,0,1,2,30,40,0.300000012,6"]
 
 
