@@ -834,6 +834,48 @@ int mmd_track_update(const float* rows, const int* cnt, int B, int cap_img, cons
 // mmd_track_update, and on n_sessions outside 1 .. 65535.
 int mmd_track_update_bank(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess, const int* win_idx, int n_sessions, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, hipStream_t stream);
 
+// ---- tracking evaluation (csrc/moteval.hip, mm_distillnet_amd/mot.py): the CLEAR-MOT counts and the identity measures of a tracked
+// hypothesis record against a ground-truth record (the rule: DESIGN.md, tracking evaluation; tests/mot_ref.py restates it in numpy /
+// scipy).  Both records as the host wrapper prepares them: rows float32 [n, 6] (x1, y1, x2, y2, score, label) sorted stably by
+// (session, window); track int32 [n], DENSE ids 0 .. tracks_of_the_session-1 per session and side (hypothesis: -1 = no track; such a
+// row can never be paired); off int32 [n_sessions * n_windows + 1]: the rows of window w of session s are off[s * n_windows + w] ..
+// off[s * n_windows + w + 1] - 1.  At most 256 rows of one side in one window take part (the first 256; the HOST refuses more);
+// offsets are clamped into 0 .. n, so nothing outside the arrays is read.  A pair is allowed when the labels are equal and
+// iou >= iou_min (false for NaN), the IoU being the tracker's float32 expression with every operation rounded on its own
+// (mmd_box_iou of csrc/moteval.hip = tests/track_ref.iou_matrix bit for bit).
+//
+// Bytes of mmd_mot_clear's `ws` for n_gt_tracks ground-truth tracks over all sessions (never 0).  -22 for a negative count or one
+// above 2^27 - 1.
+int mmd_mot_clear_ws_bytes(long long n_gt_tracks);
+
+// CLEAR: one 256-thread block per session walks windows 0 .. n_windows-1 in order.  Per window: KEEP (a ground-truth row whose track
+// was last paired with hypothesis track h keeps h when h has a row in the window, that row is free and the pair is allowed; rows in
+// row order), ASSIGN (the maximum-weight matching of the allowed pairs among the rows left, weight = IoU, by the shortest augmenting
+// path algorithm in float64; where two matchings tie, which one is taken is unspecified), COUNT.  gt_trk_off int32 [n_sessions + 1]:
+// session s owns ground-truth tracks gt_trk_off[s] .. gt_trk_off[s + 1] - 1 of the per-track arrays; n_gt_tracks = gt_trk_off[n_sessions].
+// Outputs: counts int64 [n_sessions, 8] = {n_gt, n_hyp, tp, fp, fn, idsw, frag, windows walked}; iou_sum double [n_sessions] (the sum of
+// the pairs' IoUs; the order of the sum is fixed); present / matched int32 [n_gt_tracks]: windows in which the track has a row / a
+// paired row.  ws: mmd_mot_clear_ws_bytes(n_gt_tracks) bytes, 8-byte aligned: per track {map, state}.  counts, iou_sum, present,
+// matched and ws need no zeroing: every block initialises its session's part.  A ground-truth row whose id is outside its session's
+// range (the CALLER'S ERROR) is never paired and counts as a miss.  No atomics: two runs give the same bits.  -22 before any launch on
+// null pointers (a null row / track array with a row count of 0 is allowed), negative counts, counts that do not fit an int,
+// n_sessions outside 1 .. 65535, n_windows < 1, n_sessions * n_windows >= 2^31 - 1.
+int mmd_mot_clear(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows, const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows, const int* gt_trk_off, long long n_gt_tracks, float iou_min, long long* counts, double* iou_sum, int* present, int* matched, void* ws, hipStream_t stream);
+
+// Identity, step 1: C[g][h] += 1 for every window in which a row of ground-truth track g and a row of hypothesis track h (>= 0) form
+// an allowed pair.  One block per (window, session); integer atomicAdd, so the sums do not depend on the order of arrival.  C int32:
+// session s's matrix [G_s, H_s] (G_s = gt_trk_off[s + 1] - gt_trk_off[s], H_s likewise from hyp_trk_off int32 [n_sessions + 1]), row
+// major, at C + c_off[s] (c_off int64 [n_sessions]); c_total = the ints C holds.  The CALLER ZEROES C.  A session whose matrix does not
+// lie inside C, and a row whose id is outside its session's range, add nothing.  max_tracks: the largest G_s or H_s.  -22 as
+// mmd_mot_clear, and on c_total < 1, max_tracks outside 1 .. 1024 (the capacity of the identity measures).
+int mmd_mot_id_counts(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows, const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows, const int* gt_trk_off, const int* hyp_trk_off, int max_tracks, const long long* c_off, long long c_total, float iou_min, int* C, hipStream_t stream);
+
+// Identity, step 2: idtp int64 [n_sessions] = the weight of the maximum-weight matching of session s's C (the routine of mmd_mot_clear,
+// one block per session; integer weights, so the float64 arithmetic is exact and ties do not matter); 0 for a session without tracks on
+// either side, -1 for a session whose G_s or H_s is above 1024 or whose matrix does not lie inside C (the CALLER'S ERROR).  idtp needs
+// no zeroing.  -22 before any launch on null pointers, n_sessions outside 1 .. 65535, c_total < 1, max_tracks outside 1 .. 1024.
+int mmd_mot_id_assign(const int* C, const long long* c_off, long long c_total, const int* gt_trk_off, const int* hyp_trk_off, int n_sessions, int max_tracks, long long* idtp, hipStream_t stream);
+
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction
 // (src/optimization/train_methods.py:944-961): student gradients only, sum (the 1/N average rides in the optimizer pass), plus the
