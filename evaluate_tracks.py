@@ -2,7 +2,7 @@
 """Tracking evaluation of the CSVs `detect.py --track` writes: CLEAR-MOT counts and identity measures of predicted tracks against
 ground-truth tracks, on the device (`mm_distillnet_amd.mot.mot_metrics`; the rule: DESIGN.md, tracking evaluation).
 
-    python evaluate_tracks.py --gt gt.csv --pred tracks.csv [--iou 0.5] [--no_identity] [--output metrics.csv]
+    python evaluate_tracks.py --gt gt.csv --pred tracks.csv [--iou 0.5] [--no_identity] [--hota] [--output metrics.csv]
 
 Both files have one of the two layouts of `detect.py --track`:
     window,t_start_s,x1,y1,x2,y2,score,label,track                  one recording
@@ -11,8 +11,9 @@ and both must have the same one.  A ground-truth file can be made from saved tea
 `detect.write_windows_csv`.  Every ground-truth row needs a track (>= 0); predicted rows with track -1 stay in and count as false
 positives.  n_windows is 1 + the largest window index of either file.  --iou: smallest IoU at which a ground-truth and a predicted box
 may be paired (labels must be equal).  --no_identity: the CLEAR counts alone (the identity measures hold at most 1024 tracks per file
-and session).  One line per session and one overall line are printed; --output writes them as CSV, header `session` + the keys, the
-overall row with an empty session."""
+and session).  --hota: HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr and LocA (`mot.hota_metrics`: the means over HOTA's own 19
+thresholds 0.05 .. 0.95, which --iou does not affect) behind the other keys.  One line per session and one overall line are printed;
+--output writes them as CSV, header `session` + the keys, the overall row with an empty session."""
 import argparse
 import csv
 import os
@@ -35,6 +36,8 @@ def parse_args(argv=None):
     ap.add_argument("--pred", required=True, help="predicted tracks: the CSV of detect.py --track")
     ap.add_argument("--iou", type=float, default=0.5, help="smallest IoU at which two boxes of equal label may be paired")
     ap.add_argument("--no_identity", action="store_true", help="CLEAR counts only: no IDTP / IDF1")
+    ap.add_argument("--hota", action="store_true", help="append HOTA, DetA, AssA, DetRe, DetPr, AssRe, AssPr, LocA (means over the thresholds "
+                                                        "0.05 .. 0.95; --iou does not affect them)")
     ap.add_argument("--output", default=None, help="write the per-session and overall figures as CSV")
     a = ap.parse_args(argv)
     if not (0.0 < a.iou <= 1.0):
@@ -110,7 +113,13 @@ def format_lines(result: dict):
 def evaluate(a, device=DEVICE) -> dict:
     from mm_distillnet_amd.mot import mot_metrics
     gt, hyp, n_windows = load_pair(a.gt, a.pred)
-    return mot_metrics(gt, hyp, n_windows, device, iou_min=a.iou, identity=not a.no_identity)
+    result = mot_metrics(gt, hyp, n_windows, device, iou_min=a.iou, identity=not a.no_identity)
+    if a.hota:
+        from mm_distillnet_amd import mot
+        hota = mot.hota_metrics(gt, hyp, n_windows, device)
+        for d, h in zip([result["overall"]] + result["sessions"], [hota["overall"]] + hota["sessions"]):
+            d.update((k, h[k]) for k in mot.HOTA_KEYS)
+    return result
 
 
 def main(argv=None):

@@ -876,6 +876,35 @@ int mmd_mot_id_counts(const float* gt_rows, const int* gt_track, const int* gt_o
 // no zeroing.  -22 before any launch on null pointers, n_sessions outside 1 .. 65535, c_total < 1, max_tracks outside 1 .. 1024.
 int mmd_mot_id_assign(const int* C, const long long* c_off, long long c_total, const int* gt_trk_off, const int* hyp_trk_off, int n_sessions, int max_tracks, long long* idtp, hipStream_t stream);
 
+// ---- HOTA (Luiten et al., IJCV 2021) of the same two records, in three passes (the rule: DESIGN.md, tracking evaluation, HOTA;
+// tests/hota_ref.py restates it).  Records, offsets, gt_trk_off / hyp_trk_off, c_off / c_total (the cell layout of the identity
+// matrix: session s's cell (g, h) is c_off[s] + g * H_s + h) and max_tracks as above.  Hypothesis rows with track -1 take no part.
+// s(i, j) = mmd_box_iou (float32) of a ground-truth row and a hypothesis row of one window when the labels are equal, else 0;
+// q(x) = floor(double(x) * 2^32 + 0.5); thresholds alpha_k = float32((k + 1) / 20), k = 0 .. 18; bins(s) = the number of k with
+// s >= alpha_k.  gc int32 [n_gt_tracks] / tc int32 [n_hyp_tracks]: the rows of each track, at gt_trk_off[s] + g / hyp_trk_off[s] + h.
+// Everything accumulated is an integer added with integer atomics, so two runs give the same bits.  Every entry point returns -22
+// before any launch, without touching the device, on: null pointers (a null row / track array with a row count of 0 is allowed),
+// the size errors of mmd_mot_clear, n_windows > 2^20 (P must stay below 2^52), c_total < 1 or 19 * c_total > 2^28, max_tracks outside
+// 1 .. 1024, track counts that are negative or above 2^27 - 1.
+//
+// Pass 1, alignment: one 256-thread block per (window, session).  R_i = sum_j q(s(i, j)), C_j = sum_i q(s(i, j)); every pair with
+// q(s) > 0 adds q(double(q(s)) / double(R_i + C_j - q(s))) to P[cell(g, h)], g and h the rows' tracks.  P unsigned 64-bit [c_total].
+// The CALLER ZEROES P.  A session whose cells do not lie inside P adds nothing.
+int mmd_hota_align(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows, const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows, const int* gt_trk_off, const int* hyp_trk_off, int max_tracks, const long long* c_off, long long c_total, unsigned long long* P, hipStream_t stream);
+
+// Pass 2, matching: one block per (window, session).  score(i, j) = gas(g, h) * double(s(i, j)) in float64, gas = double(P) /
+// (2^32 * double(gc + tc) - double(P)); ONE maximum-score assignment of the window's rows (the routine of mmd_mot_clear on
+// cost = -score; where two assignments tie, which one is taken is unspecified).  Every assigned pair with b = bins(s) > 0 adds 1 to
+// hist[cell(g, h) * 19 + b - 1], and for every k < b 1 to tp[s * 19 + k] and q(s) to loc[s * 19 + k].  hist int32 [c_total * 19],
+// tp int64 [n_sessions, 19], loc unsigned 64-bit [n_sessions, 19].  The CALLER ZEROES hist, tp and loc.  P, gc and tc are read only.
+int mmd_hota_match(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows, const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows, const int* gt_trk_off, const int* hyp_trk_off, int max_tracks, const long long* c_off, long long c_total, const unsigned long long* P, const int* gc, long long n_gt_tracks, const int* tc, long long n_hyp_tracks, int* hist, long long* tp, unsigned long long* loc, hipStream_t stream);
+
+// Pass 3, association: one block per session.  For each of the session's cells mc[k] = hist[cell][k] + .. + hist[cell][18]; num double
+// [n_sessions, 19, 3] = per k the sums over the cells with mc > 0 of mc * mc / (gc + tc - mc), mc * mc / gc, mc * mc / tc (float64; a
+// strided loop over the cells and a fixed reduction tree, no atomics: two runs give the same bits).  num needs no zeroing: every
+// block writes its session's 57 values, zeros for a session without cells or whose tables do not lie inside hist / gc / tc.
+int mmd_hota_assoc(const int* hist, const long long* c_off, long long c_total, const int* gt_trk_off, const int* hyp_trk_off, const int* gc, long long n_gt_tracks, const int* tc, long long n_hyp_tracks, int n_sessions, int max_tracks, double* num, hipStream_t stream);
+
 
 // ---- data-parallel exchange (RCCL over xGMI), SURVEY.md section 8b.  Replaces DistributedDataParallel's gradient reduction
 // (src/optimization/train_methods.py:944-961): student gradients only, sum (the 1/N average rides in the optimizer pass), plus the

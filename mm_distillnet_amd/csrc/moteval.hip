@@ -19,6 +19,9 @@
 // row i and hypothesis row i in registers for the whole walk; one block reduction at the end.  No atomics: two runs give the same bits.
 // mmd_mot_id_counts: one block per (window, session) adds 1 to C[g][h] for every allowed pair of its window - integer atomicAdd, so the
 // order of arrival does not matter.  mmd_mot_id_assign: one block per session, mot_assign on C, IDTP = the matching's weight.
+// HOTA (Luiten et al. 2021; the section at the end of this file): mmd_hota_align and mmd_hota_match run one block per (window, session)
+// - no window needs another window's result inside a pass - and accumulate integers only; mmd_hota_assoc, one block per session, turns
+// the per-cell histograms into the association numerators.  They share mot_assign, MotSide / mot_stage / mot_span and mmd_box_iou.
 // Plain HIP, vector stores only.
 #include "common.h"
 
@@ -462,5 +465,270 @@ extern "C" int mmd_mot_id_assign(const int* C, const long long* c_off, long long
   if (!C || !c_off || !gt_trk_off || !hyp_trk_off || !idtp) return MMD_EINVAL;
   if (n_sessions < 1 || n_sessions > 65535 || c_total < 1 || max_tracks < 1 || max_tracks > MOT_TMAX) return MMD_EINVAL;
   hipLaunchKernelGGL(mot_id_assign_kernel, dim3(n_sessions), dim3(256), 0, stream, C, c_off, c_total, gt_trk_off, hyp_trk_off, idtp);
+  return mmd_check_launch();
+}
+
+// ---- HOTA (Luiten et al. 2021) --------------------------------------------------------------------------------------------------------
+// The rule is DESIGN.md's (tracking evaluation, HOTA); tests/hota_ref.py restates it.  Everything that is accumulated is an integer:
+// q(x) = floor(x * 2^32 + 0.5) of a float32 IoU or of a float64 quotient in [0, 1], summed with integer atomics, so the order of arrival
+// does not matter and two runs give the same bits.  No window needs another window's result inside a pass: one block per (window,
+// session) in passes 1 and 2.  Hypothesis rows with track -1 (and rows whose id is outside the session's range) take no part.
+#define HOTA_NA 19          // thresholds alpha_k = float32((k + 1) / 20)
+
+__device__ __forceinline__ unsigned long long hota_q(double x) { return (unsigned long long)floor(x * 4294967296.0 + 0.5); }
+
+// s(i, j): the IoU where both rows have a track and the labels are equal, else 0 (never NaN: `!(s > 0)` is "no similarity")
+__device__ __forceinline__ float hota_sim(const MotSide& g, int i, const MotSide& h, int j) {
+  if (g.trk[i] < 0 || h.trk[j] < 0 || !(g.label[i] == h.label[j])) return 0.f;
+  const float s = mot_iou(g, i, h, j);
+  return s > 0.f ? s : 0.f;
+}
+__device__ __forceinline__ unsigned long long hota_qsim(const MotSide& g, int i, const MotSide& h, int j) {
+  const float s = hota_sim(g, i, h, j);
+  return s > 0.f ? hota_q((double)s) : 0ull;
+}
+// the number of thresholds s passes; they nest, so these are the first `bins`
+__device__ __forceinline__ int hota_bins(float s) {
+  int b = 0;
+#pragma unroll
+  for (int k = 0; k < HOTA_NA; ++k) b += (s >= (float)((double)(k + 1) / 20.0)) ? 1 : 0;
+  return b;
+}
+// gas(g, h) * s in float64, every operation rounded on its own (the restatement's bits): gas = P / (2^32 (gc + tc) - P)
+__device__ __forceinline__ double hota_score(unsigned long long p, int gcount, int tcount, float s) {
+#pragma clang fp contract(off)
+  const double den = 4294967296.0 * (double)((long long)gcount + (long long)tcount) - (double)p;
+  if (!(den > 0.0)) return 0.0;                          // the caller's counts are wrong
+  return ((double)p / den) * (double)s;
+}
+
+// the session's part of the tables; false (uniform) when the caller's tables are wrong: nothing is read or written then
+struct HotaSess { int G, H, g0, h0; long long c0; };
+__device__ __forceinline__ bool hota_sess(const int* __restrict__ gt_trk_off, const int* __restrict__ hyp_trk_off,
+                                          const long long* __restrict__ c_off, long long c_total, int sess, HotaSess& t) {
+  t.g0 = gt_trk_off[sess]; t.h0 = hyp_trk_off[sess];
+  t.G = gt_trk_off[sess + 1] - t.g0; t.H = hyp_trk_off[sess + 1] - t.h0;
+  t.c0 = c_off[sess];
+  return t.g0 >= 0 && t.h0 >= 0 && t.G >= 0 && t.H >= 0 && t.G <= MOT_TMAX && t.H <= MOT_TMAX && t.c0 >= 0 &&
+         t.c0 + (long long)t.G * t.H <= c_total;
+}
+
+struct HotaAlignShared {
+  MotSide g, h;
+  unsigned long long R[MOT_RMAX], C[MOT_RMAX];           // row / column sums of q(s)
+};
+
+// pass 1: P[g][h] += q(q(s) / (R_i + C_j - q(s))) for every pair of the window with q(s) > 0
+__global__ __launch_bounds__(256) void hota_align_kernel(const float* __restrict__ gt_rows, const int* __restrict__ gt_track,
+                                                         const int* __restrict__ gt_off, int n_gt_rows, const float* __restrict__ hyp_rows,
+                                                         const int* __restrict__ hyp_track, const int* __restrict__ hyp_off, int n_hyp_rows,
+                                                         int n_windows, const int* __restrict__ gt_trk_off,
+                                                         const int* __restrict__ hyp_trk_off, const long long* __restrict__ c_off,
+                                                         long long c_total, unsigned long long* __restrict__ P) {
+  __shared__ HotaAlignShared sh;
+  const int tid = threadIdx.x, w = blockIdx.x, sess = blockIdx.y;
+  const long long k = (long long)sess * n_windows + w;
+  int glo, ng, hlo, nh;
+  mot_span(gt_off, k, n_gt_rows, glo, ng);
+  mot_span(hyp_off, k, n_hyp_rows, hlo, nh);
+  if (ng == 0 || nh == 0) return;                        // uniform
+  HotaSess t;
+  if (!hota_sess(gt_trk_off, hyp_trk_off, c_off, c_total, sess, t) || t.G < 1 || t.H < 1) return;
+  mot_stage(sh.g, gt_rows, gt_track, glo, ng, t.G);
+  mot_stage(sh.h, hyp_rows, hyp_track, hlo, nh, t.H);
+  __syncthreads();
+  // thread i owns ground-truth row i, thread j hypothesis row j; the IoUs are recomputed below, not kept (256 x 256 floats)
+  if (tid < ng) {
+    unsigned long long r = 0;
+    for (int j = 0; j < nh; ++j) r += hota_qsim(sh.g, tid, sh.h, j);
+    sh.R[tid] = r;
+  }
+  if (tid < nh) {
+    unsigned long long c = 0;
+    for (int i = 0; i < ng; ++i) c += hota_qsim(sh.g, i, sh.h, tid);
+    sh.C[tid] = c;
+  }
+  __syncthreads();
+  for (int q = tid; q < ng * nh; q += 256) {
+    const int i = q / nh, j = q - i * nh;
+    const unsigned long long qs = hota_qsim(sh.g, i, sh.h, j);
+    if (qs == 0) continue;
+    const double c = (double)qs / (double)(sh.R[i] + sh.C[j] - qs);      // R_i and C_j both hold qs: the denominator is >= qs
+    atomicAdd(&P[t.c0 + (long long)sh.g.trk[i] * t.H + sh.h.trk[j]], hota_q(c));
+  }
+}
+
+struct HotaMatchShared {
+  MotSide g, h;
+  int glist[MOT_RMAX], hlist[MOT_RMAX];                  // the rows with a track
+  int wsum[4];
+  int cnt[HOTA_NA];                                      // the window's pairs with bins = b + 1 ..
+  unsigned long long sum[HOTA_NA];                       // .. and the sum of their q(s)
+  MotAssign<MOT_RMAX> as;
+};
+
+// pass 2: one maximum-score assignment per window, score = gas * s; the assigned pairs are counted per threshold
+__global__ __launch_bounds__(256) void hota_match_kernel(const float* __restrict__ gt_rows, const int* __restrict__ gt_track,
+                                                         const int* __restrict__ gt_off, int n_gt_rows, const float* __restrict__ hyp_rows,
+                                                         const int* __restrict__ hyp_track, const int* __restrict__ hyp_off, int n_hyp_rows,
+                                                         int n_windows, const int* __restrict__ gt_trk_off,
+                                                         const int* __restrict__ hyp_trk_off, const long long* __restrict__ c_off,
+                                                         long long c_total, const unsigned long long* __restrict__ P,
+                                                         const int* __restrict__ gc, int n_gt_tracks, const int* __restrict__ tc,
+                                                         int n_hyp_tracks, int* __restrict__ hist, long long* __restrict__ tp,
+                                                         unsigned long long* __restrict__ loc) {
+  __shared__ HotaMatchShared sh;
+  const int tid = threadIdx.x, w = blockIdx.x, sess = blockIdx.y;
+  const long long k = (long long)sess * n_windows + w;
+  int glo, ng, hlo, nh;
+  mot_span(gt_off, k, n_gt_rows, glo, ng);
+  mot_span(hyp_off, k, n_hyp_rows, hlo, nh);
+  if (ng == 0 || nh == 0) return;                        // uniform
+  HotaSess t;
+  if (!hota_sess(gt_trk_off, hyp_trk_off, c_off, c_total, sess, t) || t.G < 1 || t.H < 1) return;
+  if ((long long)t.g0 + t.G > n_gt_tracks || (long long)t.h0 + t.H > n_hyp_tracks) return;
+  mot_stage(sh.g, gt_rows, gt_track, glo, ng, t.G);
+  mot_stage(sh.h, hyp_rows, hyp_track, hlo, nh, t.H);
+  if (tid < HOTA_NA) { sh.cnt[tid] = 0; sh.sum[tid] = 0ull; }
+  __syncthreads();
+  const int nl = mot_compact(tid < ng && sh.g.trk[tid] >= 0, sh.glist, sh.wsum);
+  const int ml = mot_compact(tid < nh && sh.h.trk[tid] >= 0, sh.hlist, sh.wsum);
+  if (nl == 0 || ml == 0) return;                        // uniform
+  const unsigned long long* Ps = P + t.c0;
+  const int* gcs = gc + t.g0;
+  const int* tcs = tc + t.h0;
+  const int H = t.H;
+  // hota_sim(g, h) is the expression's order in every use: the functor of the transposed problem swaps its indices back
+  auto score = [&](int i, int j) -> double {
+    const float s = hota_sim(sh.g, i, sh.h, j);
+    if (!(s > 0.f)) return 0.0;
+    const int g = sh.g.trk[i], h = sh.h.trk[j];
+    return hota_score(Ps[(long long)g * H + h], gcs[g], tcs[h], s);
+  };
+  bool any = false;
+  if (tid < nl) {
+    const int i = sh.glist[tid];
+    for (int c = 0; c < ml && !any; ++c) any = score(i, sh.hlist[c]) > 0.0;
+  }
+  if (!__syncthreads_or(any)) return;                    // no pair with a positive score: nothing to assign, nothing to count
+  auto count = [&](int i, int j) {
+    const float s = hota_sim(sh.g, i, sh.h, j);
+    const int b = hota_bins(s);
+    if (b < 1) return;
+    atomicAdd(&hist[(t.c0 + (long long)sh.g.trk[i] * H + sh.h.trk[j]) * HOTA_NA + (b - 1)], 1);
+    atomicAdd(&sh.cnt[b - 1], 1);
+    atomicAdd(&sh.sum[b - 1], hota_q((double)s));
+  };
+  if (nl <= ml) {
+    const bool ok = mot_assign<MOT_RMAX>(sh.as, nl, ml, [&](int r, int c) -> double { return -score(sh.glist[r], sh.hlist[c]); });
+    if (ok)
+      for (int c = tid; c < ml; c += 256) {
+        const int r = sh.as.p[c + 1] - 1;
+        if (r >= 0) count(sh.glist[r], sh.hlist[c]);
+      }
+  } else {
+    const bool ok = mot_assign<MOT_RMAX>(sh.as, ml, nl, [&](int r, int c) -> double { return -score(sh.glist[c], sh.hlist[r]); });
+    if (ok)
+      for (int c = tid; c < nl; c += 256) {
+        const int r = sh.as.p[c + 1] - 1;
+        if (r >= 0) count(sh.glist[c], sh.hlist[r]);
+      }
+  }
+  __syncthreads();
+  if (tid < HOTA_NA) {                                   // threshold k counts the pairs with bins > k: a suffix sum
+    long long n = 0;
+    unsigned long long l = 0;
+    for (int b = tid; b < HOTA_NA; ++b) { n += sh.cnt[b]; l += sh.sum[b]; }
+    if (n > 0) {
+      atomicAdd((unsigned long long*)&tp[(long long)sess * HOTA_NA + tid], (unsigned long long)n);
+      atomicAdd(&loc[(long long)sess * HOTA_NA + tid], l);
+    }
+  }
+}
+
+// pass 3: per session and threshold, the three association numerators over the session's cells.  Thread t takes cells t, t + 256, ..;
+// one butterfly per wave and a fixed order across the four waves: two runs give the same bits.
+__global__ __launch_bounds__(256) void hota_assoc_kernel(const int* __restrict__ hist, const long long* __restrict__ c_off,
+                                                         long long c_total, const int* __restrict__ gt_trk_off,
+                                                         const int* __restrict__ hyp_trk_off, const int* __restrict__ gc, int n_gt_tracks,
+                                                         const int* __restrict__ tc, int n_hyp_tracks, double* __restrict__ out) {
+  __shared__ double red[4][HOTA_NA * 3];
+  const int tid = threadIdx.x, sess = blockIdx.x;
+  HotaSess t;
+  bool ok = hota_sess(gt_trk_off, hyp_trk_off, c_off, c_total, sess, t);
+  ok = ok && (long long)t.g0 + t.G <= n_gt_tracks && (long long)t.h0 + t.H <= n_hyp_tracks;
+  double acc[HOTA_NA][3];
+#pragma unroll
+  for (int k = 0; k < HOTA_NA; ++k) { acc[k][0] = 0.0; acc[k][1] = 0.0; acc[k][2] = 0.0; }
+  const int cells = ok ? t.G * t.H : 0;                  // a session whose tables are wrong reports zeros
+  for (int cell = tid; cell < cells; cell += 256) {
+    const int g = cell / t.H, h = cell - g * t.H;
+    const int* hb = hist + (t.c0 + cell) * HOTA_NA;
+    const long long a = gc[t.g0 + g], b = tc[t.h0 + h];
+    long long mc = 0;
+#pragma unroll
+    for (int k = HOTA_NA - 1; k >= 0; --k) {
+      mc += hb[k];
+      if (mc > 0 && a > 0 && b > 0 && a + b - mc > 0) {
+        const double m2 = (double)mc * (double)mc;
+        acc[k][0] += m2 / (double)(a + b - mc);
+        acc[k][1] += m2 / (double)a;
+        acc[k][2] += m2 / (double)b;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < HOTA_NA; ++k) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const double v = wave_sum_d(acc[k][q]);
+      if ((tid & 63) == 0) red[tid >> 6][k * 3 + q] = v;
+    }
+  }
+  __syncthreads();
+  if (tid < HOTA_NA * 3) out[(size_t)sess * (HOTA_NA * 3) + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+static bool hota_tables_ok(long long c_total, int max_tracks, long long n_gt_tracks, long long n_hyp_tracks) {
+  if (c_total < 1 || c_total * HOTA_NA > (1ll << 28) || max_tracks < 1 || max_tracks > MOT_TMAX) return false;
+  return n_gt_tracks >= 0 && n_hyp_tracks >= 0 && n_gt_tracks <= 0x07ffffffll && n_hyp_tracks <= 0x07ffffffll;
+}
+
+extern "C" int mmd_hota_align(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows,
+                              const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows,
+                              const int* gt_trk_off, const int* hyp_trk_off, int max_tracks, const long long* c_off, long long c_total,
+                              unsigned long long* P, hipStream_t stream) {
+  if (!gt_off || !hyp_off || !gt_trk_off || !hyp_trk_off || !c_off || !P) return MMD_EINVAL;
+  if (!mot_sizes_ok(n_gt_rows, n_hyp_rows, n_sessions, n_windows) || n_windows > (1 << 20) || !hota_tables_ok(c_total, max_tracks, 0, 0))
+    return MMD_EINVAL;
+  if ((n_gt_rows > 0 && (!gt_rows || !gt_track)) || (n_hyp_rows > 0 && (!hyp_rows || !hyp_track))) return MMD_EINVAL;
+  hipLaunchKernelGGL(hota_align_kernel, dim3(n_windows, n_sessions), dim3(256), 0, stream, gt_rows, gt_track, gt_off, (int)n_gt_rows,
+                     hyp_rows, hyp_track, hyp_off, (int)n_hyp_rows, n_windows, gt_trk_off, hyp_trk_off, c_off, c_total, P);
+  return mmd_check_launch();
+}
+
+extern "C" int mmd_hota_match(const float* gt_rows, const int* gt_track, const int* gt_off, long long n_gt_rows, const float* hyp_rows,
+                              const int* hyp_track, const int* hyp_off, long long n_hyp_rows, int n_sessions, int n_windows,
+                              const int* gt_trk_off, const int* hyp_trk_off, int max_tracks, const long long* c_off, long long c_total,
+                              const unsigned long long* P, const int* gc, long long n_gt_tracks, const int* tc, long long n_hyp_tracks,
+                              int* hist, long long* tp, unsigned long long* loc, hipStream_t stream) {
+  if (!gt_off || !hyp_off || !gt_trk_off || !hyp_trk_off || !c_off || !P || !gc || !tc || !hist || !tp || !loc) return MMD_EINVAL;
+  if (!mot_sizes_ok(n_gt_rows, n_hyp_rows, n_sessions, n_windows) || n_windows > (1 << 20) ||
+      !hota_tables_ok(c_total, max_tracks, n_gt_tracks, n_hyp_tracks))
+    return MMD_EINVAL;
+  if ((n_gt_rows > 0 && (!gt_rows || !gt_track)) || (n_hyp_rows > 0 && (!hyp_rows || !hyp_track))) return MMD_EINVAL;
+  hipLaunchKernelGGL(hota_match_kernel, dim3(n_windows, n_sessions), dim3(256), 0, stream, gt_rows, gt_track, gt_off, (int)n_gt_rows,
+                     hyp_rows, hyp_track, hyp_off, (int)n_hyp_rows, n_windows, gt_trk_off, hyp_trk_off, c_off, c_total, P, gc,
+                     (int)n_gt_tracks, tc, (int)n_hyp_tracks, hist, tp, loc);
+  return mmd_check_launch();
+}
+
+extern "C" int mmd_hota_assoc(const int* hist, const long long* c_off, long long c_total, const int* gt_trk_off, const int* hyp_trk_off,
+                              const int* gc, long long n_gt_tracks, const int* tc, long long n_hyp_tracks, int n_sessions, int max_tracks,
+                              double* num, hipStream_t stream) {
+  if (!hist || !c_off || !gt_trk_off || !hyp_trk_off || !gc || !tc || !num) return MMD_EINVAL;
+  if (n_sessions < 1 || n_sessions > 65535 || !hota_tables_ok(c_total, max_tracks, n_gt_tracks, n_hyp_tracks)) return MMD_EINVAL;
+  hipLaunchKernelGGL(hota_assoc_kernel, dim3(n_sessions), dim3(256), 0, stream, hist, c_off, c_total, gt_trk_off, hyp_trk_off, gc,
+                     (int)n_gt_tracks, tc, (int)n_hyp_tracks, num);
   return mmd_check_launch();
 }

@@ -6,7 +6,11 @@ The rule is written out in DESIGN.md (tracking evaluation) and in include/mmdist
 scipy.  A record is what `AudioDetector.track_stream`, `tracker.track_rows` or a `LiveBank` return: rows float32 [R, 6] (x1, y1, x2, y2,
 score, label), window int [R], track int [R][, session int [R]].  The ground truth may be a record of tracks made from a teacher's boxes
 with `tracker.track_rows`.  Validation, the stable sort by (session, window), the dense track ids and the offset tables are host work
-(`prepare`); the device gets one upload, the kernels run on the current stream, and the host waits and copies once."""
+(`prepare`); the device gets one upload, the kernels run on the current stream, and the host waits and copies once.
+
+HOTA (Luiten et al., IJCV 2021) with DetA / AssA / LocA and the recall / precision pairs is `hota_metrics` (`mmd_hota_align`,
+`mmd_hota_match`, `mmd_hota_assoc`), split the same way: `hota_prepare` / `hota_run_device` / `hota_assemble`; tests/hota_ref.py restates
+it."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Tuple
@@ -18,6 +22,10 @@ ID_TRACKS_MAX = 1024        # tracks per side and session of the identity measur
 CLEAR_KEYS = ("n_gt", "n_hyp", "tp", "fp", "fn", "idsw", "frag", "mt", "pt", "ml", "mota", "motp", "precision", "recall")
 ID_KEYS = ("idtp", "idfp", "idfn", "idp", "idr", "idf1")
 KEYS = CLEAR_KEYS + ID_KEYS
+HOTA_KEYS = ("hota", "deta", "assa", "detre", "detpr", "assre", "asspr", "loca")
+HOTA_ALPHAS = 19            # thresholds alpha_k = float32((k + 1) / 20)
+HOTA_WINDOWS_MAX = 2 ** 20  # the alignment sums stay below 2^52: exact in float64
+HOTA_HIST_MAX = 2 ** 28     # histogram words: 19 per cell of the identity matrix's layout
 
 
 def _ratio(a, b) -> float:
@@ -205,3 +213,127 @@ def assemble(prep: dict, res: dict) -> dict:
                      None if res["idtp"] is None else int(res["idtp"].sum()))
     table = np.stack([G["u_sess"], G["u_id"], res["present"].astype(np.int64), res["matched"].astype(np.int64)], axis=1).astype(np.int64)
     return {"overall": overall, "sessions": sessions, "gt_tracks": table.reshape(-1, 4)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- HOTA
+def hota_alphas() -> np.ndarray:
+    """the 19 thresholds as the kernels compare them: float32((k + 1) / 20), returned as float64"""
+    return np.array([np.float32((k + 1) / 20) for k in range(HOTA_ALPHAS)], np.float64)
+
+
+def hota_derive(n_gt: int, n_hyp: int, tp, loc, num) -> Tuple[dict, dict]:
+    """The figures of one session, or of all sessions from summed counts: tp int [19], loc int [19] (sums of q(s) = s * 2^32), num float64
+    [19, 3] (the AssA / AssRe / AssPr numerators).  -> ({key: mean over the thresholds}, {"tp": int64 [19], key: float64 [19]})"""
+    per = {k: np.zeros(HOTA_ALPHAS, np.float64) for k in HOTA_KEYS}
+    for k in range(HOTA_ALPHAS):
+        t = int(tp[k])
+        fn, fp = int(n_gt) - t, int(n_hyp) - t
+        per["deta"][k], per["detre"][k], per["detpr"][k] = _ratio(t, t + fn + fp), _ratio(t, t + fn), _ratio(t, t + fp)
+        per["assa"][k], per["assre"][k], per["asspr"][k] = (float(num[k][q]) / max(1, t) for q in range(3))
+        per["loca"][k] = float(int(loc[k])) / 4294967296.0 / t if t else 1.0
+        per["hota"][k] = float(np.sqrt(per["deta"][k] * per["assa"][k]))
+    means = {k: float(np.mean(per[k])) for k in HOTA_KEYS}
+    per["tp"] = np.asarray([int(v) for v in tp], np.int64)
+    return means, per
+
+
+def hota_prepare(gt, hyp, n_windows: int) -> dict:
+    """The host side of `hota_metrics`: `prepare`'s checks and tables (HOTA has no iou_min and always needs the per-session track
+    tables), HOTA's own two limits, the rows per track and the rows per session.  Touches neither the library nor the device."""
+    if int(n_windows) > HOTA_WINDOWS_MAX:
+        raise ValueError("hota_metrics: n_windows = %d: at most 2^20 = %d windows per session (the alignment sums must stay exact in "
+                         "float64)" % (int(n_windows), HOTA_WINDOWS_MAX))
+    prep = prepare(gt, hyp, n_windows, 0.5, True)
+    G, H, S, W = prep["gt"], prep["hyp"], prep["n_sessions"], prep["n_windows"]
+    sizes = np.diff(G["trk_off"]).astype(np.int64) * np.diff(H["trk_off"]).astype(np.int64)
+    c_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if HOTA_ALPHAS * int(c_off[-1]) > HOTA_HIST_MAX:
+        raise ValueError("hota_metrics: %d track pairs over all sessions need %d histogram cells: at most 2^28 = %d (19 per pair of a "
+                         "ground-truth and a hypothesis track of one session)" % (int(c_off[-1]), HOTA_ALPHAS * int(c_off[-1]), HOTA_HIST_MAX))
+    has = H["dense"] >= 0
+    prep.update(c_off=c_off, c_total=max(int(c_off[-1]), 1),
+                gc=np.bincount(G["trk_off"][G["session"]].astype(np.int64) + G["dense"], minlength=max(int(G["trk_off"][-1]), 1)).astype(np.int32),
+                tc=np.bincount(H["trk_off"][H["session"][has]].astype(np.int64) + H["dense"][has],
+                               minlength=max(int(H["trk_off"][-1]), 1)).astype(np.int32),
+                n_gt=(G["off"][W::W] - G["off"][:-1:W]).astype(np.int64), n_hyp=(H["off"][W::W] - H["off"][:-1:W]).astype(np.int64))
+    return prep
+
+
+def hota_run_device(prep: dict, device, intermediates: bool = False, times: Optional[dict] = None) -> dict:
+    """The kernels on what `hota_prepare` made: one upload, three launches on the current stream, one synchronise, one copy back.
+    -> {"tp" int64 [S, 19], "loc" uint64 [S, 19], "num" float64 [S, 19, 3]}; intermediates: also "P" uint64 [c_total] and "hist" int32
+    [c_total, 19] (two more copies: for tests).  times: a dict that receives the seconds of "upload", "align", "match", "assoc" and
+    "copy", with a synchronise behind each (tools/dev/time_hota.py; the call is slower for it)"""
+    import time
+
+    import torch
+
+    from . import _lib
+    G, H, S, W, A = prep["gt"], prep["hyp"], prep["n_sessions"], prep["n_windows"], HOTA_ALPHAS
+    n_g, n_h, T_g, T_h, c_total = len(G["rows"]), len(H["rows"]), int(G["trk_off"][-1]), int(H["trk_off"][-1]), prep["c_total"]
+    host = [G["rows"], G["dense"], G["off"], H["rows"], H["dense"], H["off"], G["trk_off"], H["trk_off"], prep["c_off"][:-1], prep["gc"], prep["tc"]]
+    buf, spans = _pack(host)
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        if times is not None:
+            torch.cuda.current_stream().synchronize()
+            clock.append(time.perf_counter())
+            times[name] = clock[-1] - clock[-2]
+    dev = torch.from_numpy(buf).to(device)                                    # the one upload
+
+    def part(k, dtype):
+        o, n = spans[k]
+        return dev[o:o + n].view(dtype) if n else None
+
+    g_rows, g_trk, g_off = part(0, torch.float32), part(1, torch.int32), part(2, torch.int32)
+    h_rows, h_trk, h_off = part(3, torch.float32), part(4, torch.int32), part(5, torch.int32)
+    g_toff, h_toff, c_off_d, gc, tc = part(6, torch.int32), part(7, torch.int32), part(8, torch.int64), part(9, torch.int32), part(10, torch.int32)
+    most = max(1, int(np.diff(G["trk_off"]).max()), int(np.diff(H["trk_off"]).max()))
+    # outputs in one buffer: tp [S, 19] int64 | loc [S, 19] uint64 (both zeroed) | num [S, 19, 3] float64 (needs no zeroing)
+    o_loc, o_num, o_end = S * A * 8, S * A * 16, S * A * 40
+    out = torch.zeros(o_end, dtype=torch.uint8, device=device)
+    tp, loc, num = out[:o_loc].view(torch.int64), out[o_loc:o_num].view(torch.int64), out[o_num:].view(torch.float64)
+    P = torch.zeros(c_total, dtype=torch.int64, device=device)               # unsigned on the device; the values stay below 2^52
+    hist = torch.zeros(c_total * A, dtype=torch.int32, device=device)
+    lap("upload")                                                             # .. and the zero fills
+    _lib.call("mmd_hota_align", g_rows, g_trk, g_off, n_g, h_rows, h_trk, h_off, n_h, S, W, g_toff, h_toff, most, c_off_d, c_total, P)
+    lap("align")
+    _lib.call("mmd_hota_match", g_rows, g_trk, g_off, n_g, h_rows, h_trk, h_off, n_h, S, W, g_toff, h_toff, most, c_off_d, c_total, P,
+              gc, T_g, tc, T_h, hist, tp, loc)
+    lap("match")
+    _lib.call("mmd_hota_assoc", hist, c_off_d, c_total, g_toff, h_toff, gc, T_g, tc, T_h, S, most, num)
+    lap("assoc")
+    torch.cuda.current_stream().synchronize()
+    back = out.cpu().numpy()                                                  # the one copy
+    lap("copy")
+    res = {"tp": back[:o_loc].view(np.int64).reshape(S, A).copy(), "loc": back[o_loc:o_num].view(np.uint64).reshape(S, A).copy(),
+           "num": back[o_num:].view(np.float64).reshape(S, A, 3).copy()}
+    if intermediates:
+        res["P"] = P.cpu().numpy().view(np.uint64)
+        res["hist"] = hist.cpu().numpy().reshape(c_total, A)
+    return res
+
+
+def hota_assemble(prep: dict, res: dict) -> dict:
+    """the dictionaries of `hota_metrics` from the kernels' sums; the overall figures come from the summed tp, n_gt, n_hyp, loc and
+    numerators (TrackEval's combination over sequences)"""
+    S = prep["n_sessions"]
+    got = [hota_derive(int(prep["n_gt"][s]), int(prep["n_hyp"][s]), res["tp"][s], [int(v) for v in res["loc"][s]], res["num"][s]) for s in range(S)]
+    loc = [sum(int(res["loc"][s][k]) for s in range(S)) for k in range(HOTA_ALPHAS)]
+    overall, per = hota_derive(int(prep["n_gt"].sum()), int(prep["n_hyp"].sum()), res["tp"].sum(axis=0), loc, res["num"].sum(axis=0))
+    return {"overall": overall, "sessions": [m for m, _ in got],
+            "alphas": {"alpha": hota_alphas(), "overall": per, "sessions": [p for _, p in got]}}
+
+
+def hota_metrics(gt, hyp, n_windows: int, device) -> dict:
+    """HOTA of the records `mot_metrics` takes.  -> {"overall": {...}, "sessions": [{...}, ..], "alphas": {"alpha": float64 [19],
+    "overall": {...}, "sessions": [{...}, ..]}}: the dicts have the keys hota deta assa detre detpr assre asspr loca, the means over the
+    19 thresholds 0.05 .. 0.95; the dicts under "alphas" hold the same keys as float64 [19] and "tp" int64 [19].  There is no iou_min:
+    the thresholds are HOTA's own.  Overall figures come from summed counts and numerators.  A ratio with a zero denominator is NaN; LocA
+    is 1 at a threshold without a true positive.
+
+    ValueError, before the library is loaded or the device touched: everything `mot_metrics` refuses (the 256 rows per window and the
+    1024 tracks per side and session included), n_windows > 2^20, more than 2^28 histogram cells (19 per track pair of a session)."""
+    prep = hota_prepare(gt, hyp, n_windows)
+    return hota_assemble(prep, hota_run_device(prep, device))
