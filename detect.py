@@ -3,7 +3,8 @@
 
     python detect.py --config_file F --checkpoint P --input X --output out.csv [--overwrite JSON]
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
-                      [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]]]
+                      [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]
+                               [--track_assign greedy|optimal]]]
                      [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS]
     python detect.py --config_file F --checkpoint P --input X0 --input X1 [--input X2 ...] --output out.csv
                      --window_s SECONDS --chunk_s SECONDS [--any_rate] [--hop_s SECONDS] [--batch N] [--track ...]
@@ -24,6 +25,8 @@ With --track (only with --window_s) the boxes of consecutive windows are linked 
 (`AudioDetector.track_stream`: greedy IoU association with a constant-velocity model) and the CSV gains a last column `track`: the id of
 the row's track - ids start at 0 and rise in order of birth - or -1.  --track_iou: smallest IoU of a pairing (0.3); --track_beta: velocity
 gain (0.5); --track_max_age: windows a track survives without a box (2); --track_max: live tracks at a time (64, at most 256).
+--track_assign: how tracks and boxes are paired in a window - greedy (the default: the largest IoU first) or optimal (the matching of
+maximum IoU sum: two vehicles that pass each other keep their ids where the greedy step would leave one of them without a box).
 
 With --resample a `.wav` may have any sample rate and 16-, 24- or 32-bit PCM samples (8 channels): its frames go to the device as they
 are in the file, are decoded there and resampled to 44.1 kHz (`mm_distillnet_amd.audio.Resampler`: what `librosa.load(path, sr=44100)`
@@ -169,6 +172,7 @@ def parse_args(argv=None):
     ap.add_argument("--track_beta", type=float, default=0.5, help="velocity gain of the constant-velocity model")
     ap.add_argument("--track_max_age", type=int, default=2, help="windows a track survives without a box")
     ap.add_argument("--track_max", type=int, default=64, help="live tracks at a time (1 .. 256)")
+    ap.add_argument("--track_assign", type=str, default="greedy", help="pairing of tracks and boxes: greedy, or optimal (maximum IoU sum)")
     ap.add_argument("--resample", action="store_true", help="a .wav of any rate, 16/24/32-bit PCM: decode and resample to 44.1 kHz on the device")
     ap.add_argument("--sample_rate", type=int, default=None, help="the rate in Hz of a .npy input; resampled to 44.1 kHz on the device")
     ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
@@ -386,7 +390,8 @@ def main(argv=None):
     track = None
     if a.track:
         from mm_distillnet_amd.tracker import TrackConfig
-        track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max)
+        track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max,
+                            assign=a.track_assign)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
     if len(a.inputs) > 1:
         mode = run_bank_any_rate if a.any_rate else run_bank

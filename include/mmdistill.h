@@ -834,6 +834,26 @@ int mmd_track_update(const float* rows, const int* cnt, int B, int cap_img, cons
 // mmd_track_update, and on n_sessions outside 1 .. 65535.
 int mmd_track_update_bank(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess, const int* win_idx, int n_sessions, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, hipStream_t stream);
 
+// mmd_track_update with the association rule as an argument (TrackConfig(assign=...)): assign 0 = greedy - the launch is the very
+// kernel mmd_track_update launches -, 1 = optimal, anything else -22.  Every other argument, the state, the offsets, the overflow rule
+// and the refusals are mmd_track_update's.  The OPTIMAL rule replaces the greedy pairing and nothing else (predict, matched-slot update,
+// ageing and freeing, births and the rows' ids stay, with their rounding): T = the live slots in rising order after the predict step,
+// D = the first min(n, 256) detections of the window; iou[t][d] = the float32 IoU of the greedy step with every operation rounded on
+// its own (tests/track_ref.iou_matrix bit for bit); a pair is ALLOWED when the labels are equal and iou >= iou_min (false for NaN);
+// W[t][d] = (double)iou[t][d] on allowed pairs and 0 elsewhere (a NaN IoU weighs 0).  The matching of MAXIMUM WEIGHT sum W is taken -
+// maximum weight, not maximum cardinality: scipy.optimize.linear_sum_assignment(W, maximize=True) with the pairs that are not allowed
+// dropped, float64 on the float32 IoUs as the "assign" step of mmd_mot_clear - and every pair of it is a match: all matched slots
+// update from their own prediction, so their order does not matter.  Where two matchings tie, which one is taken is unspecified.  No
+// live slot, no detection or no allowed pair: nothing is matched.  tests/track_assign_ref.py restates it.  The solver is mot_assign
+// (csrc/mot_assign.h, shared with the tracking evaluation), run on the slots and detections that have an allowed pair at all; should it
+// ever find no column (it cannot for finite costs) the window matches nothing and trk_glob[1] = 1.  One block of 256 threads, no
+// atomics, no workspace: two runs give the same bits.
+int mmd_track_update_assign(const float* rows, const int* cnt, int B, int cap_img, const int* ctl, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, int assign, hipStream_t stream);
+
+// mmd_track_update_bank with the association rule as an argument: assign as mmd_track_update_assign (0: the kernel
+// mmd_track_update_bank launches), everything else as mmd_track_update_bank.
+int mmd_track_update_bank_assign(const float* rows, const int* cnt, int B, int cap_img, const int* n_valid, const int* win_sess, const int* win_idx, int n_sessions, const int* rec_count, int rec_cap, int* rec_track, int* trk_slots, int* trk_glob, int max_tracks, float iou_min, float beta, int max_age, float birth_score, int assign, hipStream_t stream);
+
 // ---- tracking evaluation (csrc/moteval.hip, mm_distillnet_amd/mot.py): the CLEAR-MOT counts and the identity measures of a tracked
 // hypothesis record against a ground-truth record (the rule: DESIGN.md, tracking evaluation; tests/mot_ref.py restates it in numpy /
 // scipy).  Both records as the host wrapper prepares them: rows float32 [n, 6] (x1, y1, x2, y2, score, label) sorted stably by

@@ -3,7 +3,7 @@
 // LiveBank return - against a ground-truth record of the same shape.  The rule is written out in DESIGN.md (tracking evaluation) and
 // restated in numpy / scipy by tests/mot_ref.py.
 //
-// Both measures rest on an OPTIMAL assignment, which the tracker's greedy pairing is not.  mot_assign below is the one routine for
+// Both measures rest on an OPTIMAL assignment, which the tracker's greedy pairing is not.  mot_assign (mot_assign.h) is the one routine for
 // both: the shortest-augmenting-path algorithm with potentials (Jonker-Volgenant, the "Hungarian algorithm with potentials") for an
 // n x m cost matrix, n <= m (the caller transposes), minimising; the callers pass cost = -weight.  One 256-thread block.  Thread t owns
 // the columns t, t + 256, .. - so m may exceed 256 - and each inner step is one pass over the owned columns (relax minv / way against
@@ -24,6 +24,7 @@
 // the per-cell histograms into the association numerators.  They share mot_assign, MotSide / mot_stage / mot_span and mmd_box_iou.
 // Plain HIP, vector stores only.
 #include "common.h"
+#include "mot_assign.h"      // MotAssign / mot_assign / MOT_INF / mot_compact: shared with the tracker (track.hip)
 
 // The float32 IoU of the rule, ONE function for every user in this file: areas without +1 (area = (x2 - x1) * (y2 - y1), kept beside
 // the boxes), ww = min(x2) - max(x1), hh likewise; 0 where either is <= 0 or the union is not positive; otherwise
@@ -53,84 +54,6 @@ __device__ __forceinline__ float mmd_box_iou(float ax1, float ay1, float ax2, fl
 
 #define MOT_RMAX 256       // rows of one side in one window (the tracker's TRK_DMAX)
 #define MOT_TMAX 1024       // tracks per side and session of the identity measures
-#define MOT_INF 1.0e300
-
-// ---- the assignment ------------------------------------------------------------------------------------------------------------------
-template <int CAP>
-struct MotAssign {
-  double u[CAP + 1];          // row potentials, 1-based (u[0] unused)
-  double v[CAP + 1];          // column potentials, 1-based
-  double minv[CAP + 1];
-  int way[CAP + 1];
-  int p[CAP + 1];             // p[j]: the row matched to column j (1-based; 0: none); p[0]: the row being inserted
-  int used[CAP + 1];
-  double wv[4];               // the four waves' minima
-  int wj[4];
-};
-
-// n x m, 1 <= n <= m <= CAP, cost(row, column) with 0-based indices, finite.  Called by all 256 threads; on return (behind a
-// __syncthreads) L.p[1 .. m] holds the optimum.  Returns false - uniformly, and only for costs that are not finite - when a step
-// finds no column: the matching in L.p is then not to be used.
-template <int CAP, class Cost>
-__device__ __forceinline__ bool mot_assign(MotAssign<CAP>& L, int n, int m, Cost cost) {
-  const int tid = threadIdx.x;
-  for (int j = tid; j <= m; j += 256) { L.u[j] = 0.0; L.v[j] = 0.0; L.p[j] = 0; }
-  __syncthreads();
-  for (int i = 1; i <= n; ++i) {
-    if (tid == 0) L.p[0] = i;
-    for (int j = 1 + tid; j <= m; j += 256) { L.minv[j] = MOT_INF; L.used[j] = 0; }
-    int j0 = 0;
-    __syncthreads();
-    for (;;) {
-      const int i0 = L.p[j0];
-      const double ui0 = L.u[i0];
-      double bv = MOT_INF;
-      int bj = 0x7fffffff;
-      for (int j = 1 + tid; j <= m; j += 256) {
-        if (j == j0) L.used[j] = 1;                      // the owner marks the column that just joined the tree
-        if (L.used[j]) continue;
-        const double cur = cost(i0 - 1, j - 1) - ui0 - L.v[j];
-        double mv = L.minv[j];
-        if (cur < mv) { mv = cur; L.minv[j] = cur; L.way[j] = j0; }
-        if (mv < bv) { bv = mv; bj = j; }                // own columns rise: the first minimum is the lowest column
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oj = __shfl_xor(bj, o, 64);
-        if (ov < bv || (ov == bv && oj < bj)) { bv = ov; bj = oj; }
-      }
-      if ((tid & 63) == 0) { L.wv[tid >> 6] = bv; L.wj[tid >> 6] = bj; }
-      __syncthreads();
-      double delta = L.wv[0];
-      int j1 = L.wj[0];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) {
-        const double ov = L.wv[w];
-        const int oj = L.wj[w];
-        if (ov < delta || (ov == delta && oj < j1)) { delta = ov; j1 = oj; }
-      }
-      if (j1 > m) return false;                          // uniform: every thread read the same eight words
-      for (int j = 1 + tid; j <= m; j += 256) {
-        if (L.used[j]) { L.u[L.p[j]] += delta; L.v[j] -= delta; }      // the used columns' rows are distinct
-        else L.minv[j] -= delta;
-      }
-      if (tid == 0) L.u[i] += delta;                     // column 0 of the tree: the row being inserted
-      j0 = j1;
-      __syncthreads();                                   // the potentials are visible, every thread is done with wv / wj
-      if (L.p[j0] == 0) break;                           // uniform: a free column ends the path
-    }
-    if (tid == 0) {
-      do {
-        const int j1 = L.way[j0];
-        L.p[j0] = L.p[j1];
-        j0 = j1;
-      } while (j0);
-    }
-    __syncthreads();
-  }
-  return true;
-}
 
 // ---- one window of both records in LDS ------------------------------------------------------------------------------------------------
 struct MotSide {
@@ -169,25 +92,6 @@ __device__ __forceinline__ void mot_span(const int* __restrict__ off, long long 
   lo = min(max(a, 0), total);
   n = min(max(b, lo), total) - lo;
   n = min(n, MOT_RMAX);
-}
-
-// The indices i < n with flag set, in rising order -> list[0 .. count-1]; returns count (uniform).  n <= 256.  Ends with a __syncthreads.
-__device__ __forceinline__ int mot_compact(bool flag, int* __restrict__ list, int* __restrict__ wsum) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int before = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[w] = __popcll(b);
-  __syncthreads();
-  int base = 0, total = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = wsum[k];
-    if (k < w) base += c;
-    total += c;
-  }
-  if (flag) list[base + before] = tid;
-  __syncthreads();
-  return total;
 }
 
 struct ClearShared {

@@ -1,7 +1,8 @@
 """Streaming tracking: links the boxes of consecutive windows into per-vehicle tracks on the device (`mmd_track_update`, csrc/track.hip).
 
 The rule - a greedy IoU tracker with a constant-velocity alpha-beta model, alpha = 1 - is written out in DESIGN.md (streaming tracking)
-and in include/mmdistill.h.  `AudioDetector.track_stream` launches the kernel inside its captured chain, in front of every group's
+and in include/mmdistill.h.  `TrackConfig(assign="optimal")` pairs tracks and boxes by the matching of maximum IoU sum instead of greedily
+(`mmd_track_update_assign`; DESIGN.md, tracking evaluation, says when to prefer which).  `AudioDetector.track_stream` launches the kernel inside its captured chain, in front of every group's
 record append; `track_rows` runs the same kernel over a detection record that already exists (saved detections)."""
 from __future__ import annotations
 
@@ -16,6 +17,7 @@ from . import _lib
 SLOT_WORDS = 16             # int32 words per slot of the state (include/mmdistill.h: mmd_track_update)
 DET_MAX = 256               # detections of one window that take part
 GROUP_MAX = 1024            # windows per launch
+ASSIGN = {"greedy": 0, "optimal": 1}      # the `assign` argument of mmd_track_update_assign / mmd_track_update_bank_assign
 
 
 @dataclass(frozen=True)
@@ -25,6 +27,7 @@ class TrackConfig:
     max_age: int = 2            # a track is freed once it has been missed more than this many windows in a row
     birth_score: float = 0.0    # smallest score at which an unmatched detection starts a track
     max_tracks: int = 64        # live-track slots, 1 .. 256
+    assign: str = "greedy"      # "greedy": the largest IoU first; "optimal": the matching of maximum IoU sum per window
 
     def __post_init__(self):
         if not (0.0 < float(self.iou_min) <= 1.0):
@@ -37,9 +40,12 @@ class TrackConfig:
             raise ValueError("TrackConfig: birth_score is NaN")
         if int(self.max_tracks) != self.max_tracks or not (1 <= self.max_tracks <= 256):
             raise ValueError("TrackConfig: max_tracks = %r (1 .. 256)" % (self.max_tracks,))
+        if not isinstance(self.assign, str) or self.assign not in ASSIGN:
+            raise ValueError("TrackConfig: assign = %r ('greedy' or 'optimal')" % (self.assign,))
 
     def key(self) -> tuple:
-        return (float(self.iou_min), float(self.beta), int(self.max_age), float(self.birth_score), int(self.max_tracks))
+        key = (float(self.iou_min), float(self.beta), int(self.max_age), float(self.birth_score), int(self.max_tracks))
+        return key if self.assign == "greedy" else key + (self.assign,)
 
 
 def new_state(device, cfg: TrackConfig) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -51,9 +57,13 @@ def new_state(device, cfg: TrackConfig) -> Tuple[torch.Tensor, torch.Tensor]:
 def update(rows: torch.Tensor, cnt: torch.Tensor, ctl: torch.Tensor, rec_count: torch.Tensor, rec_cap: int, rec_track: torch.Tensor,
            state, cfg: TrackConfig):
     """One launch of mmd_track_update on the current stream for the group rows [B, cap_img, 6] / cnt [B] / ctl = {n_valid, first_window}
-    - in front of the mmd_det_record_append that advances rec_count."""
-    _lib.call("mmd_track_update", rows, cnt, rows.shape[0], rows.shape[1], ctl, rec_count, int(rec_cap), rec_track, state[0], state[1],
-              int(cfg.max_tracks), float(cfg.iou_min), float(cfg.beta), int(cfg.max_age), float(cfg.birth_score))
+    - in front of the mmd_det_record_append that advances rec_count (cfg.assign = "optimal": of mmd_track_update_assign)."""
+    args = (rows, cnt, rows.shape[0], rows.shape[1], ctl, rec_count, int(rec_cap), rec_track, state[0], state[1], int(cfg.max_tracks),
+            float(cfg.iou_min), float(cfg.beta), int(cfg.max_age), float(cfg.birth_score))
+    if cfg.assign == "greedy":
+        _lib.call("mmd_track_update", *args)
+    else:
+        _lib.call("mmd_track_update_assign", *args, ASSIGN[cfg.assign])
 
 
 def new_bank_state(device, cfg: TrackConfig, n_sessions: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -66,9 +76,12 @@ def update_bank(rows: torch.Tensor, cnt: torch.Tensor, n_valid: torch.Tensor, wi
                 rec_count: torch.Tensor, rec_cap: int, rec_track: torch.Tensor, state, cfg: TrackConfig):
     """One launch of mmd_track_update_bank on the current stream: `update` for a group whose row i is window win_idx[i] of session
     win_sess[i], on the state of `new_bank_state` - in front of the mmd_det_record_append_bank that advances rec_count."""
-    _lib.call("mmd_track_update_bank", rows, cnt, rows.shape[0], rows.shape[1], n_valid, win_sess, win_idx, state[0].shape[0], rec_count,
-              int(rec_cap), rec_track, state[0], state[1], int(cfg.max_tracks), float(cfg.iou_min), float(cfg.beta), int(cfg.max_age),
-              float(cfg.birth_score))
+    args = (rows, cnt, rows.shape[0], rows.shape[1], n_valid, win_sess, win_idx, state[0].shape[0], rec_count, int(rec_cap), rec_track,
+            state[0], state[1], int(cfg.max_tracks), float(cfg.iou_min), float(cfg.beta), int(cfg.max_age), float(cfg.birth_score))
+    if cfg.assign == "greedy":
+        _lib.call("mmd_track_update_bank", *args)
+    else:
+        _lib.call("mmd_track_update_bank_assign", *args, ASSIGN[cfg.assign])
 
 
 def overflow_message(cfg: TrackConfig, window) -> str:
