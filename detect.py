@@ -5,7 +5,7 @@
                      [--window_s SECONDS [--hop_s SECONDS] [--batch N]
                       [--track [--track_iou X] [--track_beta X] [--track_max_age N] [--track_max N]
                                [--track_assign greedy|optimal]]]
-                     [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS]
+                     [--resample | --sample_rate R] [--chunk_s SECONDS | --live_s SECONDS] [--ema]
     python detect.py --config_file F --checkpoint P --input X0 --input X1 [--input X2 ...] --output out.csv
                      --window_s SECONDS --chunk_s SECONDS [--any_rate] [--hop_s SECONDS] [--batch N] [--track ...]
 
@@ -14,7 +14,9 @@ samples / 32768).  The waveforms go through the device front end (mel spectrogra
 image_size: what mp3_to_pkl.py:31-41, `MultimodalDetection.__getitem__` and `Resizer` make of a recording upstream), the student's
 eval-mode forward and the post-processing of the reference's evaluation (score > conf_threshold, class filter, NMS).  The detection
 settings (image_size, conf_threshold, nms_threshold, valid_labels, precision, compound_coef) are read from the cfg file like train.py
-and evaluate.py read them.  No teacher is built or loaded.  Output: one CSV row per box, columns clip,x1,y1,x2,y2,score,label.
+and evaluate.py read them.  No teacher is built or loaded.  With --ema the student gets the checkpoint's averaged weights
+(`state_dict_ema`, written by a training run with cfg ema_decay) instead of its raw ones; a checkpoint without them is refused.  Output: one CSV row per box, columns
+clip,x1,y1,x2,y2,score,label.
 
 With --window_s the input is ONE recording (a `.wav`, or a `.npy` of shape [8, N]) and the detector slides over it on the device
 (`AudioDetector.detect_stream`): windows of round(window_s * 44100) samples every round(hop_s * 44100) samples (hop_s defaults to
@@ -178,8 +180,10 @@ def parse_args(argv=None):
     ap.add_argument("--chunk_s", type=float, default=None, help="read the recording this many seconds at a time into a live session (with --window_s)")
     ap.add_argument("--any_rate", action="store_true", help="several .wav inputs, each at the rate in its header (with --window_s --chunk_s)")
     ap.add_argument("--live_s", type=float, default=None, help="read a recording of any rate this many seconds at a time into a live session that resamples (with --window_s)")
+    ap.add_argument("--ema", action="store_true", help="load the checkpoint's averaged weights (state_dict_ema: cfg ema_decay), not its raw ones")
     a = ap.parse_args(argv)
     a.inputs, a.input = a.input, a.input[0]
+    a.ema_state = None                    # main(): the averaged state dict, with --ema
     check_flags(a)
     if len(a.inputs) == 1 and a.batch is None:
         a.batch = 8
@@ -271,9 +275,11 @@ def load_detector(a, cfg) -> AudioDetector:
     """The student of the cfg file with the checkpoint's weights, on the device.  Every mode calls it behind its last host-side refusal."""
     torch.cuda.set_device(0)
     sspec, _ = T.load_student_state(int(cfg.get("compound_coef", 2)))
-    c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    state = getattr(a, "ema_state", None)      # --ema: read in main(), in front of every mode's first device work
+    if state is None:
+        state = T.TR.checkpoint_student_state(torch.load(a.checkpoint, map_location="cpu", weights_only=False), False, a.checkpoint)
     det = AudioDetector.from_step_config(sspec, DEVICE, T.step_config(cfg))
-    det.load(c["state_dict"] if "state_dict" in c else c)
+    det.load(state)
     return det
 
 
@@ -393,6 +399,9 @@ def main(argv=None):
         track = TrackConfig(iou_min=a.track_iou, beta=a.track_beta, max_age=a.track_max_age, max_tracks=a.track_max,
                             assign=a.track_assign)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
+    if a.ema:
+        # a checkpoint without averaged weights is refused here, on the host: some modes touch the device before they load the detector
+        a.ema_state = T.TR.checkpoint_student_state(torch.load(a.checkpoint, map_location="cpu", weights_only=False), True, a.checkpoint)
     if len(a.inputs) > 1:
         mode = run_bank_any_rate if a.any_rate else run_bank
     elif a.live_s is not None:

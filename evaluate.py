@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Evaluation entry point with the reference's CLI (evaluate.py:51-170 upstream):
 
-    python evaluate.py --config_file F --checkpoint P [--overwrite JSON]
+    python evaluate.py --config_file F --checkpoint P [--overwrite JSON] [--ema]
+
+--ema: the checkpoint's averaged weights (`state_dict_ema`, written by a run with cfg ema_decay) instead of its raw ones (`state_dict`).
 
 The student's detections (score > conf_threshold, class filter, NMS — the same device kernels that make the
 teachers' pseudo-labels) are scored against the merged multi-teacher pseudo ground truth with the reference's
@@ -38,12 +40,21 @@ def main(argv=None):
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--overwrite", type=str, default=None)
     ap.add_argument("--just_plot", action="store_true")
+    ap.add_argument("--ema", action="store_true", help="evaluate the checkpoint's averaged weights (state_dict_ema: cfg ema_decay)")
     a = ap.parse_args(argv)
     cfg, _ = T.parse_config(["--config_file", a.config_file] + (["--overwrite", a.overwrite] if a.overwrite else []))
+    ckpt_state = None
+    if a.ema:
+        # refused on the host, before the device is touched: no checkpoint, or one without averaged weights
+        if not a.checkpoint:
+            raise ValueError("--ema reads the averaged weights of a checkpoint: it needs --checkpoint")
+        ckpt_state = T.TR.checkpoint_student_state(torch.load(a.checkpoint, map_location="cpu", weights_only=False), True, a.checkpoint)
     torch.cuda.set_device(0)
     dev = "cuda:0"
     sspec, sstate, tspecs, tstates = T.load_states(cfg, int(cfg.get("compound_coef", 2)))
-    if a.checkpoint:
+    if ckpt_state is not None:
+        sstate = ckpt_state
+    elif a.checkpoint:
         c = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
         sstate = c["state_dict"] if "state_dict" in c else c
     eng = DistillEngine(sspec, tspecs, dev, T.step_config(cfg))

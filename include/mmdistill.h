@@ -284,6 +284,17 @@ int mmd_memset_async(void* p, int value, long long bytes, hipStream_t stream);
 // Capturable: the replay loop of a captured step then issues no RNG / elementwise launches of its own.
 int mmd_drop_scale(float* out, const float* keep, int n_skip, int batch, unsigned long long seed, unsigned long long* state, hipStream_t stream);
 
+// Exponential moving average of the student's weights, one update: ema = fmaf(1 - d, p - ema, ema) per element over up to three
+// (live, ema) fp32 segment pairs of n0 / n1 / n2 floats (the flat parameter buffer, the BatchNorm running means, the running variances)
+// in ONE launch.  ema_state [2] (device floats, zeroed by the caller when an average starts): ema_state[0] = n, the updates done before
+// this one, advanced to n + 1 by the call (exact up to 2^24); ema_state[1] = the d this update used: `decay` with warmup = 0,
+// min(decay, (1 + n) / (10 + n)) with warmup != 0.  No host read: capturable, and a replay advances the counter like a call.
+// The live buffers are only read; any length is allowed (float4 body, scalar tail), nothing at or behind ema[n] is written.
+// A zero length or a null (live, ema) pair is an empty segment.  Every non-null segment pointer must be 16-byte aligned; a misaligned
+// pointer, one null pointer of a pair with a positive length, a negative length, a null ema_state or a decay outside (0, 1)
+// -> MMD_EINVAL, nothing is launched.
+int mmd_ema_update(const float* p0, float* ema0, long long n0, const float* p1, float* ema1, long long n1, const float* p2, float* ema2, long long n2, float* ema_state, float decay, int warmup, hipStream_t stream);
+
 // clip_grad_norm_ on the flat gradient buffer (src/optimization/traditional.py:184-188).
 int mmd_clip_grad_norm(float* g, long long n, float max_norm, double* sumsq_ws, hipStream_t stream);
 

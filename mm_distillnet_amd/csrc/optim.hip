@@ -216,6 +216,61 @@ extern "C" int mmd_opt_step_gated(int mode, float* p, const float* g, float* m, 
   return mmd_check_launch();
 }
 
+// ---------------------------------------------------------------- exponential moving average of the student's weights
+// ema = fmaf(1 - d, p - ema, ema) over up to three (live, ema) fp32 segment pairs - the flat parameter buffer, the BatchNorm running means
+// and running variances - in ONE launch behind the optimizer's, inside the captured optimizer graph.  The averaged copy is what
+// EfficientDet-class detectors are evaluated on (decay 0.9998 upstream of the reference's detector family).
+// state [2] on the device, the adam_prep_kernel / adam_kernel split: a one-thread launch takes n = state[0], the updates done so far,
+// leaves d in state[1] and n + 1 in state[0]; the main launch reads d only.  warmup: d = min(decay, (1 + n) / (10 + n)), so the first
+// updates follow the young weights instead of averaging the initialisation in for 1 / (1 - decay) steps.  n is a float: exact up to 2^24
+// updates, where it stops advancing and the warm-up quotient (0.9999995) has long been above any decay in use.
+struct EmaSegs { const float* p[3]; float* e[3]; long long n[3]; };
+__global__ void ema_prep_kernel(float* state, float decay, int warmup) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float n = state[0];
+  float d = decay;
+  if (warmup) d = fminf(decay, (1.f + n) / (10.f + n));
+  state[0] = n + 1.f;
+  state[1] = d;
+}
+__global__ __launch_bounds__(256) void ema_kernel(EmaSegs s, const float* state) {
+  const float w = 1.f - state[1];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float* __restrict__ p = s.p[k];
+    float* __restrict__ e = s.e[k];
+    const size_t n = (size_t)s.n[k], n4 = n / 4;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+      const float4 pp = mmd_ld4(p + i * 4);
+      float4 ee = mmd_ld4(e + i * 4);
+      ee.x = fmaf(w, pp.x - ee.x, ee.x); ee.y = fmaf(w, pp.y - ee.y, ee.y);
+      ee.z = fmaf(w, pp.z - ee.z, ee.z); ee.w = fmaf(w, pp.w - ee.w, ee.w);
+      mmd_st4(e + i * 4, ee);
+    }
+    const size_t t = n4 * 4 + threadIdx.x;          // scalar tail: the last n % 4 elements, block 0
+    if (blockIdx.x == 0 && threadIdx.x < 3 && t < n) e[t] = fmaf(w, p[t] - e[t], e[t]);
+  }
+}
+extern "C" int mmd_ema_update(const float* p0, float* ema0, long long n0, const float* p1, float* ema1, long long n1, const float* p2,
+                              float* ema2, long long n2, float* ema_state, float decay, int warmup, hipStream_t stream) {
+  if (!ema_state || !(decay > 0.f && decay < 1.f)) return MMD_EINVAL;
+  EmaSegs s{{p0, p1, p2}, {ema0, ema1, ema2}, {n0, n1, n2}};
+  long long total4 = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (s.n[k] < 0) return MMD_EINVAL;
+    if (!s.p[k] && !s.e[k]) s.n[k] = 0;             // a null pair is an empty segment
+    if (s.n[k] > 0 && (!s.p[k] || !s.e[k])) return MMD_EINVAL;
+    if (((uintptr_t)s.p[k] | (uintptr_t)s.e[k]) & 15) return MMD_EINVAL;
+    total4 += (s.n[k] + 3) / 4;
+  }
+  hipLaunchKernelGGL(ema_prep_kernel, dim3(1), dim3(64), 0, stream, ema_state, decay, warmup ? 1 : 0);
+  if (total4 > 0) {
+    int blocks = cdiv(total4, 256); if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(ema_kernel, dim3(blocks), dim3(256), 0, stream, s, (const float*)ema_state);
+  }
+  return mmd_check_launch();
+}
+
 // ---------------------------------------------------------------- drop-connect masks on the device
 // reference: drop_connect (src/YetAnotherEfficientNet.py:173-182): per sample and skip block, mask = floor(keep + U[0, 1)), scale = mask / keep.
 // One launch INSIDE the captured step draws all of them, so the replay loop holds no ATen RNG / floor / div / copy launches:

@@ -10,7 +10,9 @@ their gradients, the student backward, gradient all-reduce (RCCL, student gradie
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import numbers
 import os
 
 from dataclasses import dataclass, field
@@ -60,6 +62,17 @@ class StepConfig:
     augment: bool = False              # cfg audio_augmentation_merge (ModelWithNMSLossAugmented.forward augment=True)
     seed: int = 0                      # cfg `seed` (train.py:120 make_reproducible_run): keys the device-side drop-connect draws
     precision: str = "fp32"            # "bf16": 1x1-conv GEMMs of every net on the bf16 MFMA (fp32 accumulate, fp32 tensors)
+    ema_decay: float = 0.0             # extension key: 0 = off; 0 < d < 1: an exponential moving average of the student's weights and BatchNorm
+                                       # running statistics rides behind every optimizer launch (csrc/optim.hip mmd_ema_update; 0.9998 is
+                                       # the EfficientDet recipe's)
+    ema_warmup: bool = True            # d = min(ema_decay, (1 + n) / (10 + n)) at the n-th update (n from 0)
+
+    def __post_init__(self):
+        d = self.ema_decay
+        if isinstance(d, bool) or not isinstance(d, numbers.Real) or not (d == 0 or 0.0 < d < 1.0):
+            raise ValueError(f"ema_decay {d!r}: 0 (off) or a decay with 0 < d < 1")
+        if not isinstance(self.ema_warmup, bool):
+            raise ValueError(f"ema_warmup {self.ema_warmup!r}: True or False")
 
 
 class DistillEngine:
@@ -100,6 +113,12 @@ class DistillEngine:
         # device-side hyper-parameters [lr, beta1, beta2, eps, weight_decay, momentum]: a captured graph sees scheduler updates
         self.hyper = torch.tensor([cfg.lr, cfg.b1, cfg.b2, cfg.eps, cfg.weight_decay, cfg.momentum], device=device)
         self.head_active = torch.zeros(1, dtype=torch.int32, device=device)
+        # cfg ema_decay > 0: the averaged copies of (flat, rmean, rvar) and [updates so far, decay of the last update] on the device; one
+        # launch behind the optimizer's keeps them up to date (optimizer_body).  Off: no buffer, no launch
+        self.ema_flat = self.ema_rmean = self.ema_rvar = self.ema_state = self._ema_scratch = None
+        if cfg.ema_decay > 0:
+            self.ema_flat, self.ema_rmean, self.ema_rvar = ps.flat.clone(), ps.rmean.clone(), ps.rvar.clone()
+            self.ema_state = torch.zeros(2, device=device)
         self.overflow = torch.zeros(1, dtype=torch.int32, device=device)
         self.ws = Arena(device, 256 << 20)        # loss / pseudo-label workspaces (bump, reset per step)
         self.head_ranges = self._head_ranges()
@@ -182,6 +201,47 @@ class DistillEngine:
         self.student.load_state(student_state)
         for m, net in self.teachers.items():
             net.load_state(teacher_states[m])
+        self.reset_ema()
+
+    # ------------------------------------------------------------------ weight averaging (cfg ema_decay)
+    def _ema_pairs(self):
+        ps = self.student.ps
+        return ((ps.flat, self.ema_flat), (ps.rmean, self.ema_rmean), (ps.rvar, self.ema_rvar))
+
+    def reset_ema(self):
+        """Start the average again from the live weights, with 0 updates: whoever writes the student's state (load, a broadcast from
+        rank 0, a resume from a checkpoint without an average) calls it.  A no-op with ema_decay = 0."""
+        if self.ema_flat is None:
+            return
+        for live, ema in self._ema_pairs():
+            ema.copy_(live)
+        self.ema_state.zero_()
+
+    def ema_updates(self) -> int:
+        return int(self.ema_state[0].item())
+
+    def _ema_exchange(self):
+        """contents of (flat, rmean, rvar) <-> the averaged copies, by device copies through one scratch buffer: no pointer moves, so
+        the captured graphs stay valid"""
+        if self._ema_scratch is None:
+            self._ema_scratch = torch.empty_like(self.ema_flat)
+        for live, ema in self._ema_pairs():
+            tmp = self._ema_scratch[:live.numel()]
+            tmp.copy_(live); live.copy_(ema); ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the student computes with the averaged weights and running statistics (validation, export); the live ones
+        wait in the EMA buffers and come back on exit, bit for bit.  No training step may run inside."""
+        if self.ema_flat is None:
+            raise RuntimeError("ema_weights: the engine keeps no averaged weights (cfg ema_decay = 0)")
+        self._ema_exchange()
+        self.student.refresh()
+        try:
+            yield self
+        finally:
+            self._ema_exchange()
+            self.student.refresh()
 
     def set_lr(self, lr: float):
         self.lr = float(lr)            # host copy in double (checkpoints carry it; the device copy is its fp32 rounding)
@@ -532,6 +592,11 @@ class DistillEngine:
         else:
             call("mmd_opt_step_gated", self.opt_mode, ps.flat, ps.grad, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head,
                  self.hyper, self.head_active, r[0], r[1], r[2], r[3], r[4], r[5], float(gs), ps.n_params)
+        if self.ema_flat is not None:
+            # reads ps.flat only, so its order against refresh_wt() does not matter.  Every rank holds the same weights after the
+            # all-reduced step, hence the same average: no collective
+            call("mmd_ema_update", ps.flat, self.ema_flat, ps.n_params, ps.rmean, self.ema_rmean, ps.bn_total, ps.rvar, self.ema_rvar,
+                 ps.bn_total, self.ema_state, float(cfg.ema_decay), 1 if cfg.ema_warmup else 0)
         self.student.refresh_wt()
 
     # ------------------------------------------------------------------ eager / graph drivers
@@ -571,8 +636,11 @@ class DistillEngine:
         torch.cuda.synchronize()
         # snapshot so the warm-up steps do not change the training trajectory
         ps = self.student.ps
-        snap = [t.clone() for t in (ps.flat, ps.rmean, ps.rvar, ps.nbt, self.exp_avg, self.exp_avg_sq, self.adam_main,
-                                    self.adam_head, self.head_active)]
+        # (the averaged weights and their update counter too: a warm-up step is not an update)
+        state = [ps.flat, ps.rmean, ps.rvar, ps.nbt, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head, self.head_active]
+        if self.ema_flat is not None:
+            state += [self.ema_flat, self.ema_rmean, self.ema_rvar, self.ema_state]
+        snap = [t.clone() for t in state]
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -599,8 +667,7 @@ class DistillEngine:
         self.g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_opt, capture_error_mode="thread_local"):
             self.optimizer_body()
-        for dst, src in zip((ps.flat, ps.rmean, ps.rvar, ps.nbt, self.exp_avg, self.exp_avg_sq, self.adam_main,
-                             self.adam_head, self.head_active), snap):
+        for dst, src in zip(state, snap):
             dst.copy_(src)
         self.student.refresh()
         torch.cuda.synchronize()

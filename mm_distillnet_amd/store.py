@@ -126,8 +126,14 @@ class ParamStore:
                 "fscale": self.fold_scale[o:o + c], "fshift": self.fold_shift[o:o + c]}
 
     # ---- state dict ---------------------------------------------------------------------
-    def load_state(self, state: Dict[str, torch.Tensor]) -> None:
-        """Import a reference-layout state dict (missing keys raise, like load_state_dict(strict=True))."""
+    def load_state(self, state: Dict[str, torch.Tensor], flat: Optional[torch.Tensor] = None, rmean: Optional[torch.Tensor] = None,
+                   rvar: Optional[torch.Tensor] = None) -> None:
+        """Import a reference-layout state dict (missing keys raise, like load_state_dict(strict=True)).
+        flat / rmean / rvar: all three or none - buffers shaped like the store's own that receive the state instead (the averaged
+        weights of a checkpoint); the store's buffers and its num_batches_tracked are then left alone."""
+        other = [t is not None for t in (flat, rmean, rvar)]
+        if any(other) and not all(other):
+            raise ValueError("load_state: flat, rmean and rvar go together")
         host = torch.zeros(self.n_params, dtype=torch.float32)
         rm = torch.zeros(self.bn_total, dtype=torch.float32)
         rv = torch.ones(self.bn_total, dtype=torch.float32)
@@ -153,14 +159,20 @@ class ParamStore:
             k = name + ".num_batches_tracked"
             if k in state:
                 nbt[i] = int(state[k])
+        if any(other):
+            flat.copy_(host); rmean.copy_(rm); rvar.copy_(rv)
+            return
         self.flat.copy_(host)
         self.rmean.copy_(rm)
         self.rvar.copy_(rv)
         self.nbt.copy_(nbt)
 
-    def export_state(self) -> Dict[str, torch.Tensor]:
-        host = self.flat.detach().cpu()
-        rm, rv, nbt = self.rmean.cpu(), self.rvar.cpu(), self.nbt.cpu()
+    def export_state(self, flat: Optional[torch.Tensor] = None, rmean: Optional[torch.Tensor] = None,
+                     rvar: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """The store's state in reference layout.  flat / rmean / rvar: buffers shaped like the store's own to export in their place (the
+        averaged weights); num_batches_tracked is always the store's."""
+        host = (self.flat if flat is None else flat).detach().cpu()
+        rm, rv, nbt = (self.rmean if rmean is None else rmean).cpu(), (self.rvar if rvar is None else rvar).cpu(), self.nbt.cpu()
         out: Dict[str, torch.Tensor] = {}
         bn_index = {n: i for i, n in enumerate(self.bn_names)}
         for key, shape, kind in state_layout(self.spec):

@@ -49,6 +49,36 @@ def optimizer_settings(cfg) -> Dict:
     raise Exception(f"Unsupported optimizer {name}")
 
 
+def ema_settings(cfg) -> Dict:
+    """cfg -> StepConfig keyword arguments of the weight averaging (extension keys, absent from the reference's cfg files -> off):
+    ema_decay (0 < d < 1; StepConfig refuses anything else) and ema_warmup (default True)."""
+    return {"ema_decay": cfg.getfloat("ema_decay", 0.0), "ema_warmup": bool(cfg.getboolean("ema_warmup", True))}
+
+
+def ema_validate_setting(cfg) -> bool:
+    """cfg ema_validate (default False): validate(), and with it best-checkpoint selection and early stopping, on the averaged weights"""
+    on = bool(cfg.getboolean("ema_validate", False))
+    if on and not cfg.getfloat("ema_decay", 0.0) > 0:
+        raise Exception("ema_validate = True needs averaged weights: set ema_decay (0 < d < 1)")
+    return on
+
+
+def ema_state_dict(eng) -> Dict:
+    """The averaged weights and running statistics in reference layout (num_batches_tracked: the live counters)"""
+    return eng.student.ps.export_state(flat=eng.ema_flat, rmean=eng.ema_rmean, rvar=eng.ema_rvar)
+
+
+def checkpoint_student_state(c: Dict, ema: bool, path: str) -> Dict:
+    """The student's state dict out of a loaded checkpoint `c` (or a bare state dict): the raw weights, or with `ema` the averaged ones.
+    Host work only: the tools call it before they touch the device."""
+    if ema:
+        if not isinstance(c, dict) or "state_dict_ema" not in c:
+            raise ValueError(f"{path}: --ema asks for the averaged weights, and this checkpoint holds no `state_dict_ema`: "
+                             "train.py writes it when the cfg sets ema_decay (0 < d < 1)")
+        return c["state_dict_ema"]
+    return c["state_dict"] if "state_dict" in c else c
+
+
 def _is_head(key: str) -> bool:
     return key.startswith(("regressor", "classifier"))
 
@@ -190,8 +220,13 @@ def save_checkpoint(state: Dict, is_best: bool, cfg) -> None:
 def checkpoint_state(eng, sched: LrSchedule, epoch: int, best_loss: float, best_epoch: int) -> Dict:
     # ("drop_draws": the device-side draw counter of the drop-connect masks - an extra key upstream ignores - so a resumed run goes on
     # with fresh masks instead of replaying the first epoch's)
-    return {"epoch": epoch + 1, "state_dict": eng.student.ps.export_state(), "best_loss": best_loss, "best_epoch": best_epoch,
-            "optimizer": optimizer_state_dict(eng), "scheduler": sched.state_dict(), "drop_draws": int(eng.drop_state[0].item())}
+    state = {"epoch": epoch + 1, "state_dict": eng.student.ps.export_state(), "best_loss": best_loss, "best_epoch": best_epoch,
+             "optimizer": optimizer_state_dict(eng), "scheduler": sched.state_dict(), "drop_draws": int(eng.drop_state[0].item())}
+    if eng.ema_flat is not None:
+        # (cfg ema_decay: the averaged weights beside the raw ones and the number of updates behind them - two more keys upstream ignores)
+        state["state_dict_ema"] = ema_state_dict(eng)
+        state["ema_updates"] = eng.ema_updates()
+    return state
 
 
 def resume_from_checkpoint(cfg, eng, sched: LrSchedule):
@@ -207,6 +242,15 @@ def resume_from_checkpoint(cfg, eng, sched: LrSchedule):
         sched.sync_lr(eng.lr)
         if "drop_draws" in c:
             eng.drop_state[0] = int(c["drop_draws"])
+        if eng.ema_flat is not None:
+            if "state_dict_ema" in c and "ema_updates" in c:
+                eng.student.ps.load_state(strip_module(c["state_dict_ema"]), flat=eng.ema_flat, rmean=eng.ema_rmean, rvar=eng.ema_rvar)
+                eng.ema_state.zero_()          # ([1], the decay of the last update, is rewritten by the next one)
+                eng.ema_state[0] = float(int(c["ema_updates"]))
+            else:
+                eng.reset_ema()
+                logger.warning(f"{path} holds no averaged weights (state_dict_ema / ema_updates): the average starts from the loaded "
+                               "weights with 0 updates")
         logger.info(f"Starting from epoch={start_epoch}")
         logger.info(f"Load {path}")
     return start_epoch, best_loss, best_epoch

@@ -11,9 +11,12 @@ epoch, state_dict, best_loss, best_epoch, optimizer, scheduler (src/optimization
 is a torch.optim state_dict over named_parameters() order and `scheduler` torch's scheduler state_dict (mm_distillnet_amd/trainer.py),
 so upstream can resume from these files and this script from upstream's.  Epoch logic as upstream (:966-1064): scheduler step on the
 epoch's last training loss, validate() every val_interval epochs, best / early stopping on the validation loss.
+Extension keys `ema_decay` / `ema_warmup` / `ema_validate` (absent -> off): an exponential moving average of the student's weights kept on
+the device, saved as two more checkpoint keys (`state_dict_ema`, `ema_updates`) and as only_parameters_student_best_ema.<rank>.
 """
 import argparse
 import configparser
+import contextlib
 import json
 import logging
 import os
@@ -98,7 +101,7 @@ def step_config(cfg) -> StepConfig:
                       augment=bool(cfg.getboolean("audio_augmentation_merge", False)) and method == "traditional_nms_augmented",
                       # extension key (absent from the reference's cfg files -> fp32): "bf16" = 1x1 convs on the bf16 MFMA
                       precision=cfg.get("precision", "fp32"), seed=cfg.getint("seed", 24),
-                      **TR.optimizer_settings(cfg))
+                      **TR.optimizer_settings(cfg), **TR.ema_settings(cfg))
 
 
 def augment_from_config(cfg, raw: bool, rank: int = 0):
@@ -235,6 +238,7 @@ def main(argv=None):
         import torch.distributed as dist
         dist.broadcast(eng.student.ps.flat, 0)
         eng.student.refresh()
+        eng.reset_ema()              # (cfg ema_decay: the average starts from the weights every rank now holds)
         if os.environ.get("MMD_COMM") == "rccl":
             eng.init_comm(rank)      # exchange through the C ABI's RCCL communicator (csrc/comm.hip) instead of torch.distributed
     # input_pipeline = raw: samples arrive as decoded frames (uint8/uint16/float mel stacks) and Normalizer/Resizer/transposes
@@ -290,6 +294,14 @@ def main(argv=None):
         p.copy_(t)
         return p.to(dev, non_blocking=True)
     no_validation = cfg.getboolean("no_validation", False)
+    # ema_decay / ema_warmup (extension keys, absent -> off: step_config): the engine averages the student's weights on the device behind
+    # every optimizer step.  ema_validate (absent -> False): validate() runs on the averaged weights, so the best checkpoint and early
+    # stopping follow the averaged model's validation loss
+    ema_on, ema_validate = eng.ema_flat is not None, TR.ema_validate_setting(cfg)
+
+    def run_validate(ep):
+        with (eng.ema_weights() if ema_validate else contextlib.nullcontext()):
+            return TR.validate(eng, val_set, cfg, ep, writer, to_batch, collate_fn, world)
     steps, captured, loss, val_loss = 0, False, float("nan"), float("nan")
     stop = False
     for epoch in range(start_epoch, n_epochs):
@@ -405,10 +417,12 @@ def main(argv=None):
             continue
         is_best = False
         if epoch % cfg.getint("val_interval", 1) == 0:
-            val_loss = TR.validate(eng, val_set, cfg, epoch, writer, to_batch, collate_fn, world)
+            val_loss = run_validate(epoch)
             is_best = val_loss < best_loss
             if is_best:
                 torch.save(eng.student.ps.export_state(), f"{cfg['exp_name']}/only_parameters_student_best.{rank}")
+                if ema_on:
+                    torch.save(TR.ema_state_dict(eng), f"{cfg['exp_name']}/only_parameters_student_best_ema.{rank}")
                 best_loss, best_epoch = val_loss, epoch + 1
             if epoch - best_epoch > cfg.getint("es_patience", 5) > 0:
                 logger.info(f"ES Epoch{epoch}. Lowest loss is {val_loss}")
@@ -422,7 +436,7 @@ def main(argv=None):
     writer.export_scalars_to_json(f"{cfg['exp_name']}/all_logs.{rank}.json")
     try:
         if no_validation and captured:
-            val_loss = TR.validate(eng, val_set, cfg, n_epochs, writer, to_batch, collate_fn, world)
+            val_loss = run_validate(n_epochs)
     finally:
         eng.close_comm()        # the C-ABI RCCL communicator (MMD_COMM=rccl) goes before the process group does
         if world > 1:
