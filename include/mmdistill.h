@@ -338,6 +338,24 @@ int mmd_nms_merge(const float* t0, const int* c0, const float* t1, const int* c1
 // in srcs / cnts -> MMD_EINVAL, nothing is launched.
 int mmd_nms_merge_n(const float* const* srcs, const int* const* cnts, int nsrc, float iou_threshold, int inclusive, int B, float* boxes, int* nbox, int maxg, unsigned long long* mask_ws, int* overflow, int merge01, int cap, float* big_ws, hipStream_t stream);
 
+// Weighted box fusion (Solovyev, Wang, Gabruseva 2021) over the rows mmd_nms_merge_n gathers (same sources, counts, clamping and merge01
+// rule; every gathered row remembers its source index 0..3, whichever image it came from): overlapping boxes of one label are averaged
+// with their scores as weights instead of suppressed.  The rule, in fp32 with separately rounded operations (no FMA contraction):
+// rows in the NMS's order (score descending, equal scores by gather index) are walked one at a time; a row joins, among the clusters
+// of its own label (labels compared as stored floats), the one whose current fused box has the best IoU (the NMS's arithmetic) with
+// it, provided IoU > iou_threshold (>= with inclusive != 0), the lowest cluster index on ties; joining advances the cluster in arrival
+// order: w = fmaxf(score, FLT_MIN), W += w, Xk += w * xk for the four coordinates, n += 1, the source's bit is set, the fused box becomes
+// Xk / W and its area (x2 - x1) * (y2 - y1) is recomputed.  Without such a cluster the row opens the next one, by the same advance from
+// zeroed sums (a lone box comes out as (w * xk) / w).  After the walk the clusters with at least min_votes distinct sources go out in
+// birth order: boxes [B, maxg, 5] (fused x1,y1,x2,y2, label), nbox [B], and into the nullable aux [B, maxg, 3] (W / n = mean member
+// weight, n members, distinct sources); rows at and behind nbox[b] are left as they were.
+// Capacity: more than maxg emitted clusters -> *overflow = 1, nbox = maxg, rows [0, maxg) are the first maxg emitted clusters.  More than
+// 1024 gathered rows in an image -> *overflow = 1 and the fusion runs over its first 1024 rows in gather order (there is no chunked
+// path and no global workspace: rows and clusters live in up to 86 016 B of LDS).  The outputs need no zeroing; `overflow` is sticky:
+// the caller zeroes it.  nsrc outside 1..4, min_votes outside 1..nsrc, a null entry in srcs / cnts, maxg <= 0 or cap <= 0 ->
+// MMD_EINVAL, nothing is launched.
+int mmd_wbf_merge_n(const float* const* srcs, const int* const* cnts, int nsrc, float iou_threshold, int inclusive, int B, float* boxes, int* nbox, int maxg, float* aux, int min_votes, int* overflow, int merge01, int cap, hipStream_t stream);
+
 // Floats per image of `big_ws` for NMS lists of up to nmax rows (0 when nmax <= 1024).  mmd_nms_merge: nmax = nteachers * cap * (merge01 ? 2 : 1).
 int mmd_nms_ws_floats(int nmax);
 

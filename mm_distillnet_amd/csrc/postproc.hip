@@ -8,6 +8,7 @@
 // Reference quirk kept: the score emitted for a kept box is the score of the idx-th OVER-THRESHOLD
 // candidate, idx being the box's index in the class-filtered list (src/utils/utils.py:193-213).
 #include "common.h"
+#include <cfloat>
 
 #define PP_CAP 1024          // candidates per image the single-pass (all-in-LDS) NMS handles; longer lists take the chunked path
 // Capacities are run-time arguments (`cap` = rows per image of the candidate / label arrays).  The reference has no cap at all
@@ -196,6 +197,25 @@ __device__ __forceinline__ bool nms_hit(float ix1, float iy1, float ix2, float i
   return inclusive ? (ovr >= thr) : (ovr > thr);
 }
 
+// Bitonic sort of (skey, sidx) in LDS by a 1024-thread block: descending score, ascending index on ties, over the smallest power of two
+// >= n (>= 64) slots: the slots past n hold -inf keys and sort behind every row; a teacher's ~100 candidates need 28 barrier stages
+// instead of the 55 of a 1024-wide sort.  Ends on a barrier.
+__device__ __forceinline__ void pp_lds_sort(float* skey, int* sidx, int n, int tid) {
+  int PS = 64;
+  while (PS < n) PS <<= 1;
+  for (int k = 2; k <= PS; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      int ixj = tid ^ j;
+      if (ixj > tid && ixj < PS) {
+        float k0 = skey[tid], k1 = skey[ixj]; int i0 = sidx[tid], i1 = sidx[ixj];
+        bool first_before = (k0 > k1) || (k0 == k1 && i0 < i1);     // "tid element sorts before ixj element"
+        bool up = ((tid & k) == 0);
+        if (up ? !first_before : first_before) { skey[tid] = k1; skey[ixj] = k0; sidx[tid] = i1; sidx[ixj] = i0; }
+      }
+      __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(1024) void pp_nms_kernel(NmsArgs a) {
   __shared__ float skey[PP_CAP];
   __shared__ int sidx[PP_CAP];
@@ -264,21 +284,7 @@ __global__ __launch_bounds__(1024) void pp_nms_kernel(NmsArgs a) {
     if (tid < n) myscore = row_ptr(tid)[4];
     skey[tid] = myscore; sidx[tid] = tid;
     __syncthreads();
-    // bitonic sort, descending score, ascending index on ties, over the smallest power of two >= n (>= 64) slots: the slots past n hold
-    // -inf keys and sort behind every row; a teacher's ~100 candidates need 28 barrier stages instead of the 55 of a 1024-wide sort
-    int PS = 64;
-    while (PS < n) PS <<= 1;
-    for (int k = 2; k <= PS; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        int ixj = tid ^ j;
-        if (ixj > tid && ixj < PS) {
-          float k0 = skey[tid], k1 = skey[ixj]; int i0 = sidx[tid], i1 = sidx[ixj];
-          bool first_before = (k0 > k1) || (k0 == k1 && i0 < i1);     // "tid element sorts before ixj element"
-          bool up = ((tid & k) == 0);
-          if (up ? !first_before : first_before) { skey[tid] = k1; skey[ixj] = k0; sidx[tid] = i1; sidx[ixj] = i0; }
-        }
-        __syncthreads();
-      }
+    pp_lds_sort(skey, sidx, n, tid);
     if (tid < n) stage_box(tid, sidx[tid]);
     __syncthreads();
     const int words = (n + 63) >> 6;
@@ -465,6 +471,181 @@ extern "C" int mmd_nms_merge_n(const float* const* srcs, const int* const* cnts,
   a.in_cap = cap; a.nmax = nsrc * cap * (a.merge01 ? 2 : 1); a.big_ws = big_ws; a.P = pp_pow2(a.nmax);
   a.big_stride = mmd_nms_ws_floats(a.nmax);
   hipLaunchKernelGGL(pp_nms_kernel, dim3(B), dim3(1024), 0, stream, a);
+  return mmd_check_launch();
+}
+
+// ---- weighted box fusion over the same gathered rows (one block per image): the cross-teacher merge that averages overlapping boxes
+// of one label with their scores as weights instead of keeping the best and dropping the others (Solovyev, Wang, Gabruseva 2021).
+// The rule, in fp32 with separately rounded operations (tests/wbf_ref.py restates it):
+//   rows sorted as for the NMS (score desc, gather index asc) and walked one at a time; a row joins, among the clusters of its own
+//   label, the one whose current fused box has the largest IoU (nms_hit's operations) above the threshold, the lowest cluster index on ties; joining:
+//   w = fmaxf(score, FLT_MIN), W += w, Xk += w * xk, n += 1, source bit set, fused box = Xk / W, area recomputed; without a candidate
+//   the row opens the next cluster, which is the same advance from zeroed sums (so a lone box comes out as (w * xk) / w).
+// The whole block gathers and sorts; the walk - sequential in rows, parallel over clusters - runs in wave 0 alone, lane l owning the
+// clusters l, l + 64, ...: every cluster's LDS words are written and read by one lane only, so the loop needs no barrier and no fence,
+// and a wave arg-max (IoU desc, cluster index asc) picks the winner across lanes.
+struct WbfArgs {
+  const float* src[4]; const int* cnt[4]; int nsrc;
+  float thr; int inclusive; int merge01; int in_cap;
+  float* out; int* out_cnt; int out_cap; float* aux; int min_votes; int* overflow;
+  int rows;           // LDS slots = threads: the power of two (>= 64) >= min(PP_CAP, nsrc * in_cap (* 2 with merge01))
+};
+#define WBF_LDS_PER_ROW 84      // rbox, cbox, csum: 3 x 16 B; skey, sidx, rlabel, rsrc, carea, clabel, cW, cn, cbits: 9 x 4 B
+#define WBF_NONE 0x7fffffff
+
+// Every operation of the fusion is rounded on its own, as tests/wbf_ref.py restates it.  The __f*_rn forms do not say that to the
+// compiler: they are plain operators inlined from a header compiled with contraction on, and a product still melts into the sum behind
+// it (the intersection into the union, w * xk into Xk).  So the arithmetic below is written with operators inside contract(off) blocks.
+__device__ __forceinline__ float wbf_area(float4 r) {
+#pragma clang fp contract(off)
+  return (r.z - r.x) * (r.w - r.y);
+}
+// nms_hit's IoU
+__device__ __forceinline__ float wbf_iou(float4 r, float ra, float4 c, float ca) {
+#pragma clang fp contract(off)
+  float xx1 = fmaxf(r.x, c.x), yy1 = fmaxf(r.y, c.y);
+  float xx2 = fminf(r.z, c.z), yy2 = fminf(r.w, c.w);
+  float ww = fmaxf(0.f, xx2 - xx1), hh = fmaxf(0.f, yy2 - yy1);
+  float inter = ww * hh;
+  float uni = (ra + ca) - inter;
+  return inter / uni;
+}
+// one cluster's advance by a row of weight w: W += w, Xk += w * xk, fused box = Xk / W
+__device__ __forceinline__ float4 wbf_advance(float& W, float4& S, float w, float4 r) {
+#pragma clang fp contract(off)
+  W = W + w;
+  float px = w * r.x, py = w * r.y, pz = w * r.z, pw = w * r.w;
+  S.x = S.x + px; S.y = S.y + py; S.z = S.z + pz; S.w = S.w + pw;
+  return make_float4(S.x / W, S.y / W, S.z / W, S.w / W);
+}
+
+__global__ __launch_bounds__(1024) void pp_wbf_kernel(WbfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char wbf_lds[];
+  const int R = a.rows, b = blockIdx.x, tid = threadIdx.x;      // blockDim.x == R
+  float4* rbox = reinterpret_cast<float4*>(wbf_lds);            // rows in sorted order
+  float4* cbox = rbox + R;                                      // clusters: fused box, weighted coordinate sums
+  float4* csum = cbox + R;
+  float* skey = reinterpret_cast<float*>(csum + R);             // sort key = score; after the sort: the score of sorted slot t
+  int* sidx = reinterpret_cast<int*>(skey + R);
+  float* rlabel = reinterpret_cast<float*>(sidx + R);
+  int* rsrc = reinterpret_cast<int*>(rlabel + R);
+  float* carea = reinterpret_cast<float*>(rsrc + R);
+  float* clabel = carea + R;
+  float* cW = clabel + R;
+  int* cn = reinterpret_cast<int*>(cW + R);
+  int* cbits = cn + R;
+  // gather: pp_nms_kernel's mode 1 (image 1 takes image 0's rows in front of its own when it has rows itself), without a chunked path
+  int cnts[4] = {0, 0, 0, 0}, cnts0[4] = {0, 0, 0, 0}, n = 0, n0 = 0;
+  for (int s = 0; s < a.nsrc; ++s) { cnts[s] = max(0, min(a.cnt[s][b], a.in_cap)); n += cnts[s]; }
+  if (a.merge01 && b == 1 && n > 0) {
+    for (int s = 0; s < a.nsrc; ++s) { cnts0[s] = max(0, min(a.cnt[s][0], a.in_cap)); n0 += cnts0[s]; }
+    n += n0;
+  }
+  if (n > PP_CAP) { if (tid == 0) *a.overflow = 1; n = PP_CAP; }      // the fusion of the FIRST 1024 rows in gather order
+  if (n <= 0) { if (tid == 0) a.out_cnt[b] = 0; return; }
+  auto row_ptr = [&](int i, int& s) -> const float* {       // gathered row i and the source (teacher) it came from, whichever image
+    int img = b;
+    s = 0;
+    if (i < n0) {
+      while (s < a.nsrc - 1 && i >= cnts0[s]) { i -= cnts0[s]; ++s; }
+      img = 0;
+    } else {
+      i -= n0;
+      while (s < a.nsrc - 1 && i >= cnts[s]) { i -= cnts[s]; ++s; }
+    }
+    return a.src[s] + ((size_t)img * a.in_cap + i) * 6;
+  };
+  int s = 0;
+  skey[tid] = tid < n ? row_ptr(tid, s)[4] : -INFINITY; sidx[tid] = tid;
+  __syncthreads();
+  pp_lds_sort(skey, sidx, n, tid);
+  if (tid < n) {
+    const float* r = row_ptr(sidx[tid], s);
+    rbox[tid] = make_float4(r[0], r[1], r[2], r[3]); rlabel[tid] = r[5]; rsrc[tid] = s;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  // ---------------- the walk: wave 0, no barrier from here on
+  const int lane = tid;
+  int nc = 0;
+  for (int i = 0; i < n; ++i) {
+    const float4 rb = rbox[i];
+    const float lb = rlabel[i];
+    const float ra = wbf_area(rb);
+    float best = 0.f; int bc = WBF_NONE;          // this lane's best candidate: ascending c and a strict >, so its lowest index on ties
+    for (int c = lane; c < nc; c += 64) {
+      if (clabel[c] != lb) continue;
+      const float4 cb = cbox[c];
+      const float ovr = wbf_iou(rb, ra, cb, carea[c]);
+      const bool cand = a.inclusive ? (ovr >= a.thr) : (ovr > a.thr);
+      if (cand && (bc == WBF_NONE || ovr > best)) { best = ovr; bc = c; }
+    }
+    if (__ballot(bc != WBF_NONE)) {               // (wave-uniform) arg-max across the lanes: a total order, so every lane ends on the winner
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64); const int oc = __shfl_xor(bc, o, 64);
+        if (oc != WBF_NONE && (bc == WBF_NONE || ob > best || (ob == best && oc < bc))) { best = ob; bc = oc; }
+      }
+    }
+    const bool fresh = bc == WBF_NONE;
+    const int c = fresh ? nc : bc;
+    if ((c & 63) == lane) {                       // the owner advances the cluster
+      const float w = fmaxf(skey[i], FLT_MIN);
+      float W = 0.f; float4 S = make_float4(0.f, 0.f, 0.f, 0.f); int m = 0, bits = 0;
+      if (!fresh) { W = cW[c]; S = csum[c]; m = cn[c]; bits = cbits[c]; }
+      const float4 f = wbf_advance(W, S, w, rb);
+      cW[c] = W; csum[c] = S; cn[c] = m + 1; cbits[c] = bits | (1 << rsrc[i]);
+      cbox[c] = f; carea[c] = wbf_area(f);
+      if (fresh) clabel[c] = lb;
+    }
+    nc += fresh ? 1 : 0;
+  }
+  // ---------------- emit the clusters with enough distinct sources, in birth order
+  int nk = 0;
+  for (int c0 = 0; c0 < nc; c0 += 64) {
+    const int c = c0 + lane;
+    const int votes = c < nc ? __popc(cbits[c]) : 0;
+    const bool keep = c < nc && votes >= a.min_votes;
+    const unsigned long long m = __ballot(keep);
+    const int k = nk + __popcll(m & ((1ull << lane) - 1ull));
+    if (keep && k < a.out_cap) {
+      const float4 f = cbox[c];
+      float* o = a.out + ((size_t)b * a.out_cap + k) * 5;
+      o[0] = f.x; o[1] = f.y; o[2] = f.z; o[3] = f.w; o[4] = clabel[c];
+      if (a.aux) {
+        float* x = a.aux + ((size_t)b * a.out_cap + k) * 3;
+        x[0] = cW[c] / (float)cn[c]; x[1] = (float)cn[c]; x[2] = (float)votes;
+      }
+    }
+    nk += __popcll(m);
+  }
+  if (lane == 0) {
+    if (nk > a.out_cap) { *a.overflow = 1; nk = a.out_cap; }
+    a.out_cnt[b] = nk;
+  }
+}
+
+extern "C" int mmd_wbf_merge_n(const float* const* srcs, const int* const* cnts, int nsrc, float iou_threshold, int inclusive, int B,
+                               float* boxes, int* nbox, int maxg, float* aux, int min_votes, int* overflow, int merge01, int cap,
+                               hipStream_t stream) {
+  if (!srcs || !cnts || !boxes || !nbox || !overflow || B <= 0 || nsrc < 1 || nsrc > 4 || maxg <= 0 || cap <= 0) return MMD_EINVAL;
+  if (min_votes < 1 || min_votes > nsrc) return MMD_EINVAL;
+  WbfArgs a{};
+  for (int i = 0; i < nsrc; ++i) { if (!srcs[i] || !cnts[i]) return MMD_EINVAL; a.src[i] = srcs[i]; a.cnt[i] = cnts[i]; }
+  a.nsrc = nsrc; a.thr = iou_threshold; a.inclusive = inclusive; a.merge01 = (merge01 && B >= 2) ? 1 : 0; a.in_cap = cap;
+  a.out = boxes; a.out_cnt = nbox; a.out_cap = maxg; a.aux = aux; a.min_votes = min_votes; a.overflow = overflow;
+  const long long nmax = (long long)nsrc * cap * (a.merge01 ? 2 : 1);
+  a.rows = 64;
+  while (a.rows < PP_CAP && a.rows < nmax) a.rows <<= 1;
+  const size_t lds = (size_t)a.rows * WBF_LDS_PER_ROW;
+  if (lds > 64 * 1024) {      // 1024 rows: 86 016 B, above the default dynamic-LDS limit (the CU has 160 KB)
+    static bool attr = false;
+    if (!attr) {
+      if (hipFuncSetAttribute((const void*)pp_wbf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_CAP * WBF_LDS_PER_ROW) != hipSuccess) return MMD_ELAUNCH;
+      attr = true;
+    }
+  }
+  hipLaunchKernelGGL(pp_wbf_kernel, dim3(B), dim3(a.rows), lds, stream, a);
   return mmd_check_launch();
 }
 

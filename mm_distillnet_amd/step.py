@@ -24,7 +24,7 @@ import torch
 from . import _lib
 from .arch import NetSpec, make_spec
 from .engine import Net, Feat, NONE, SWISH, pack_nets
-from .postproc import decode_nms, nms_workspace, valid_class_mask
+from .postproc import LABEL_MERGES, decode_nms, nms_workspace, valid_class_mask, wbf_merge
 from .store import Arena
 
 call = _lib.call
@@ -66,8 +66,20 @@ class StepConfig:
                                        # running statistics rides behind every optimizer launch (csrc/optim.hip mmd_ema_update; 0.9998 is
                                        # the EfficientDet recipe's)
     ema_warmup: bool = True            # d = min(ema_decay, (1 + n) / (10 + n)) at the n-th update (n from 0)
+    label_merge: str = "nms"           # extension key: how the teachers' boxes become the pseudo-labels.  "nms": upstream's class-agnostic
+                                       # NMS over their concatenation; "wbf": weighted box fusion (csrc/postproc.hip pp_wbf_kernel) at the
+                                       # same merge_iou / inclusive_nms - overlapping boxes of one label are averaged, weights = scores
+    label_merge_votes: int = 1         # wbf: a fused box needs members from at least this many distinct sources (1 .. number of sources)
 
     def __post_init__(self):
+        if self.label_merge not in LABEL_MERGES:
+            raise ValueError(f"label_merge {self.label_merge!r}: one of {' | '.join(LABEL_MERGES)}")
+        v = self.label_merge_votes
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v <= 4:
+            raise ValueError(f"label_merge_votes {v!r}: an integer between 1 and the number of sources (at most 4)")
+        if self.label_merge == "wbf" and not self.conf_threshold > 0:
+            # the fusion's weights are the scores: a row of score 0 would pull nothing and still count as a member and a vote
+            raise ValueError(f"label_merge wbf needs conf_threshold > 0 (got {self.conf_threshold!r}): the scores are the fusion's weights")
         d = self.ema_decay
         if isinstance(d, bool) or not isinstance(d, numbers.Real) or not (d == 0 or 0.0 < d < 1.0):
             raise ValueError(f"ema_decay {d!r}: 0 (off) or a decay with 0 < d < 1")
@@ -84,6 +96,9 @@ class DistillEngine:
             # upstream's ModelWithNMSKDListLoss hands AttentionLoss a per-teacher LIST per level: at_loss fails at the first step
             # (AttributeError: 'list' object has no attribute 'shape')
             raise Exception("kd_loss AttentionLoss does not run with the kdlist train methods (upstream fails on the teachers' list)")
+        n_src = sum(1 for m in TEACHER_ORDER if m in teacher_specs)
+        if cfg.label_merge == "wbf" and cfg.label_merge_votes > n_src:
+            raise ValueError(f"label_merge_votes {cfg.label_merge_votes} exceeds the {n_src} teachers whose boxes are fused")
         self.cfg = cfg
         self.device = device
         self.world_size = world_size
@@ -128,6 +143,7 @@ class DistillEngine:
         self.valid_mask = valid_class_mask(cfg.valid_prediction_ids)
         self.cap = int(cfg.cand_cap)     # 0: set to the anchor count at the first step
         self._eval: Optional[dict] = None  # the evaluation record between begin_eval and end_eval
+        self._merge_aux = None             # label_merge = wbf: the last merge's [B, G, 3] (mean score, members, sources) per fused box
         self.graph = None
         self._graphs: Dict[str, tuple] = {}       # step variant ("plain" / "aug") -> (static inputs, g_main, g_tail, g_opt, outputs)
         self.concurrent_teachers = True
@@ -277,17 +293,41 @@ class DistillEngine:
         return nms_workspace(self.ws, B, nmax)
 
     def _merge(self, rows_t, cnt_t, B: int, augment: bool):
-        """cross-teacher concat + NMS -> (boxes [B,G,5], nbox [B], G).  Up to 4 sources: the teachers in ModuleDict order, then the
-        "augmentation" pass of ModelWithNMSKDListLossAugmented."""
+        """cross-teacher concat + NMS (cfg label_merge = nms, upstream's) or weighted box fusion (wbf) -> (boxes [B,G,5], nbox [B], G).
+        Up to 4 sources: the teachers in ModuleDict order, then the "augmentation" pass of ModelWithNMSKDListLossAugmented.  Leaves the
+        fusion's per-box record in self._merge_aux (None after an NMS)."""
         nt, cap = len(rows_t), self.cap
         nmax = nt * cap * (2 if (augment and B >= 2) else 1)
         G = self.cfg.max_boxes if self.cfg.max_boxes > 0 else nmax
+        self._merge_aux = None
+        if self.cfg.label_merge == "wbf":
+            # (a fused list is never longer than the gathered one, so G holds it whenever it held the NMS's)
+            boxes, nbox, self._merge_aux = wbf_merge(self.ws, rows_t, cnt_t, B, cap, self.cfg.merge_iou, self.cfg.inclusive_nms, G,
+                                                     self.cfg.label_merge_votes, self.overflow, merge01=augment)
+            return boxes, nbox, G
         boxes = self.ws.alloc((B, G, 5)); nbox = self.ws.alloc((B,), torch.int32)
         vp = ctypes.c_void_p
         srcs = (vp * nt)(*[t.data_ptr() for t in rows_t]); cnts = (vp * nt)(*[t.data_ptr() for t in cnt_t])
         call("mmd_nms_merge_n", srcs, cnts, nt, float(self.cfg.merge_iou), 1 if self.cfg.inclusive_nms else 0, B, boxes, nbox, G,
              self.mask_ws, self.overflow, 1 if augment else 0, cap, self._nms_ws(B, nmax))
         return boxes, nbox, G
+
+    def merge_labels(self, rows_t: List[torch.Tensor], cnt_t: List[torch.Tensor], augment: bool = False):
+        """The step's cross-teacher merge alone, as cfg `label_merge` sets it: per source rows [B, cap, 6] (x1, y1, x2, y2, score, label)
+        and counts [B] int32 on the device (`labels_from_rows` makes them from host arrays) -> (boxes [B, G, 5], nbox [B], aux), aux
+        [B, G, 3] = (mean member score, members, distinct sources) per fused box with `wbf`, None with `nms`.  The results lie in the
+        step workspace, which this call starts afresh like a step does: read them before the next step, and a step's outputs before it."""
+        if not rows_t or len(rows_t) != len(cnt_t):
+            raise ValueError("merge_labels: one count array per source")
+        B, cap = int(rows_t[0].shape[0]), int(rows_t[0].shape[1])
+        if self.cap <= 0:
+            self.cap = cap
+        if any(tuple(r.shape) != (B, self.cap, 6) for r in rows_t):
+            raise ValueError(f"merge_labels: every source is [B, {self.cap}, 6] (the engine's candidate capacity)")
+        self.ws.reset()
+        self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
+        boxes, nbox, _ = self._merge(list(rows_t), list(cnt_t), B, bool(augment))
+        return boxes, nbox, self._merge_aux
 
     def _pseudo_labels(self, net: Net, cls, reg, B: int, A: int, S: int):
         return decode_nms(self.ws, net, cls, reg, B, A, S, self._caps(A), self.cfg.conf_threshold, self.valid_mask, self.label_map,
@@ -490,7 +530,7 @@ class DistillEngine:
         if train and not _lib.dev_switch("MMD_DEV_NO_BWD"):      # (MMD_DEV_NO_BWD=1: timing experiment - forward + losses only)
             call("mmd_memset_async", st.ps.grad, 0, st.ps.grad.numel() * 4)
             st.backward(dcls, dreg, dfe, stop_before=self.ar_split, dfeat_pyr=d_all)
-        self.out = {"reg": main[0:1], "cls": main[1:2], "kd": kd, "boxes": boxes, "nbox": nbox,
+        self.out = {"reg": main[0:1], "cls": main[1:2], "kd": kd, "boxes": boxes, "nbox": nbox, "label_aux": self._merge_aux,
                     "cls_s": cls_s, "reg_s": reg_s, "feats_s": feats_s, "rows_t": rows_t, "cnt_t": cnt_t}
         return self.out
 
@@ -621,12 +661,14 @@ class DistillEngine:
     def _variant(batch) -> str:
         return "aug" if (batch is not None and batch.get("aug_rgb") is not None) else "plain"
 
-    def capture(self, batch: Dict[str, torch.Tensor]):
+    def capture(self, batch: Dict[str, torch.Tensor], teacher_labels: Optional[List[tuple]] = None):
         """Warm up eagerly (sizes the arenas), then capture forward+loss+backward and the optimizer as
         hipGraphs (the backward in two segments when world_size > 1); the gradient all-reduce is launched eagerly between
         them (RCCL is not captured) and overlaps with the second backward segment.
         One set of graphs per step variant: "plain", and "aug" when the batch carries `aug_rgb` (the extra RGB-teacher pass of
-        ModelWithNMSKDListLossAugmented); replay() picks by the batch's keys and captures a missing variant on first use."""
+        ModelWithNMSKDListLossAugmented); replay() picks by the batch's keys and captures a missing variant on first use.
+        teacher_labels: as step_body - the captured step then reads its pseudo-labels from these very tensors (cached labels of the frozen
+        teachers: write new ones into them between replays)."""
         B = batch["audio"].shape[0]
         arenas = [self.ws, self.student.arena, self.student.zarena] + [a for n in self.teachers.values() for a in (n.arena, n.zarena)]
         for arena in arenas:
@@ -645,7 +687,7 @@ class DistillEngine:
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):
-                self.step_body(self.static, self.static["drop_scale"])
+                self.step_body(self.static, self.static["drop_scale"], teacher_labels=teacher_labels)
                 self.backward_tail()
                 self.optimizer_body()
         torch.cuda.current_stream().wait_stream(s)
@@ -657,7 +699,7 @@ class DistillEngine:
         self.g_main = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_main, capture_error_mode="thread_local"):
             self.draw_drop_scale(self.static["drop_scale"])      # (no-op while a mask is injected: set_drop_scale)
-            self.step_body(self.static, self.static["drop_scale"])
+            self.step_body(self.static, self.static["drop_scale"], teacher_labels=teacher_labels)
         out = self.out
         self.g_tail = None
         if self.ar_split is not None:

@@ -55,6 +55,17 @@ def ema_settings(cfg) -> Dict:
     return {"ema_decay": cfg.getfloat("ema_decay", 0.0), "ema_warmup": bool(cfg.getboolean("ema_warmup", True))}
 
 
+def label_merge_settings(cfg) -> Dict:
+    """cfg -> StepConfig keyword arguments of the cross-teacher merge (extension keys, absent from the reference's cfg files -> upstream's
+    NMS): label_merge (nms | wbf) and label_merge_votes (distinct teachers a fused box needs, default 1).  Host work only: an unknown value
+    raises here, before any device work (StepConfig repeats the checks for direct users)."""
+    from .postproc import LABEL_MERGES
+    name = cfg.get("label_merge", "nms")
+    if name not in LABEL_MERGES:
+        raise ValueError(f"label_merge {name!r}: one of {' | '.join(LABEL_MERGES)}")
+    return {"label_merge": name, "label_merge_votes": cfg.getint("label_merge_votes", 1)}
+
+
 def ema_validate_setting(cfg) -> bool:
     """cfg ema_validate (default False): validate(), and with it best-checkpoint selection and early stopping, on the averaged weights"""
     on = bool(cfg.getboolean("ema_validate", False))

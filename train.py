@@ -13,6 +13,8 @@ so upstream can resume from these files and this script from upstream's.  Epoch 
 epoch's last training loss, validate() every val_interval epochs, best / early stopping on the validation loss.
 Extension keys `ema_decay` / `ema_warmup` / `ema_validate` (absent -> off): an exponential moving average of the student's weights kept on
 the device, saved as two more checkpoint keys (`state_dict_ema`, `ema_updates`) and as only_parameters_student_best_ema.<rank>.
+Extension keys `label_merge` (nms | wbf, absent -> nms: upstream's NMS) / `label_merge_votes` (absent -> 1): the teachers' boxes become the
+pseudo-labels by weighted box fusion on the device instead of the NMS.
 """
 import argparse
 import configparser
@@ -101,7 +103,7 @@ def step_config(cfg) -> StepConfig:
                       augment=bool(cfg.getboolean("audio_augmentation_merge", False)) and method == "traditional_nms_augmented",
                       # extension key (absent from the reference's cfg files -> fp32): "bf16" = 1x1 convs on the bf16 MFMA
                       precision=cfg.get("precision", "fp32"), seed=cfg.getint("seed", 24),
-                      **TR.optimizer_settings(cfg), **TR.ema_settings(cfg))
+                      **TR.optimizer_settings(cfg), **TR.ema_settings(cfg), **TR.label_merge_settings(cfg))
 
 
 def augment_from_config(cfg, raw: bool, rank: int = 0):
