@@ -9,7 +9,8 @@ reduces over N and writes K columns: Kg = N is the REDUCTION LENGTH, Ng = K the 
 the case table, the names of the cases) uses Kg / Ng; a case carries both spellings.
 
 OUT OF SCOPE here: the w16 storage flags of pw_bwd_data_bn2_impl (no public entry point), the grouped-nets mode, MMD_SK_BQ_LDS / MMD_SK_PF2 and
-the other dispatch variables (test_bd_ref_cpu.py asserts that none is set), the fused expand backward (mmd_mbconv_expand_bwd_fused).
+the other dispatch variables (test_bd_ref_cpu.py asserts that none is set), the fused expand backward (mmd_mbconv_expand_bwd_fused: mb_ref.py,
+which takes xs_ref below).
 
 Conventions are those of elt_ref.py / pw_ref.py / wg_ref.py.  bd_fwd computes in the dtype (and on the device) of its tensor arguments: float64 is
 the oracle, float32 the model that calibrates K.  It returns a dict of (value, A), A_i the magnitude of what element i was built from:

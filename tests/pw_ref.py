@@ -9,7 +9,7 @@ BatchNorm-backward operand forms included - lives in wg_ref.py, which takes its 
 mmd_pwconv_bwd_data* entry points with their BatchNorm-backward operand forms, the slab kernel's <PRO 1> instantiations included - lives in
 bd_ref.py, whose plain launches are pw_fwd below with the sizes swapped.
 OUT OF SCOPE still (pw_fwd is the forward of every one of them): mmd_pwconv_fwd_pyr*, the grouped-nets mode (mmd_set_group), the stem
-im2col GEMM (mmd_pw_stem_gemm) and the stem weight gradient, the forward slab family (form 4 of mmd_pwconv_fwd_form, pw_slab.hip: route
+im2col GEMM (mmd_pw_stem_gemm) and the stem weight gradient (both in mb_ref.py, which calls pw_fwd below), the forward slab family (form 4 of mmd_pwconv_fwd_form, pw_slab.hip: route
 names it where the auto form could take a launch, and no case may land there) and the MMD_STREAM dev kernel.
 
 Conventions are those of elt_ref.py / dw_ref.py.  pw_fwd computes in the dtype (and on the device) of its tensor arguments: float64 is the

@@ -6,7 +6,7 @@ copies of the two host planners (plan: mmd_wgrad_plan; per_layer_plan: pw_wgrad_
 tables (WG_TABLES, PER_LAYER_CASES) that test_wg_ref_cpu.py and test_gpu_wg_float64.py share.
 
 OUT OF SCOPE here: the square tile forms (wgrad_grouped_kernel<64 / 128>, wgrad_fold_kernel<T>: MMD_WG_TILE), the MMD_WG_SPLIT_W3 / MMD_WG_XCD8 /
-MMD_WG_BLOCKS knobs, the w16 storage flags, the stem weight gradient.
+MMD_WG_BLOCKS knobs, the w16 storage flags, the stem weight gradient (mb_ref.py has it).
 
 Conventions are those of elt_ref.py / pw_ref.py.  wg_fwd computes in the dtype (and on the device) of its tensor arguments: float64 is the
 oracle, float32 the model that calibrates K.  It returns {"dw"} (with `bn` also {"dgamma", "dbeta"}) of (value, A):
