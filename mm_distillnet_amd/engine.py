@@ -18,7 +18,7 @@ import ctypes
 import os
 import threading
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -29,6 +29,7 @@ from .store import ParamStore, Arena
 NONE, SWISH, SIGMOID = 0, 1, 2
 
 _PACK = threading.local()      # .on: this thread is inside a pack forward (Net.forward(pack=...))
+_SKIP = threading.local()      # .on: this thread is inside Net._wgrad_stream() under MMD_DEV_SKIP_WG: call() launches nothing
 # entry points a pack forward may issue WITHOUT the group descriptor: they read no per-net parameters (or, the stems, are issued once per net)
 PACK_PLAIN_OK = frozenset({"mmd_stem_conv_fwd", "mmd_maxpool_same_fwd", "mmd_memset_async"})
 
@@ -36,6 +37,8 @@ PACK_PLAIN_OK = frozenset({"mmd_stem_conv_fwd", "mmd_maxpool_same_fwd", "mmd_mem
 def call(name: str, *args):
     """_lib.call, except inside a pack forward: there every launch that reads parameters must go through Net._c (group descriptor set,
     honoured by the library or refused) - a plain launch would evaluate every net's images with the first net's weights, silently."""
+    if getattr(_SKIP, "on", False):
+        return 0
     if getattr(_PACK, "on", False) and name not in PACK_PLAIN_OK:
         raise RuntimeError(f"{name} issued inside a pack forward without the group descriptor (engine.Net._c): it would read net 0's parameters for every image")
     return _lib.call(name, *args)
@@ -99,19 +102,54 @@ class GradSlot:
         self.stream: Optional[int] = None   # linear mode: the stream every contribution must be issued on (see Net._contrib)
 
 
+class Aff(NamedTuple):
+    """A train-mode BatchNorm's finalized coefficients, in the order every BatchNorm-backward entry point takes them (`*aff`)."""
+    scale: Optional[torch.Tensor]; shift: Optional[torch.Tensor]; mean: Optional[torch.Tensor]; invstd: Optional[torch.Tensor]
+
+
+class BnOut(NamedTuple):
+    """Net._bnout[y]: the tensor y = BN(z) [* mul_b[image]] (+ skip) is the output of this train-mode BatchNorm over C channels."""
+    z: torch.Tensor; mean: torch.Tensor; invstd: torch.Tensor; C: int
+    mul_b: Optional[torch.Tensor]; rpi: int                  # (rpi: rows per image, for mul_b)
+
+
+class BnSums(NamedTuple):
+    """Net._contrib's hand-off to the kernel that writes a gradient contribution: take the backward sums of this BatchNorm over it."""
+    z: torch.Tensor; mean: torch.Tensor; invstd: torch.Tensor; sums: torch.Tensor
+    mul_b: Optional[torch.Tensor]; rpi: int
+    linear: int                 # 1: a max-pooled tensor - the kernel adds the sums of its OWN share (see Net._contrib)
+
+    @property
+    def quad(self):             # mmd_bifpn_node_* and mmd_maxpool_same_bwd_acc2; mmd_pyr_add_bnsums takes one pointer array per field
+        return self.z, self.mean, self.invstd, self.sums
+
+    @property
+    def gemm(self):             # GEMM order: mmd_pwconv_bwd_data_bn2* (the sums' slot workspace follows) and mmd_mbconv_expand_bwd_fused
+        return self.z, self.mean, self.invstd, self.mul_b, self.rpi, self.sums
+
+
+NO_SUMS_QUAD = (None, None, None, None)             # what the kernels take in place of BnSums.quad / .gemm: no sums
+NO_SUMS_GEMM = (None, None, None, None, 0, None)
+
+
+class WgRec(NamedTuple):
+    """Net._wg_pending: one recorded 1x1-conv weight gradient dw[N,K] (+)= dy^T pro(x) (the arguments of mmd_pwconv_bwd_weight)."""
+    dy: torch.Tensor; x: torch.Tensor; dw: torch.Tensor; M: int; K: int; N: int
+    in_scale: Optional[torch.Tensor]; in_shift: Optional[torch.Tensor]; in_act: int; gate: Optional[torch.Tensor]; rpi: int
+
+
+class SeWgRec(NamedTuple):
+    """Net._se_wg: the squeeze-excite FC weight gradients of one block, a row of mmd_se_fc_wgrad_batched's table in field order."""
+    dpe: torch.Tensor; dpr: torch.Tensor; hpre: torch.Tensor; pooled: torch.Tensor
+    g_reduce_w: torch.Tensor; g_reduce_b: torch.Tensor; g_expand_w: torch.Tensor; g_expand_b: torch.Tensor; C: int; S: int
+
+
 @dataclass
 class LazyDz:
     """A BatchNorm backward that is not materialised: the input- and weight-gradient GEMMs of the conv in front of the
     BatchNorm evaluate dz = BnBwd(g, z) in their operand prologues (mmd_pwconv_bwd_data_bn / _weight_bn)."""
-    g: torch.Tensor
-    z: torch.Tensor
-    aff: tuple                  # (scale, shift, mean, invstd, ...)
-    sums: torch.Tensor
-    act: int
-    mul_b: Optional[torch.Tensor]
-    rpi: int
-    bn_name: str
-    count: int
+    g: torch.Tensor; z: torch.Tensor; aff: Aff; sums: torch.Tensor
+    act: int; mul_b: Optional[torch.Tensor]; rpi: int; bn_name: str; count: int
 
 
 # MBConv expand convs with a thin input at high resolution (round 4): BatchNorm-0 backward, input gradient and weight gradient in one pass over
@@ -195,16 +233,16 @@ class Net:
         self._side = None
         self._wg = None           # weight-gradient stream: nothing downstream of a wgrad until the optimizer
         self.mark_block, self.mark_event = -1, None
-        self._wg_pending: list = []          # deferred 1x1-conv weight gradients of the current backward segment
+        self._wg_pending: List[WgRec] = []   # deferred 1x1-conv weight gradients of the current backward segment
         self._wg_count = 0                   # layers recorded so far in this backward
         self._wg_plans: Dict[tuple, dict] = {}  # (segment index, operand signature) -> planned table (built once: arena addresses repeat every step)
         self._wg_segment = 0
         self._linear: set = set()              # train forward: tensors that are a BiFPN node's POOLED operand (their gradient is scattered: linear sums)
         self._uses: Dict[int, int] = {}        # train forward: tensor -> number of gradient contributions its slot will receive
-        self._bnout: Dict[int, tuple] = {}     # train forward: tensor y = BN(z) [* mul_b[image]] (+ skip) -> (z, mean, invstd, C, mul_b, rows_per_image)
+        self._bnout: Dict[int, BnOut] = {}     # train forward: tensor y = BN(z) [* mul_b[image]] (+ skip) -> that BatchNorm
         self._counting = False
         self._theta_desc: Dict[tuple, torch.Tensor] = {}
-        self._se_wg: list = []                 # squeeze-excite FC weight gradients of the current backward segment (one batched launch)
+        self._se_wg: List[SeWgRec] = []        # squeeze-excite FC weight gradients of the current backward segment (one batched launch)
         self._se_wg_tabs: Dict[tuple, torch.Tensor] = {}
         # test aid ("teacher forcing"): probe = dict that receives a copy of every materialised unit output of a forward (stem, MBConv
         # blocks, BiFPN down-channel convs and nodes); force_out = dict name -> rows [M, C] written over that output AFTER the probe, so the
@@ -286,14 +324,14 @@ class Net:
         return self.stats_flat[2 * o:2 * o + 2 * c]
 
     def _bn_aff(self, name: str, train: bool, stats, count: int):
-        """-> (scale, shift, mean, invstd, live).  eval: folded running stats.  train: views that the batched finalize
+        """-> (Aff, live).  eval: folded running stats.  train: views that the batched finalize
         at the end of the forward fills (the backward reads them) + the `live` tuple forward consumers use."""
         b = self.ps.bn(name)
         if not train:
-            return b["fscale"], b["fshift"], None, None, None
+            return Aff(b["fscale"], b["fshift"], None, None), None
         o, c = b["off"], b["C"]
         self.bn_count_host[o:o + c] = float(count)
-        return (self.t_scale[o:o + c], self.t_shift[o:o + c], self.t_mean[o:o + c], self.t_invstd[o:o + c],
+        return (Aff(self.t_scale[o:o + c], self.t_shift[o:o + c], self.t_mean[o:o + c], self.t_invstd[o:o + c]),
                 (stats, b["gamma"], b["beta"], int(count)))
 
     @staticmethod
@@ -424,7 +462,7 @@ class Net:
         # direct 3x3/s2 stem conv (NCHW image -> NHWC rows); the im2col matrix is only built in the backward, for the
         # weight gradient, on the wgrad stream
         st = self._bn_stats(f"{P}._bn0", train)
-        sc, sh, mu, istd, live = self._bn_aff(f"{P}._bn0", train, st, B * OH * OH)
+        (sc, sh, mu, istd), live = self._bn_aff(f"{P}._bn0", train, st, B * OH * OH)
         z = self._alloc(B * OH * OH, spec.stem_out)
         wstem = ps.w(f"{P}._conv_stem.conv.weight")
         if train:
@@ -461,12 +499,12 @@ class Net:
                 f0 = None           # frozen net, thin input: expand + depthwise in one kernel below, the expanded tensor stays in LDS
             elif blk.expand != 1:
                 st0 = self._bn_stats(f"{q}._bn0", train)
-                a0 = self._bn_aff(f"{q}._bn0", train, st0, inp.M)
+                a0, live0 = self._bn_aff(f"{q}._bn0", train, st0, inp.M)
                 if train:
                     z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, stats=st0)
-                    f0 = Feat(z0, B, inp.H, inp.W, blk.cmid, a0[0], a0[1], SWISH, a0[4])
+                    f0 = Feat(z0, B, inp.H, inp.W, blk.cmid, a0.scale, a0.shift, SWISH, live0)
                 else:           # frozen net: activate in the producer's epilogue (see the stem)
-                    z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, out_aff=(a0[0], a0[1]), out_act=SWISH)
+                    z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, out_aff=(a0.scale, a0.shift), out_act=SWISH)
                     f0 = Feat(z0, B, inp.H, inp.W, blk.cmid)
                 rec["f0"], rec["bn0"] = f0, a0
             else:
@@ -483,22 +521,21 @@ class Net:
             if train:
                 st1 = self._bn_stats(f"{q}._bn1", True)
                 z1, _, _ = self._dw(f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride, stats=st1)
-                a1 = self._bn_aff(f"{q}._bn1", True, st1, M1)
-                f1 = Feat(z1, B, H1, W1, blk.cmid, a1[0], a1[1], SWISH, a1[4])
+                a1, live1 = self._bn_aff(f"{q}._bn1", True, st1, M1)
+                f1 = Feat(z1, B, H1, W1, blk.cmid, a1.scale, a1.shift, SWISH, live1)
                 call("mmd_chan_pool", z1, *self._xf(f1)[:2], *self._xf(f1)[3:], SWISH, None, pooled, 1.0 / (H1 * W1), B,
                      H1 * W1, blk.cmid)
                 call("mmd_se_fc_fwd", pooled, *se_w, hpre, gate, B, blk.cmid, blk.se)
                 st2 = self._bn_stats(f"{q}._bn2", True)
                 z2 = self._pw(f1, f"{q}._project_conv.conv.weight", blk.cout, stats=st2, gate=gate)
-                a2 = self._bn_aff(f"{q}._bn2", True, st2, M1)
+                a2, live2 = self._bn_aff(f"{q}._bn2", True, st2, M1)
                 y = self._alloc(M1, blk.cout)
                 rs = None
                 if blk.skip and blk.drop_rate and drop_scale is not None:
                     rs = drop_scale[skip_i]
-                call("mmd_affine_act", z2, None, None, a2[4][0], a2[4][1], a2[4][2], a2[4][3], NONE, rs, H1 * W1, res, y, M1,
-                     blk.cout)
+                call("mmd_affine_act", z2, None, None, *live2, NONE, rs, H1 * W1, res, y, M1, blk.cout)
                 rec.update(f1=f1, bn1=a1, pooled=pooled, hpre=hpre, gate=gate, z2=z2, bn2=a2, rs=rs)
-                self._bnout[y.data_ptr()] = (z2, a2[2], a2[3], blk.cout, rs, H1 * W1)
+                self._bnout[y.data_ptr()] = BnOut(z2, a2.mean, a2.invstd, blk.cout, rs, H1 * W1)
             else:
                 # frozen net: BN1+swish and the SE average pool ride in the depthwise epilogue (no separate pool pass)
                 b1 = ps.bn(f"{q}._bn1")
@@ -566,12 +603,12 @@ class Net:
         if train:
             st = self._bn_stats(bn_name, True)
             z = self._pw(zdf, f"{name}.pointwise_conv.conv.weight", W, bias=bias, stats=st)
-            a = self._bn_aff(bn_name, True, st, x.M)
+            a, live = self._bn_aff(bn_name, True, st, x.M)
             if y is None:
                 y = self._alloc(x.M, W)
-            call("mmd_affine_act", z, None, None, a[4][0], a[4][1], a[4][2], a[4][3], NONE, None, 0, None, y, x.M, W)
+            call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, x.M, W)
             rec.update(zd=zdf, z=z, bn=a)
-            self._bnout[y.data_ptr()] = (z, a[2], a[3], W, None, 0)
+            self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
         else:
             b = ps.bn(bn_name)
             y = self._pw(zdf, f"{name}.pointwise_conv.conv.weight", W, bias=bias, out_aff=(b["fscale"], b["fshift"]), y=y)
@@ -586,24 +623,24 @@ class Net:
             # lazy output: the raw conv output + its BatchNorm as a pending transform the consuming node kernels apply (no affine launch)
             st = self._bn_stats(f"{name}.1", True)
             z = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, stats=st)
-            a = self._bn_aff(f"{name}.1", True, st, x.M)
+            a, live = self._bn_aff(f"{name}.1", True, st, x.M)
             rec.update(z=z, bn=a)
             tape[name] = rec
             self._use(x)
-            self._bnout[z.data_ptr()] = (z, a[2], a[3], W, None, 0)
-            out = Feat(z, x.B, x.H, x.W, W, a[0], a[1], NONE, a[4])
+            self._bnout[z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
+            out = Feat(z, x.B, x.H, x.W, W, a.scale, a.shift, NONE, live)
             rec["out"] = out
             return out
         if train:
             st = self._bn_stats(f"{name}.1", True)
             z = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, stats=st)
-            a = self._bn_aff(f"{name}.1", True, st, x.M)
+            a, live = self._bn_aff(f"{name}.1", True, st, x.M)
             y = self._alloc(x.M, W)
-            call("mmd_affine_act", z, None, None, a[4][0], a[4][1], a[4][2], a[4][3], NONE, None, 0, None, y, x.M, W)
+            call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, x.M, W)
             rec.update(z=z, bn=a)
             tape[name] = rec
             self._use(x)
-            self._bnout[y.data_ptr()] = (z, a[2], a[3], W, None, 0)
+            self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
         else:
             b = ps.bn(f"{name}.1")
             y = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, out_aff=(b["fscale"], b["fshift"]))
@@ -659,7 +696,7 @@ class Net:
                 call("mmd_bifpn_node_fwd_fused_train_lz", *args, pick(0), pick(1), pick(2), cnt)
             else:
                 call("mmd_bifpn_node_fwd_fused_train", *args)
-            a = self._bn_aff(bn_name, True, st, in0.M)
+            a, live = self._bn_aff(bn_name, True, st, in0.M)
             for operand in ops:
                 if operand is not None:
                     self._use(operand)
@@ -668,14 +705,14 @@ class Net:
             zdf = Feat(zd, in0.B, in0.H, in0.W, W)
             if self._lazy and y is None:
                 # lazy output (every cell but the last, whose outputs the heads and the MTA loss read): no affine launch
-                out = Feat(z, in0.B, in0.H, in0.W, W, a[0], a[1], NONE, a[4])
-                self._bnout[z.data_ptr()] = (z, a[2], a[3], W, None, 0)
+                out = Feat(z, in0.B, in0.H, in0.W, W, a.scale, a.shift, NONE, live)
+                self._bnout[z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
             else:
                 if y is None:
                     y = self._alloc(in0.M, W)
-                call("mmd_affine_act", z, None, None, a[4][0], a[4][1], a[4][2], a[4][3], NONE, None, 0, None, y, in0.M, W)
+                call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, in0.M, W)
                 out = Feat(y, in0.B, in0.H, in0.W, W)
-                self._bnout[y.data_ptr()] = (z, a[2], a[3], W, None, 0)
+                self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
             tape.setdefault(cell + ".nodes", []).append({"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "conv": conv,
                                                          "zd": zdf, "z": z, "bn": a, "out": out})
             return out
@@ -858,21 +895,21 @@ class Net:
     # ------------------------------------------------------------------ backward (student)
     def _slot(self, f: Feat) -> GradSlot:
         k = f.z.data_ptr()
-        s = self._bw["slots"].get(k)
-        if s is None:
-            s = self._bw["slots"][k] = GradSlot(self._uses.get(k, 0))
-        return s
+        if k not in self._slots:
+            self._slots[k] = GradSlot(self._uses.get(k, 0))
+        return self._slots[k]
 
-    def _contrib(self, f: Feat, can_sum: bool):
-        """One gradient contribution to `f` is about to be written.  -> (slot, xs); xs = (z, mean, invstd, sums, mul_b, rows_per_image)
-        when this is the LAST contribution, f is the output of a BatchNorm and the writing kernel can take that BatchNorm's backward sums
-        over the completed gradient (`can_sum`); the caller passes xs to the kernel, which marks the slot's sums valid."""
+    def _contrib(self, f: Feat, can_sum: bool) -> Tuple[GradSlot, Optional[BnSums]]:
+        """One gradient contribution to `f` is about to be written.  -> (slot, xs); xs = a BnSums when f is the output of a BatchNorm and
+        the writing kernel can take that BatchNorm's backward sums (`can_sum`): over the completed gradient when this is the LAST
+        contribution (xs.linear = 0), or over its own share when f is max-pooled somewhere (xs.linear = 1, below).  The caller passes
+        xs to the kernel in the layout it takes (BnSums.quad / .gemm); the slot's sums are valid once the last contribution has run."""
         s = self._slot(f)
         s.remaining -= 1
-        info = self._bnout.get(f.z.data_ptr())
+        info: Optional[BnOut] = self._bnout.get(f.z.data_ptr())
         if info is not None and self.ps.flat.is_cuda and f.z.data_ptr() in self._linear:
             # linear mode (the tensor is max-pooled by some node, whose backward scatters into its gradient): every contribution adds the
-            # sums of its OWN share (7th element = 1); they are complete when the last one has, provided none was unable to
+            # sums of its OWN share (linear = 1); they are complete when the last one has, provided none was unable to
             # Exclusivity (ADVICE r5): the node backward's LDS-tile scatter reads the interior of this gradient at block start and stores it
             # plainly at block end, so a contribution running BESIDE it on another stream would be lost without a trace (global atomics used
             # to make that safe).  Every contribution to a scattered gradient therefore has to be issued on ONE stream.
@@ -885,17 +922,14 @@ class Net:
             if not can_sum:
                 s.linear_ok = False
                 return s, None
-            z, mu, istd, C, mul_b, rpi = info
-            if s.sums is None:
-                s.sums = self._zalloc((2 * C,), torch.float64)
-            s.have_sums = s.remaining == 0 and s.linear_ok
-            return s, (z, mu, istd, s.sums, mul_b, rpi, 1)
-        if not (can_sum and s.remaining == 0 and info is not None and self.ps.flat.is_cuda):
+            linear, s.have_sums = 1, s.remaining == 0 and s.linear_ok
+        elif can_sum and s.remaining == 0 and info is not None and self.ps.flat.is_cuda:
+            linear, s.have_sums, s.sums = 0, True, None
+        else:
             return s, None
-        z, mu, istd, C, mul_b, rpi = info
-        s.sums = self._zalloc((2 * C,), torch.float64)
-        s.have_sums = True
-        return s, (z, mu, istd, s.sums, mul_b, rpi, 0)
+        if s.sums is None:
+            s.sums = self._zalloc((2 * info.C,), torch.float64)
+        return s, BnSums(info.z, info.mean, info.invstd, s.sums, info.mul_b, info.rpi, linear)
 
     def _acc(self, f: Feat, src: torch.Tensor):
         """gradient of f (+)= src ; the first writer just adopts the tensor (a contribution without BatchNorm sums)."""
@@ -921,15 +955,13 @@ class Net:
             self._wg = torch.cuda.Stream()
         self._wg.wait_event(torch.cuda.current_stream().record_event())
         with torch.cuda.stream(self._wg):
-            if _lib.dev_switch("MMD_DEV_SKIP_WG"):      # timing experiment only (gradients are WRONG): what do the weight-gradient
-                global call                            # kernels cost the step through contention with the main chain?
-                saved, call = call, (lambda *a, **k: 0)
-                try:
-                    yield
-                finally:
-                    call = saved
-                return
-            yield
+            # MMD_DEV_SKIP_WG, timing experiment only (gradients are WRONG): what do the weight-gradient kernels cost the step through
+            # contention with the main chain?  Every call() issued inside this context is skipped
+            saved, _SKIP.on = getattr(_SKIP, "on", False), bool(_lib.dev_switch("MMD_DEV_SKIP_WG"))
+            try:
+                yield
+            finally:
+                _SKIP.on = saved
 
     def _pw_wgrad(self, dy: torch.Tensor, xz: torch.Tensor, dw: torch.Tensor, M: int, K: int, N: int, in_scale=None, in_shift=None,
                   in_act: int = NONE, gate=None, rpi: int = 1):
@@ -938,7 +970,7 @@ class Net:
             with self._wgrad_stream():
                 call("mmd_pwconv_bwd_weight" + self._sfx, dy, xz, dw, M, K, N, in_scale, in_shift, in_act, gate, rpi)
             return
-        self._wg_pending.append((dy, xz, dw, M, K, N, in_scale, in_shift, in_act, gate, rpi))
+        self._wg_pending.append(WgRec(dy, xz, dw, M, K, N, in_scale, in_shift, in_act, gate, rpi))
         self._wg_count += 1
         if self._wg_count % WG_CHUNK == 0:
             # (counted over the whole backward, not per segment: the split backward of the data-parallel step then flushes at the same layers as
@@ -967,7 +999,7 @@ class Net:
         if not pend:
             return
         ptr = lambda t: 0 if t is None else t.data_ptr()
-        sig = tuple((ptr(d), ptr(x), ptr(w), M, K, N, ptr(a), ptr(b), act, ptr(gt), rpi) for d, x, w, M, K, N, a, b, act, gt, rpi in pend)
+        sig = tuple((ptr(r.dy), ptr(r.x), ptr(r.dw), r.M, r.K, r.N, ptr(r.in_scale), ptr(r.in_shift), r.in_act, ptr(r.gate), r.rpi) for r in pend)
         # one plan per (segment, operand signature): a second step variant captured later ("aug") may lay its operands out
         # differently, and the device tables of the variants captured before must stay alive - their graphs keep reading them
         plan = self._wg_plans.get((seg, sig))
@@ -976,10 +1008,10 @@ class Net:
                 raise RuntimeError("weight-gradient operands moved after graph capture")
             n = len(pend)
             arr = (WgLayer * n)()
-            for i, (d, x, w, M, K, N, a, b, act, gt, rpi) in enumerate(pend):
-                arr[i].dy, arr[i].x, arr[i].dw = ptr(d), ptr(x), ptr(w)
-                arr[i].in_scale, arr[i].in_shift, arr[i].gate = ptr(a) or None, ptr(b) or None, ptr(gt) or None
-                arr[i].M, arr[i].K, arr[i].N, arr[i].in_act, arr[i].rows_per_image = M, K, N, act, max(int(rpi), 1)
+            for a, r in zip(arr, pend):
+                a.dy, a.x, a.dw = ptr(r.dy), ptr(r.x), ptr(r.dw)
+                a.in_scale, a.in_shift, a.gate = ptr(r.in_scale) or None, ptr(r.in_shift) or None, ptr(r.gate) or None
+                a.M, a.K, a.N, a.in_act, a.rows_per_image = r.M, r.K, r.N, r.in_act, max(int(r.rpi), 1)
             ni, nt, wsf = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
             rc = _lib.LIB.load().mmd_wgrad_plan(ctypes.cast(arr, ctypes.c_void_p), n, WG_ROWS, ctypes.cast(ctypes.pointer(ni), ctypes.c_void_p),
                                                 ctypes.cast(ctypes.pointer(nt), ctypes.c_void_p), ctypes.cast(ctypes.pointer(wsf), ctypes.c_void_p))
@@ -987,17 +1019,17 @@ class Net:
                 raise RuntimeError(f"mmd_wgrad_plan failed with status {rc}")
             table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
             plan = {"sig": sig, "table": table, "n": n, "items": ni.value, "tiles": nt.value, "ws": wsf.value,
-                    "flops": float(sum(2.0 * M * K * N for _, _, _, M, K, N, *_ in pend)),
-                    "bytes": float(sum(4.0 * (M * K + M * N + N * K) for _, _, _, M, K, N, *_ in pend)),
+                    "flops": float(sum(2.0 * r.M * r.K * r.N for r in pend)),
+                    "bytes": float(sum(4.0 * (r.M * r.K + r.M * r.N + r.N * r.K) for r in pend)),
                     # every layer's M a multiple of 32 (any net at B >= 2): the launch runs without row clamps / masks (mmd_wgrad_grouped_form)
-                    "rows32": int(all(M % 32 == 0 for _, _, _, M, *_ in pend))}
+                    "rows32": int(all(r.M % 32 == 0 for r in pend))}
             self._wg_plans[(seg, sig)] = plan
         ws = self._alloc(plan["ws"])
         with self._wgrad_stream():
             call("mmd_wgrad_grouped_form", plan["table"], plan["n"], plan["items"], plan["tiles"], ws, WG_BLOCKS,
                  plan["flops"], plan["bytes"], 1 if self._sfx else 0, plan["rows32"])
 
-    def _bn_bwd(self, g_in: torch.Tensor, z: torch.Tensor, aff, bn_name: str, act: int, M: int, C: int, rpi: int = 0,
+    def _bn_bwd(self, g_in: torch.Tensor, z: torch.Tensor, aff: Aff, bn_name: str, act: int, M: int, C: int, rpi: int = 0,
                 mul_bc=None, mul_b=None, add_bc=None, sums=None, lazy: bool = False):
         """BN(+act) backward: returns dz (gradient w.r.t. the conv's raw output); dgamma/dbeta accumulated.
         `sums` given = the per-channel sums were produced elsewhere (fused into another pass): pass 2 only.
@@ -1005,82 +1037,27 @@ class Net:
         b = self.ps.bn(bn_name)
         if sums is None:
             sums = self._zalloc((2 * C,), torch.float64)
-            call("mmd_bn_bwd_reduce", g_in, z, aff[0], aff[1], aff[2], aff[3], act, mul_bc, mul_b, add_bc, rpi, None, sums, M, C,
-                 *self._stats_ws(sums, M, C))
+            call("mmd_bn_bwd_reduce", g_in, z, *aff, act, mul_bc, mul_b, add_bc, rpi, None, sums, M, C, *self._stats_ws(sums, M, C))
         if lazy and mul_bc is None and add_bc is None:
             return LazyDz(g_in, z, aff, sums, act, mul_b, rpi, bn_name, M)
         dz = self._alloc(M, C)
-        call("mmd_bn_bwd_apply", g_in, z, aff[2], aff[3], b["gamma"], sums, M, dz, b["dgamma"], b["dbeta"], M, C,
-             aff[0], aff[1], act, mul_bc, mul_b, add_bc, rpi)
+        call("mmd_bn_bwd_apply", g_in, z, aff.mean, aff.invstd, b["gamma"], sums, M, dz, b["dgamma"], b["dbeta"], M, C,
+             aff.scale, aff.shift, act, mul_bc, mul_b, add_bc, rpi)
         return dz
 
-    def _pw_bwd(self, dz: torch.Tensor, x: Feat, wkey: str, N: int, bias_key: Optional[str], want_dx: bool,
+    def _pw_bwd(self, dz, x: Feat, wkey: str, N: int, bias_key: Optional[str], want_dx: bool,
                 gate=None, plain_in=False, into: Optional[Feat] = None, pool5: Optional[tuple] = None) -> Optional[torch.Tensor]:
         """Gradients of a 1x1 conv.  into = the Feat whose gradient slot receives dx (normally x itself): dx is then written into / on top
         of that slot by the GEMM's epilogue (no scale_acc launch), together with the backward sums of the BatchNorm that produced the
         Feat when this is the slot's last contribution; returns None in that case."""
-        ps = self.ps
-        M, K = x.M, x.C
+        ps, M, K = self.ps, x.M, x.C
+        # the weight gradient's operand prologue: (in_scale, in_shift, in_act, gate, rows_per_image)
+        xargs = (None, None, NONE, gate, x.H * x.W) if plain_in else (x.scale, x.shift, x.act, gate, x.H * x.W)
         if isinstance(dz, LazyDz):
-            # BatchNorm backward in the operand prologue of the input-gradient GEMM (a bias in front of a BatchNorm has an exactly-
-            # zero gradient).  That launch also stores the evaluated dz once and adds dgamma / dbeta, so the weight gradient - a
-            # leaf on the side stream, ordered behind it - is the plain GEMM on one tensor
-            L, b = dz, ps.bn(dz.bn_name)
-            bnargs = (L.aff[0], L.aff[1], L.aff[2], L.aff[3], L.sums, L.count, L.act, L.mul_b, L.rpi)
-            xargs = (None if plain_in else x.scale, None if plain_in else x.shift, NONE if plain_in else x.act, gate, x.H * x.W)
-            self._wg_read_done = None
-            if not want_dx:
-                with self._wgrad_stream():
-                    call("mmd_pwconv_bwd_weight_bn" + self._sfx, L.g, L.z, x.z, ps.g(wkey), M, K, N, *xargs, *bnargs, b["dgamma"],
-                         b["dbeta"])
-                    self._wg_read_done = torch.cuda.current_stream().record_event() if ps.flat.is_cuda else None
-                return None
-            dzm = self._alloc(M, N)
-            if (into is not None and M >= MBW_MIN_ROWS and L.act == SWISH and L.mul_b is None and gate is None
-                    and x.scale is None and x.bn is None and x.act == NONE and ps.flat.is_cuda
-                    and _lib.LIB.load().mmd_mbconv_expand_bwd_supported(K, N) == 1):
-                # thin-input expand conv of a high-resolution block: one pass over (g0, z0) - input gradient, weight gradient, no dz0 in HBM
-                slot, xs = self._contrib(into, True)
-                assert xs is None or not xs[6], "the epilogue sums the accumulated total: not a linear-sum (pooled) tensor"
-                residual = slot.t
-                if slot.t is None:
-                    slot.t = self._alloc(M, K)
-                xsa = (None, None, None, None, 0, None) if xs is None else (xs[0], xs[1], xs[2], xs[4], xs[5], xs[3])
-                call("mmd_mbconv_expand_bwd_fused", L.g, L.z, x.z, ps.w(wkey), slot.t, residual, ps.g(wkey), M, K, N, L.aff[0], L.aff[1], L.aff[2],
-                     L.aff[3], L.sums, L.count, b["dgamma"], b["dbeta"], *xsa)
-                return None
-            if into is not None:
-                slot, xs = self._contrib(into, True)
-                assert xs is None or not xs[6], "the GEMM epilogue sums the accumulated total: not a linear-sum (pooled) tensor"
-                residual = slot.t
-                if slot.t is None:
-                    slot.t = self._alloc(M, K)
-                xsargs = (None, None, None, None, 0, None, None, 0)
-                if xs is not None:
-                    xsargs = (xs[0], xs[1], xs[2], xs[4], xs[5], xs[3], *self._stats_ws(xs[3], M, K))
-                if self._sfx:
-                    call("mmd_pwconv_bwd_data_bn2" + self._sfx, L.g, L.z, ps.w_t(wkey), slot.t, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"],
-                         residual, *xsargs, None, None, None, None, None, None, 0)
-                else:
-                    # (the GEMM reduces over N = the conv's output channels: the slab kernel's "K")
-                    call("mmd_pwconv_bwd_data_bn2_form", L.g, L.z, ps.w_t(wkey), slot.t, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"],
-                         residual, *xsargs, None, None, None, None, None, None, 0, *self._slab_ws(M, N, K, 1), 0)
-                self._pw_wgrad(dzm, x.z, ps.g(wkey), M, K, N, *xargs)
-                return None
-            dx = self._alloc(M, K)
-            if pool5 is not None:
-                # MBConv project conv: the pooled pass of the squeeze-excite / BatchNorm-1 backward over (z1, dx) rides in this launch's epilogue
-                call("mmd_pwconv_bwd_data_bn2" + self._sfx, L.g, L.z, ps.w_t(wkey), dx, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"],
-                     None, None, None, None, None, 0, None, None, 0, *pool5)
-                self._pw_wgrad(dzm, x.z, ps.g(wkey), M, K, N, *xargs)
-                return dx
-            call("mmd_pwconv_bwd_data_bn" + self._sfx, L.g, L.z, ps.w_t(wkey), dx, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"])
-            self._pw_wgrad(dzm, x.z, ps.g(wkey), M, K, N, *xargs)
-            return dx
+            return self._pw_bwd_lazy(dz, x, wkey, N, want_dx, gate, xargs, into, pool5)
         if bias_key:
             self._leaf(lambda dz=dz, gb=ps.g(bias_key): call("mmd_colsum", dz, gb, M, N))
-        self._pw_wgrad(dz, x.z, ps.g(wkey), M, K, N, None if plain_in else x.scale, None if plain_in else x.shift,
-                       NONE if plain_in else x.act, gate, x.H * x.W)
+        self._pw_wgrad(dz, x.z, ps.g(wkey), M, K, N, *xargs)
         if not want_dx:
             return None
         dx = self._alloc(M, K)
@@ -1090,8 +1067,57 @@ class Net:
             return None
         return dx
 
-    def _dw_bwd(self, dzd: torch.Tensor, x: Feat, wkey: str, k: int, s: int, bn_aff=None):
-        """-> dx, or (dx, sums) when `bn_aff` = (scale, shift, mean, invstd) of the BatchNorm(+swish) that produced x: the
+    def _into_slot(self, into: Feat, M: int, K: int) -> Tuple[GradSlot, Optional[torch.Tensor], Optional[BnSums]]:
+        """A GEMM epilogue is about to write dx [M, K] into `into`'s slot -> (slot, residual = what it holds so far or None, xs of the total)"""
+        slot, xs = self._contrib(into, True)
+        assert xs is None or not xs.linear, "the GEMM epilogue sums the accumulated total: not a linear-sum (pooled) tensor"
+        residual = slot.t
+        if slot.t is None:
+            slot.t = self._alloc(M, K)
+        return slot, residual, xs
+
+    def _pw_bwd_lazy(self, L: LazyDz, x: Feat, wkey: str, N: int, want_dx: bool, gate, xargs: tuple, into: Optional[Feat], pool5: Optional[tuple]):
+        """_pw_bwd behind a lazy BatchNorm backward: the BatchNorm backward runs in the operand prologue of the input-gradient GEMM (a
+        bias in front of a BatchNorm has an exactly-zero gradient).  That launch also stores the evaluated dz once and adds dgamma /
+        dbeta, so the weight gradient - a leaf on the side stream, ordered behind it - is the plain GEMM on one tensor"""
+        ps, b, M, K = self.ps, self.ps.bn(L.bn_name), x.M, x.C
+        bnargs = (*L.aff, L.sums, L.count, L.act, L.mul_b, L.rpi)
+        self._wg_read_done = None
+        if not want_dx:
+            with self._wgrad_stream():
+                call("mmd_pwconv_bwd_weight_bn" + self._sfx, L.g, L.z, x.z, ps.g(wkey), M, K, N, *xargs, *bnargs, b["dgamma"], b["dbeta"])
+                self._wg_read_done = torch.cuda.current_stream().record_event() if ps.flat.is_cuda else None
+            return None
+        dzm = self._alloc(M, N)
+        if (into is not None and M >= MBW_MIN_ROWS and L.act == SWISH and L.mul_b is None and gate is None
+                and x.scale is None and x.bn is None and x.act == NONE and ps.flat.is_cuda
+                and _lib.LIB.load().mmd_mbconv_expand_bwd_supported(K, N) == 1):
+            # thin-input expand conv of a high-resolution block: one pass over (g0, z0) - input gradient, weight gradient, no dz0 in HBM
+            slot, residual, xs = self._into_slot(into, M, K)
+            call("mmd_mbconv_expand_bwd_fused", L.g, L.z, x.z, ps.w(wkey), slot.t, residual, ps.g(wkey), M, K, N, *L.aff, L.sums, L.count,
+                 b["dgamma"], b["dbeta"], *(xs.gemm if xs else NO_SUMS_GEMM))
+            return None
+        # the input-gradient GEMM: mmd_pwconv_bwd_data_bn*, or _bn2* when its epilogue has work - (residual, *BnSums.gemm, slot workspace, slots)
+        # for a gradient slot, then pool5 = the MBConv project conv's pooled pass of the squeeze-excite / BatchNorm-1 backward over (z1, dx)
+        slot, residual, xs = self._into_slot(into, M, K) if into is not None else (None, None, None)
+        dx = slot.t if into is not None else self._alloc(M, K)
+        gemm = (L.g, L.z, ps.w_t(wkey), dx, M, K, N, *bnargs, dzm, b["dgamma"], b["dbeta"])
+        if into is not None:
+            xsargs = (*xs.gemm, *self._stats_ws(xs.sums, M, K)) if xs else (*NO_SUMS_GEMM, None, 0)
+            if self._sfx:
+                call("mmd_pwconv_bwd_data_bn2" + self._sfx, *gemm, residual, *xsargs, None, None, None, None, None, None, 0)
+            else:
+                # (the GEMM reduces over N = the conv's output channels: the slab kernel's "K")
+                call("mmd_pwconv_bwd_data_bn2_form", *gemm, residual, *xsargs, None, None, None, None, None, None, 0, *self._slab_ws(M, N, K, 1), 0)
+        elif pool5 is not None:
+            call("mmd_pwconv_bwd_data_bn2" + self._sfx, *gemm, None, *NO_SUMS_GEMM, None, 0, *pool5)
+        else:
+            call("mmd_pwconv_bwd_data_bn" + self._sfx, *gemm)
+        self._pw_wgrad(dzm, x.z, ps.g(wkey), M, K, N, *xargs)
+        return None if into is not None else dx
+
+    def _dw_bwd(self, dzd: torch.Tensor, x: Feat, wkey: str, k: int, s: int, bn_aff: Optional[Aff] = None):
+        """-> dx, or (dx, sums) when `bn_aff` = the coefficients of the BatchNorm(+swish) that produced x: the
         input-gradient launch then also accumulates that BN's backward sums (no separate reduce pass; stride 2, round 5: they ride in the
         gather launch too) and, except for thin stride-1 layers, the conv's weight gradient (tile kernel; for the 3x3 layers that gives up
         the faster row-streaming input-gradient kernel and still wins: a weight-gradient leaf costs its full kernel time on the saturated
@@ -1099,33 +1125,29 @@ class Net:
         ps = self.ps
         wg_inside = bn_aff is not None and (s == 2 or x.C >= 64)      # (block 0, 32 channels at 256^2: 221 us inside vs 47 + 67)
         if not wg_inside:
-            self._leaf(lambda x=x, dzd=dzd, gw=ps.g(wkey): call("mmd_dwconv_bwd_weight", x.z, dzd, gw, x.B, x.H, x.W, x.C, k, s, x.scale, x.shift,
-                                                                 x.act))
+            self._leaf(lambda: call("mmd_dwconv_bwd_weight", x.z, dzd, ps.g(wkey), x.B, x.H, x.W, x.C, k, s, x.scale, x.shift, x.act))
         dx = self._alloc(x.M, x.C)
         if bn_aff is None:
             call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, None, None, None, None, None, None, None, 0, None)
             return dx
         sums = self._zalloc((2 * x.C,), torch.float64)
-        call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, x.z, bn_aff[0], bn_aff[1], bn_aff[2],
-             bn_aff[3], sums, *self._stats_ws(sums, x.M, x.C), ps.g(wkey) if wg_inside else None)
+        call("mmd_dwconv_bwd_data", dzd, ps.w(wkey), dx, x.B, x.H, x.W, x.C, k, s, x.z, *bn_aff, sums,
+             *self._stats_ws(sums, x.M, x.C), ps.g(wkey) if wg_inside else None)
         return dx, sums
 
-    def _pyr_dw_bwd(self, dzd, wkey: str, g, desc, C: int, ls: int, x, sc, sh, act: int, bn=None):
+    def _pyr_dw_bwd(self, dzd, wkey: str, g, desc, C: int, ls: int, x, xo: Optional[int], sums):
         """Input gradient of a shared-weight pyramid depthwise conv; its weight gradient rides in the same launch, and so do the sums of
-        the BatchNorm(+swish) backward that consumes g: `bn` = (mean, invstd, sums) of x's producer (None: x is the heads' input, whose
-        BatchNorms belong to the BiFPN)."""
-        ps = self.ps
-        mu, istd, sums = bn if bn is not None else (None, None, None)
-        call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, ls, x, sc, sh, act, ps.g(wkey),
-             mu, istd, sums)
+        the BatchNorm(+swish) backward that consumes g: xo = where x's producer sits in the contiguous BatchNorm arrays, `sums` its sums
+        (xo None: x is the heads' input, whose BatchNorms belong to the BiFPN)."""
+        ps, t = self.ps, (lambda v: None if xo is None else v[xo:])
+        call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, ls, x, t(self.t_scale), t(self.t_shift),
+             NONE if xo is None else SWISH, ps.g(wkey), t(self.t_mean), t(self.t_invstd), sums)
 
     def _head_bwd(self, hname: str, per_anchor: int, dout: torch.Tensor, tape: dict, pyr: dict, A: int, C: int):
         """Backward of one head over the whole pyramid; returns the gradient w.r.t. the pyramid feature buffer."""
         spec, ps = self.spec, self.ps
-        desc, Mt = pyr["desc"], pyr["total"]
-        rec = tape[hname]
-        nout = spec.num_anchors * per_anchor
-        ls = rec["lev_stride"]
+        rec, nout = tape[hname], spec.num_anchors * per_anchor
+        desc, Mt, ls = pyr["desc"], pyr["total"], rec["lev_stride"]
         dy = self._alloc_pyr(pyr, nout, False)          # (the slice launch writes the padding rows itself; the plain input-gradient GEMMs below write every row)
         call("mmd_slice_rows_pyr", dout, dy, desc, nout, A * per_anchor, (ctypes.c_longlong * len(rec["yoff"]))(*[int(v) for v in rec["yoff"]]))
         hw_key = f"{hname}.header.pointwise_conv.conv.weight"
@@ -1140,26 +1162,23 @@ class Net:
         bsums = self._zalloc((2 * 5 * ls,), torch.float64)
         off0 = rec["layers"][0]["off"]
         g = self._alloc_pyr(pyr, C)
-        self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec["hx"], self.t_scale[xo:], self.t_shift[xo:],
-                         SWISH, bn=(self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
+        self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec["hx"], xo, bsums[2 * (xo - off0):])
         for i in reversed(range(spec.head_layers)):
             L = rec["layers"][i]
             cname = f"{hname}.conv_list.{i}"
             o = L["off"]
             sums = bsums[2 * (o - off0):]
             dz = self._alloc_pyr(pyr, C)
-            call("mmd_bn_bwd_apply_pyr", g, L["z"], self.t_mean[o:], self.t_invstd[o:], ps.flat[ps.gamma_off + o:], sums,
-                 desc, ls, dz, ps.grad[ps.gamma_off + o:], ps.grad[ps.beta_off + o:], C, self.t_scale[o:], self.t_shift[o:],
-                 SWISH)
+            call("mmd_bn_bwd_apply_pyr", g, L["z"], self.t_mean[o:], self.t_invstd[o:], ps.flat[ps.gamma_off + o:], sums, desc, ls, dz,
+                 ps.grad[ps.gamma_off + o:], ps.grad[ps.beta_off + o:], C, self.t_scale[o:], self.t_shift[o:], SWISH)
             wkey = f"{cname}.pointwise_conv.conv.weight"
             self._pw_wgrad(dz, L["zd"], ps.g(wkey), Mt, C, C)
             dzd = self._alloc_pyr(pyr, C, False)
             call("mmd_pwconv_bwd_data" + self._sfx, dz, ps.w_t(wkey), dzd, Mt, C, C, 0)
             xo = L["x_off"]
             g = self._alloc_pyr(pyr, C)
-            self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L["x"], None if xo is None else self.t_scale[xo:],
-                             None if xo is None else self.t_shift[xo:], NONE if xo is None else SWISH,
-                             bn=None if xo is None else (self.t_mean[xo:], self.t_invstd[xo:], bsums[2 * (xo - off0):]))
+            self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L["x"], xo,
+                             None if xo is None else bsums[2 * (xo - off0):])
         return g
 
     def backward(self, dcls_logit: torch.Tensor, dreg: torch.Tensor, dfeats: List[Optional[torch.Tensor]],
@@ -1170,23 +1189,29 @@ class Net:
         that the caller can start the all-reduce of those gradients; backward_finish() runs blocks < k and the stem.
         dfeat_pyr: the same gradients as dfeats as ONE pyramid row buffer (dfeats[l] are its level slices): the heads' input gradients
         and it are then added in one launch that also takes the BatchNorm-backward sums of the last BiFPN cell's five output nodes."""
-        spec, ps, tape = self.spec, self.ps, self.tape
-        feats: List[Feat] = tape["feats"]
-        A = tape["A"]
-        slots: Dict[int, GradSlot] = {}
-        self._bw = {"slots": slots, "stem_sums": None}
-        self._wg_pending, self._wg_segment, self._se_wg = [], 0, []
-        self._wg_count = 0
-        slot = self._slot
+        # (gradient slot of every activation tensor; the stem BatchNorm's backward sums, once block 0's input-gradient launch has taken them)
+        self._slots, self._stem_sums = {}, None
+        self._wg_pending, self._wg_segment, self._se_wg, self._wg_count = [], 0, [], 0
+        self._backward_heads(dcls_logit, dreg, dfeats, dfeat_pyr)
+        self._backward_bifpn()
+        self._backward_blocks([b for b in self.spec.blocks if stop_before is None or b.idx >= stop_before])
+        if stop_before is None:
+            self.backward_finish(0)
+        else:
+            self._wg_flush()
+            if self._wg is not None:
+                torch.cuda.current_stream().wait_stream(self._wg)
+
+    def _backward_heads(self, dcls_logit, dreg, dfeats, dfeat_pyr):
+        """Both heads, every layer over the whole pyramid in one launch; their input gradients (+ dfeats) land in the last BiFPN cell's slots."""
+        spec, ps, tape, pyr = self.spec, self.ps, self.tape, self._pyr
+        feats, C = tape["feats"], tape["feats"][0].C
+        lv = lambda t, lvl: t[pyr["row0"][lvl]:pyr["row0"][lvl] + pyr["rows"][lvl]]      # level lvl's rows of a pyramid row buffer
         fold_heads = ps.flat.is_cuda and (dfeat_pyr is not None or all(d is None for d in dfeats))
         if not fold_heads:
             for f, d in zip(feats, dfeats):
                 if d is not None:
-                    slot(f).t = d
-        # ---- heads: every layer handles the whole pyramid in one launch
-        pyr = self._pyr
-        desc, Mt = pyr["desc"], pyr["total"]
-        C = feats[0].C
+                    self._slot(f).t = d
         # the two heads are independent until their input gradients meet: the regressor runs on a side stream
         # (a parallel branch of the captured graph); bsums / workspaces are allocated here on the host, in order
         main_stream = torch.cuda.current_stream() if ps.flat.is_cuda else None
@@ -1199,125 +1224,40 @@ class Net:
             if use_side:
                 self._side.wait_event(fork)
             with torch.cuda.stream(self._side if use_side else main_stream):
-                gparts.append(self._head_bwd(hname, per_anchor, dout, tape, pyr, A, C))
+                gparts.append(self._head_bwd(hname, per_anchor, dout, tape, pyr, tape["A"], C))
         if main_stream is not None:
             main_stream.wait_stream(self._side)
         gsum = gparts[0]
         if fold_heads:
             # classifier + regressor (+ MTA) gradients in one launch, which also takes the BatchNorm-backward sums of the five output nodes
-            vp = ctypes.c_void_p
-            ptrs = [[None] * 5 for _ in range(4)]
+            quads = []
             for lvl, f in enumerate(feats):
                 sl, xs = self._contrib(f, True)
-                sl.t = gsum[pyr["row0"][lvl]:pyr["row0"][lvl] + pyr["rows"][lvl]]
-                if xs is not None:
-                    for k in range(4):
-                        ptrs[k][lvl] = xs[k].data_ptr()
-            arrs = [(vp * 5)(*p_) for p_ in ptrs]
-            call("mmd_pyr_add_bnsums", gparts[0], gparts[1], dfeat_pyr, gsum, desc, C, *arrs)
+                sl.t = lv(gsum, lvl)
+                quads.append(NO_SUMS_QUAD if xs is None else [t.data_ptr() for t in xs.quad])
+            arrs = [(ctypes.c_void_p * 5)(*col) for col in zip(*quads)]         # (z, mean, invstd, sums), each one pointer per level
+            call("mmd_pyr_add_bnsums", gparts[0], gparts[1], dfeat_pyr, gsum, pyr["desc"], C, *arrs)
         else:
             call("mmd_scale_acc", gparts[1], gsum, None, 0, 0, 1, gsum.numel())
             for lvl, f in enumerate(feats):
-                self._acc(f, gsum[pyr["row0"][lvl]:pyr["row0"][lvl] + pyr["rows"][lvl]])
-        # ---- BiFPN (cells and nodes in reverse)
+                self._acc(f, lv(gsum, lvl))
+
+    def _backward_bifpn(self):
+        """BiFPN cells and nodes in reverse; ONE launch at the end finishes all fusion-weight gradients (the nodes' dot products: wdot_all)."""
+        spec, ps, tape = self.spec, self.ps, self.tape
         n_nodes = sum(len(tape[f"bifpn.{c}.nodes"]) for c in range(spec.fpn_cells))
         wdot_all = self._zalloc((4 * n_nodes,))
-        theta_desc, node_i = [], 0
-        xsn = lambda xs: (None, None, None, None) if xs is None else xs[:4]
+        theta_desc = []
         for c in reversed(range(spec.fpn_cells)):
             cell = f"bifpn.{c}"
             for rec in reversed(tape[cell + ".nodes"]):
-                out: Feat = rec["out"]
-                s = slot(out)
-                if s.t is None:
+                if self._slot(rec["out"]).t is None:
                     continue          # node output unused downstream (cannot happen in this topology)
-                name = f"{cell}.{rec['conv']}"
-                W = out.C
-                wkey, dwkey = f"{name}.pointwise_conv.conv.weight", f"{name}.depthwise_conv.conv.weight"
-                L = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.bn", NONE, out.M, W, lazy=True, sums=s.sums if s.have_sums else None)
-                ops = in0, in1, up, pl = rec["in0"], rec["in1"], rec["up"], rec["pl"]
-                mode_ = (1 if in1 is not None else 0) | (2 if up is not None else 0) | (4 if pl is not None else 0)
-                # whole-node backward (round 4): the node's BatchNorm backward + its 1x1 conv's input gradient (exact fp32 MFMA) + the depthwise /
-                # fusion backward in ONE launch instead of a GEMM launch in front of it - 40 launches off the backward's serial chain.  bf16
-                # modes: up to width 160 (closer to the fp32 reference than the mode's operand-rounding rule asks for, like the whole-node
-                # forward; D2 bf16 13.48 -> 13.25 ms/step); D4 (224) 49.9 -> 52.2: there the bf16 GEMM + two-launch form stays
-                full = W % 16 == 0 and W <= 224 and mode_ in (2, 5, 4) and (self.precision == "fp32" or W <= 160)
-                dzd = None if full else self._pw_bwd(L, rec["zd"], wkey, W, None, True)
-                th = ps.w(f"{cell}.{rec['theta']}")
-                # One gradient contribution per operand, in the order in0, in1, up, pl; all of them leave the one launch below: the
-                # same-resolution operands directly, the upsampled one as 2x2 block sums, the pooled one scattered - added to each
-                # window's arg-max with atomics, on top of the earlier contributions (or of zeros: a zero-initialised arena buffer when this
-                # is the first one), no dx tensor and no max-pool gather launch over the 4x larger source map.  The launch also takes the
-                # BatchNorm-backward sums of every operand gradient it completes (bnsums); `own` bits: an operand that is max-pooled by
-                # ANOTHER node keeps its sums linearly, this launch adds the sums of its share
-                grad, bnsums, own = [], [], 0
-                for oi, o in enumerate(ops):
-                    if o is None:
-                        grad.append((None, 0))
-                        bnsums.append((None, None, None, None))
-                        continue
-                    sl, xs = self._contrib(o, True)
-                    accumulate = 0 if sl.t is None else 1
-                    if sl.t is None:
-                        sl.t = self._zalloc((o.M, W)) if oi == 3 else self._alloc(o.M, W)
-                    grad.append((sl.t, accumulate))
-                    bnsums.append(xsn(xs))
-                    if oi < 3 and xs is not None and xs[6]:
-                        own |= 1 << oi
-                assert in1 is None or grad[0][0].data_ptr() != grad[1][0].data_ptr()
-                # the fusion-weight gradients of all nodes are finished by ONE launch after the BiFPN (their dot products land in wdot_all)
-                wdot = wdot_all[4 * node_i:4 * node_i + 4]
-                theta_desc.append((ps.entries[f"{cell}.{rec['theta']}"].off, th.numel()))
-                node_i += 1
-                # lazy operands: their values are read as z * scale + shift (finalized coefficients) inside the launch
-                lzb = [o is not None and o.bn is not None for o in ops]
-                scs = shs = None
-                if any(lzb):
-                    vp = ctypes.c_void_p
-                    scs = (vp * 4)(*[(o.scale.data_ptr() if l else None) for o, l in zip(ops, lzb)])
-                    shs = (vp * 4)(*[(o.shift.data_ptr() if l else None) for o, l in zip(ops, lzb)])
-                xargs = (*[o.z if o is not None else None for o in ops], th, ps.w(dwkey))
-                gargs = (in0.B, in0.H, in0.W, W, *grad[0], *grad[1], *grad[2], ps.g(dwkey), *bnsums[0], *bnsums[1], *bnsums[2])
-                plargs = (grad[3][0], *bnsums[3], own)
-                if full:
-                    # the evaluated dz is stored once for the conv's weight-gradient GEMM (grouped flush)
-                    bq, zdf = ps.bn(L.bn_name), rec["zd"]
-                    dzm = self._alloc(out.M, W)
-                    call("mmd_bifpn_node_bwd_full", *xargs, wdot, *gargs, *plargs, scs, shs, L.g, L.z, L.aff[0], L.aff[2], L.aff[3], L.sums,
-                         L.count, ps.w_t(wkey), dzm, bq["dgamma"], bq["dbeta"])
-                    self._pw_wgrad(dzm, zdf.z, ps.g(wkey), out.M, W, W, None, None, NONE, None, zdf.H * zdf.W)
-                elif scs is not None:
-                    call("mmd_bifpn_node_dw_bwd3_lz", *xargs, dzd, None, wdot, *gargs, *plargs, scs, shs)
-                elif pl is not None or own:
-                    call("mmd_bifpn_node_dw_bwd3", *xargs, dzd, None, wdot, *gargs, *plargs)
-                else:
-                    call("mmd_bifpn_node_dw_bwd2", *xargs, dzd, None, wdot, *gargs)
+                n = len(theta_desc)
+                self._node_bwd(cell, rec, wdot_all[4 * n:4 * n + 4])
+                theta_desc.append((ps.entries[f"{cell}.{rec['theta']}"].off, ps.w(f"{cell}.{rec['theta']}").numel()))
             if c == 0:
-                first = tape[cell + ".first"]
-                c6, p6_in, p7_in = first["c6"], first["p6_in"], first["p7_in"]
-                s7, s6 = slot(p7_in), slot(p6_in)
-                if s7.t is not None:
-                    self._contrib(p6_in, False)
-                    acc = 0 if s6.t is None else 1
-                    if s6.t is None:
-                        s6.t = self._alloc(p6_in.M, p6_in.C)
-                    call("mmd_maxpool_same_bwd_acc", p6_in.z, s7.t, s6.t, None, 0, 0, acc, p6_in.B, p6_in.H, p6_in.W, p6_in.C)
-                if s6.t is not None:
-                    sc6, xs = self._contrib(c6, True)
-                    sc6.t = self._alloc(c6.M, c6.C)
-                    call("mmd_maxpool_same_bwd_acc2", c6.z, s6.t, sc6.t, None, 0, 0, 0, c6.B, c6.H, c6.W, c6.C, *xsn(xs))
-                for nm in ("p5_down_channel_2", "p4_down_channel_2", "p5_down_channel", "p4_down_channel",
-                           "p3_down_channel", "p5_to_p6"):
-                    name = f"{cell}.{nm}"
-                    rec = tape[name]
-                    out = rec["out"]
-                    s = slot(out)
-                    if s.t is None:
-                        continue
-                    x: Feat = rec["x"]
-                    dz = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.1", NONE, out.M, out.C, lazy=True,
-                                      sums=s.sums if s.have_sums else None)
-                    self._pw_bwd(dz, x, f"{name}.0.conv.weight", out.C, None, True, into=x)
+                self._bifpn_inputs_bwd(cell)
         if theta_desc:
             key = tuple(theta_desc)
             if key not in self._theta_desc:
@@ -1325,13 +1265,89 @@ class Net:
                     raise RuntimeError("fusion-weight gradient operands moved after graph capture")
                 self._theta_desc[key] = torch.tensor(theta_desc, dtype=torch.int64, device=self.device)
             self._leaf(lambda d=self._theta_desc[key], n=len(theta_desc): call("mmd_bifpn_theta_bwd_batched", ps.flat, ps.grad, wdot_all, d, n))
-        self._backward_blocks([b for b in spec.blocks if stop_before is None or b.idx >= stop_before])
-        if stop_before is None:
-            self.backward_finish(0)
+
+    def _node_bwd(self, cell: str, rec: dict, wdot: torch.Tensor):
+        """Backward of one BiFPN node; wdot [4] receives the dot products of its fusion-weight gradient."""
+        ps, out = self.ps, rec["out"]
+        s, name, W = self._slot(out), f"{cell}.{rec['conv']}", out.C
+        wkey, dwkey = f"{name}.pointwise_conv.conv.weight", f"{name}.depthwise_conv.conv.weight"
+        L = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.bn", NONE, out.M, W, lazy=True, sums=s.sums if s.have_sums else None)
+        ops = in0, in1, up, pl = rec["in0"], rec["in1"], rec["up"], rec["pl"]
+        mode_ = (1 if in1 is not None else 0) | (2 if up is not None else 0) | (4 if pl is not None else 0)
+        # whole-node backward (round 4): the node's BatchNorm backward + its 1x1 conv's input gradient (exact fp32 MFMA) + the depthwise /
+        # fusion backward in ONE launch instead of a GEMM launch in front of it - 40 launches off the backward's serial chain.  bf16
+        # modes: up to width 160 (closer to the fp32 reference than the mode's operand-rounding rule asks for, like the whole-node
+        # forward; D2 bf16 13.48 -> 13.25 ms/step); D4 (224) 49.9 -> 52.2: there the bf16 GEMM + two-launch form stays
+        full = W % 16 == 0 and W <= 224 and mode_ in (2, 5, 4) and (self.precision == "fp32" or W <= 160)
+        dzd = None if full else self._pw_bwd(L, rec["zd"], wkey, W, None, True)
+        th = ps.w(f"{cell}.{rec['theta']}")
+        # One gradient contribution per operand, in the order in0, in1, up, pl; all of them leave the one launch below: the
+        # same-resolution operands directly, the upsampled one as 2x2 block sums, the pooled one scattered - added to each
+        # window's arg-max with atomics, on top of the earlier contributions (or of zeros: a zero-initialised arena buffer when this
+        # is the first one), no dx tensor and no max-pool gather launch over the 4x larger source map.  The launch also takes the
+        # BatchNorm-backward sums of every operand gradient it completes (bnsums); `own` bits: an operand that is max-pooled by
+        # ANOTHER node keeps its sums linearly, this launch adds the sums of its share
+        grad, bnsums, own = [(None, 0)] * 4, [NO_SUMS_QUAD] * 4, 0
+        for oi, o in enumerate(ops):
+            if o is None:
+                continue
+            sl, xs = self._contrib(o, True)
+            accumulate = 0 if sl.t is None else 1
+            if sl.t is None:
+                sl.t = self._zalloc((o.M, W)) if oi == 3 else self._alloc(o.M, W)
+            grad[oi] = (sl.t, accumulate)
+            if xs is not None:
+                bnsums[oi] = xs.quad
+                own |= (1 << oi) if oi < 3 and xs.linear else 0
+        assert in1 is None or grad[0][0].data_ptr() != grad[1][0].data_ptr()
+        # lazy operands: their values are read as z * scale + shift (finalized coefficients) inside the launch
+        lzb = [o is not None and o.bn is not None for o in ops]
+        scs = shs = None
+        if any(lzb):
+            scs = (ctypes.c_void_p * 4)(*[(o.scale.data_ptr() if l else None) for o, l in zip(ops, lzb)])
+            shs = (ctypes.c_void_p * 4)(*[(o.shift.data_ptr() if l else None) for o, l in zip(ops, lzb)])
+        xargs = (*[o.z if o is not None else None for o in ops], th, ps.w(dwkey))
+        gargs = (in0.B, in0.H, in0.W, W, *grad[0], *grad[1], *grad[2], ps.g(dwkey), *bnsums[0], *bnsums[1], *bnsums[2])
+        plargs = (grad[3][0], *bnsums[3], own)
+        if full:
+            # the evaluated dz is stored once for the conv's weight-gradient GEMM (grouped flush)
+            bq, zdf = ps.bn(L.bn_name), rec["zd"]
+            dzm = self._alloc(out.M, W)
+            call("mmd_bifpn_node_bwd_full", *xargs, wdot, *gargs, *plargs, scs, shs, L.g, L.z, L.aff.scale, L.aff.mean, L.aff.invstd, L.sums,
+                 L.count, ps.w_t(wkey), dzm, bq["dgamma"], bq["dbeta"])
+            self._pw_wgrad(dzm, zdf.z, ps.g(wkey), out.M, W, W, None, None, NONE, None, zdf.H * zdf.W)
+        elif scs is not None:
+            call("mmd_bifpn_node_dw_bwd3_lz", *xargs, dzd, None, wdot, *gargs, *plargs, scs, shs)
+        elif pl is not None or own:
+            call("mmd_bifpn_node_dw_bwd3", *xargs, dzd, None, wdot, *gargs, *plargs)
         else:
-            self._wg_flush()
-            if self._wg is not None:
-                torch.cuda.current_stream().wait_stream(self._wg)
+            call("mmd_bifpn_node_dw_bwd2", *xargs, dzd, None, wdot, *gargs)
+
+    def _bifpn_inputs_bwd(self, cell: str):
+        """The first cell's inputs: the p6 / p7 max-pool backward, then the six down-channel convs (into the backbone taps' slots)."""
+        tape = self.tape
+        first = tape[cell + ".first"]
+        c6, p6_in, p7_in = first["c6"], first["p6_in"], first["p7_in"]
+        s7, s6 = self._slot(p7_in), self._slot(p6_in)
+        if s7.t is not None:
+            self._contrib(p6_in, False)
+            acc = 0 if s6.t is None else 1
+            if s6.t is None:
+                s6.t = self._alloc(p6_in.M, p6_in.C)
+            call("mmd_maxpool_same_bwd_acc", p6_in.z, s7.t, s6.t, None, 0, 0, acc, p6_in.B, p6_in.H, p6_in.W, p6_in.C)
+        if s6.t is not None:
+            sc6, xs = self._contrib(c6, True)
+            sc6.t = self._alloc(c6.M, c6.C)
+            call("mmd_maxpool_same_bwd_acc2", c6.z, s6.t, sc6.t, None, 0, 0, 0, c6.B, c6.H, c6.W, c6.C, *(xs.quad if xs else NO_SUMS_QUAD))
+        for nm in ("p5_down_channel_2", "p4_down_channel_2", "p5_down_channel", "p4_down_channel", "p3_down_channel", "p5_to_p6"):
+            name = f"{cell}.{nm}"
+            rec = tape[name]
+            out, x = rec["out"], rec["x"]
+            s = self._slot(out)
+            if s.t is None:
+                continue
+            dz = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.1", NONE, out.M, out.C, lazy=True, sums=s.sums if s.have_sums else None)
+            self._pw_bwd(dz, x, f"{name}.0.conv.weight", out.C, None, True, into=x)
 
     def backward_finish(self, stop_before: int):
         """Second part of a split backward: backbone blocks < stop_before, then the stem."""
@@ -1339,105 +1355,89 @@ class Net:
         self._backward_stem()
 
     def _backward_blocks(self, blocks):
-        """Backbone blocks in reverse."""
-        spec, ps, tape = self.spec, self.ps, self.tape
-        slot = self._slot
-        P = "backbone_net.model"
-        stem_sums = self._bw["stem_sums"]
+        """Backbone blocks in reverse, then the squeeze-excite FC weight gradients of all of them in one launch."""
         for blk in reversed(blocks):
-            q = f"{P}._blocks.{blk.idx}"
-            rec = tape[f"blk{blk.idx}"]
-            out: Feat = rec["out"]
-            inp: Feat = rec["inp"]
-            s = slot(out)
-            if s.t is None:
-                continue              # blocks after the last tap do not exist; defensive
-            dy = s.t
-            f1: Feat = rec["f1"]
-            M1, HW1 = f1.M, f1.H * f1.W
-            dz2 = self._bn_bwd(dy, rec["z2"], rec["bn2"], f"{q}._bn2", NONE, M1, blk.cout, rpi=HW1, mul_b=rec["rs"], lazy=True,
-                               sums=s.sums if s.have_sums else None)
-            # squeeze-excite backward.  One pass over (z1, g1) pools d(gate) AND the partials of the BN-1 backward sums (the SE kernels finish
-            # those sums once dpooled is known, so the expanded tensor is not read by a BN reduce pass); that pass rides in the epilogue of
-            # the project conv's input-gradient GEMM, which produces g1
-            a1 = rec["bn1"]
-            pool5 = self._zalloc((5, f1.B, blk.cmid))
-            g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec["gate"],
-                              pool5=(f1.z, a1[0], a1[1], a1[2], a1[3], pool5, f1.B))
-            # the skip branch may ADOPT dy as the gradient slot of the block input, and the block's own input gradient is later
-            # accumulated into that buffer in place; with a lazy BatchNorm backward the project conv's weight-gradient GEMM (side
-            # stream) still reads dy, so that later accumulation waits for it (the event is long past by then)
-            dy_read = self._wg_read_done if blk.skip else None
-            if blk.skip:
-                self._acc(inp, dy)
-            dpe = self._alloc(f1.B, blk.cmid)
-            dpr = self._alloc(f1.B, blk.se)
-            dpooled = self._alloc(f1.B, blk.cmid)
-            sums1 = self._zalloc((2 * blk.cmid,), torch.float64)
-            segrads = (ps.g(f"{q}._se_reduce.conv.weight"), ps.g(f"{q}._se_reduce.conv.bias"), ps.g(f"{q}._se_expand.conv.weight"),
-                       ps.g(f"{q}._se_expand.conv.bias"))
-            # two wide launches for the two FC data gradients (both in one, mmd_se_fc_bwd_fused, is correct, but every block recomputes its
-            # image's hidden gradient - S*C MACs, serial per wave: measured 17.0 -> 17.7 ms/step)
-            dh = self._zalloc((f1.B, blk.se))
-            call("mmd_se_fc_bwd", pool5[0], rec["gate"], rec["hpre"], rec["pooled"], ps.w(f"{q}._se_reduce.conv.weight"),
-                 ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dh, dpooled, 1.0 / HW1, None, None, None, None,
-                 f1.B, blk.cmid, blk.se, pool5, sums1)
-            # the FC weight gradients of all blocks of the segment in one launch at its end
-            self._se_wg.append((dpe, dpr, rec["hpre"], rec["pooled"], *segrads, blk.cmid, blk.se))
-            f0: Feat = rec.get("f0", inp)
-            # BatchNorm-1 backward evaluated in the prologue of the depthwise input-gradient launch (stride-1 blocks with an expand conv and
-            # >= 64 channels: 17 of D2's 23): dz1 is never written; the other blocks keep the apply pass
-            bn1_in_dw = blk.expand != 1 and blk.stride == 1 and blk.cmid >= 64
-            if not bn1_in_dw:
-                dz1 = self._bn_bwd(g1, f1.z, a1, f"{q}._bn1", SWISH, M1, blk.cmid, rpi=HW1, mul_bc=rec["gate"],
-                                   add_bc=dpooled, sums=sums1)
-            if bn1_in_dw:
-                b1, a0 = ps.bn(f"{q}._bn1"), rec["bn0"]
-                wkey = f"{q}._depthwise_conv.conv.weight"
-                g0 = self._alloc(f0.M, f0.C)
-                sums0 = self._zalloc((2 * f0.C,), torch.float64)
-                call("mmd_dwconv_bwd_data_bn1", g1, f1.z, ps.w(wkey), g0, f0.B, f0.H, f0.W, f0.C, blk.kernel, a1[0], a1[1], a1[2], a1[3],
-                     sums1, M1, rec["gate"], dpooled, b1["dgamma"], b1["dbeta"], f0.z, a0[0], a0[1], a0[2], a0[3], sums0,
-                     *self._stats_ws(sums0, f0.M, f0.C), ps.g(wkey))
-                dz0 = self._bn_bwd(g0, f0.z, rec["bn0"], f"{q}._bn0", SWISH, f0.M, blk.cmid, sums=sums0, lazy=True)
-                if dy_read is not None:
-                    torch.cuda.current_stream().wait_event(dy_read)
-                self._pw_bwd(dz0, inp, f"{q}._expand_conv.conv.weight", blk.cmid, None, True, into=inp)
-            elif blk.expand != 1:
-                g0, sums0 = self._dw_bwd(dz1, f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride, bn_aff=rec["bn0"])
-                dz0 = self._bn_bwd(g0, f0.z, rec["bn0"], f"{q}._bn0", SWISH, f0.M, blk.cmid, sums=sums0, lazy=True)
-                if dy_read is not None:
-                    torch.cuda.current_stream().wait_event(dy_read)
-                # the input gradient lands in (on top of) the block input's slot - which may be dy itself, adopted by the skip branch
-                # above - and, as that slot's last contribution, carries the previous block's BatchNorm-2 backward sums with it
-                self._pw_bwd(dz0, inp, f"{q}._expand_conv.conv.weight", blk.cmid, None, True, into=inp)
-            elif blk.idx == 0 and not blk.skip and blk.stride == 1 and slot(inp).t is None:
-                # block 0 consumes the stem activation directly and is its only consumer: the stem BN's backward sums ride
-                # in this input-gradient launch
-                g0, stem_sums = self._dw_bwd(dz1, f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride,
-                                             bn_aff=(inp.scale, inp.shift, tape["stem"][2], tape["stem"][3]))
-                self._acc(inp, g0)
-            else:
-                g0 = self._dw_bwd(dz1, f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride)
-                if dy_read is not None:
-                    torch.cuda.current_stream().wait_event(dy_read)
-                self._acc(inp, g0)
-        self._bw["stem_sums"] = stem_sums
+            self._block_bwd(blk, self.tape[f"blk{blk.idx}"])
         if self._se_wg:
             recs, self._se_wg = self._se_wg, []
-            key = tuple((r[0].data_ptr(), r[1].data_ptr(), r[2].data_ptr(), r[3].data_ptr(), r[4].data_ptr()) for r in recs)
+            key = tuple((r.dpe.data_ptr(), r.dpr.data_ptr(), r.hpre.data_ptr(), r.pooled.data_ptr(), r.g_reduce_w.data_ptr()) for r in recs)
             if key not in self._se_wg_tabs:
                 if self.arena.frozen:
                     raise RuntimeError("squeeze-excite weight-gradient operands moved after graph capture")
-                rows = [[t.data_ptr() for t in r[:8]] + [r[8], r[9]] for r in recs]
+                rows = [[v.data_ptr() if isinstance(v, torch.Tensor) else v for v in r] for r in recs]
                 self._se_wg_tabs[key] = torch.tensor(rows, dtype=torch.int64, device=self.device)
-            tab, nb = self._se_wg_tabs[key], recs[0][0].shape[0]
-            self._leaf(lambda tab=tab, n=len(recs), mx=max(r[8] * r[9] for r in recs), nb=nb: call("mmd_se_fc_wgrad_batched", tab, n, mx, nb))
+            tab, nb = self._se_wg_tabs[key], recs[0].dpe.shape[0]
+            self._leaf(lambda tab=tab, n=len(recs), mx=max(r.C * r.S for r in recs), nb=nb: call("mmd_se_fc_wgrad_batched", tab, n, mx, nb))
+
+    def _block_bwd(self, blk, rec: dict):
+        """Backward of one MBConv block: project conv, squeeze-excite, depthwise conv, expand conv."""
+        ps, q = self.ps, f"backbone_net.model._blocks.{blk.idx}"
+        inp, f1 = rec["inp"], rec["f1"]
+        s = self._slot(rec["out"])
+        if s.t is None:
+            return                # blocks after the last tap do not exist; defensive
+        dy, M1, HW1 = s.t, f1.M, f1.H * f1.W
+        dz2 = self._bn_bwd(dy, rec["z2"], rec["bn2"], f"{q}._bn2", NONE, M1, blk.cout, rpi=HW1, mul_b=rec["rs"], lazy=True,
+                           sums=s.sums if s.have_sums else None)
+        # squeeze-excite backward.  One pass over (z1, g1) pools d(gate) AND the partials of the BN-1 backward sums (the SE kernels finish
+        # those sums once dpooled is known, so the expanded tensor is not read by a BN reduce pass); that pass rides in the epilogue of
+        # the project conv's input-gradient GEMM, which produces g1
+        a1: Aff = rec["bn1"]
+        pool5 = self._zalloc((5, f1.B, blk.cmid))
+        g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec["gate"], pool5=(f1.z, *a1, pool5, f1.B))
+        # the skip branch may ADOPT dy as the gradient slot of the block input, and the block's own input gradient is later
+        # accumulated into that buffer in place; with a lazy BatchNorm backward the project conv's weight-gradient GEMM (side
+        # stream) still reads dy, so that later accumulation waits for it (the event is long past by then)
+        dy_read = self._wg_read_done if blk.skip else None
+        if blk.skip:
+            self._acc(inp, dy)
+        dpe, dpr, dpooled = self._alloc(f1.B, blk.cmid), self._alloc(f1.B, blk.se), self._alloc(f1.B, blk.cmid)
+        sums1 = self._zalloc((2 * blk.cmid,), torch.float64)
+        segrads = [ps.g(f"{q}._se_{fc}.conv.{p}") for fc in ("reduce", "expand") for p in ("weight", "bias")]
+        # two wide launches for the two FC data gradients (both in one, mmd_se_fc_bwd_fused, is correct, but every block recomputes its
+        # image's hidden gradient - S*C MACs, serial per wave: measured 17.0 -> 17.7 ms/step)
+        dh = self._zalloc((f1.B, blk.se))
+        call("mmd_se_fc_bwd", pool5[0], rec["gate"], rec["hpre"], rec["pooled"], ps.w(f"{q}._se_reduce.conv.weight"),
+             ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dh, dpooled, 1.0 / HW1, None, None, None, None, f1.B, blk.cmid, blk.se, pool5, sums1)
+        # the FC weight gradients of all blocks of the segment in one launch at its end
+        self._se_wg.append(SeWgRec(dpe, dpr, rec["hpre"], rec["pooled"], *segrads, blk.cmid, blk.se))
+        f0: Feat = rec.get("f0", inp)
+        wkey = f"{q}._depthwise_conv.conv.weight"
+        # BatchNorm-1 backward evaluated in the prologue of the depthwise input-gradient launch (stride-1 blocks with an expand conv and
+        # >= 64 channels: 17 of D2's 23): dz1 is never written; the other blocks keep the apply pass
+        bn1_in_dw = blk.expand != 1 and blk.stride == 1 and blk.cmid >= 64
+        if not bn1_in_dw:
+            dz1 = self._bn_bwd(g1, f1.z, a1, f"{q}._bn1", SWISH, M1, blk.cmid, rpi=HW1, mul_bc=rec["gate"], add_bc=dpooled, sums=sums1)
+        if blk.expand != 1:
+            a0: Aff = rec["bn0"]
+            if bn1_in_dw:
+                b1 = ps.bn(f"{q}._bn1")
+                g0 = self._alloc(f0.M, f0.C)
+                sums0 = self._zalloc((2 * f0.C,), torch.float64)
+                call("mmd_dwconv_bwd_data_bn1", g1, f1.z, ps.w(wkey), g0, f0.B, f0.H, f0.W, f0.C, blk.kernel, *a1, sums1, M1, rec["gate"],
+                     dpooled, b1["dgamma"], b1["dbeta"], f0.z, *a0, sums0, *self._stats_ws(sums0, f0.M, f0.C), ps.g(wkey))
+            else:
+                g0, sums0 = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride, bn_aff=a0)
+            dz0 = self._bn_bwd(g0, f0.z, a0, f"{q}._bn0", SWISH, f0.M, blk.cmid, sums=sums0, lazy=True)
+            if dy_read is not None:
+                torch.cuda.current_stream().wait_event(dy_read)
+            # the input gradient lands in (on top of) the block input's slot - which may be dy itself, adopted by the skip branch
+            # above - and, as that slot's last contribution, carries the previous block's BatchNorm-2 backward sums with it
+            self._pw_bwd(dz0, inp, f"{q}._expand_conv.conv.weight", blk.cmid, None, True, into=inp)
+        elif blk.idx == 0 and not blk.skip and blk.stride == 1 and self._slot(inp).t is None:
+            # block 0 consumes the stem activation directly and is its only consumer: the stem BN's backward sums ride
+            # in this input-gradient launch
+            mu, istd = self.tape["stem"][2:]
+            g0, self._stem_sums = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride, bn_aff=Aff(inp.scale, inp.shift, mu, istd))
+            self._acc(inp, g0)
+        else:
+            g0 = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride)
+            if dy_read is not None:
+                torch.cuda.current_stream().wait_event(dy_read)
+            self._acc(inp, g0)
 
     def _backward_stem(self):
-        ps, tape = self.ps, self.tape
-        P = "backbone_net.model"
-        stem_sums = self._bw["stem_sums"]
+        ps, tape, P, stem_sums = self.ps, self.tape, "backbone_net.model", self._stem_sums
         ximg, stem, mu, istd = tape["stem"]
         s = self._slot(stem)
         Bi, Cin, Hi, Wi = ximg.shape
@@ -1464,7 +1464,7 @@ class Net:
             call("mmd_stem_conv_bwd_weight_bn", ximg, s.t, stem.z, ps.g(f"{P}._conv_stem.conv.weight"), ws, Bi, Cin, Hi, Wi, ps.stem_kp, stem.C,
                  stem.scale, stem.shift, mu, istd, stem_sums, stem.M, SWISH, b0["dgamma"], b0["dbeta"])
         else:
-            dz = self._bn_bwd(s.t, stem.z, (stem.scale, stem.shift, mu, istd), f"{P}._bn0", SWISH, stem.M, stem.C, sums=stem_sums)
+            dz = self._bn_bwd(s.t, stem.z, Aff(stem.scale, stem.shift, mu, istd), f"{P}._bn0", SWISH, stem.M, stem.C, sums=stem_sums)
             with self._wgrad_stream():          # im2col of the input image + weight-gradient GEMM, both off the critical path
                 col = self._alloc(stem.M, ps.stem_kp)
                 call("mmd_stem_im2col", ximg, col, Bi, Cin, Hi, Wi, ps.stem_kp)
