@@ -158,7 +158,11 @@ __device__ __forceinline__ void pw_gemm_body(const PwArgs& a) {
   }
   // grouped frozen nets: this row tile's group (a tile never straddles two groups: host-checked) selects the parameter set
   size_t gw = 0, gb = 0;
-  if (a.g_images) { const int gi = ((m0 - srow0) / rpi) / a.g_images; gw = (size_t)gi * a.g_w; gb = (size_t)gi * a.g_bn; }
+  if (a.g_images) {
+    int gi = ((m0 - srow0) / rpi) / a.g_images;
+    if (a.pyr.n) gi = min(gi, a.pyr.B / a.g_images - 1);      // a tile of a level's padding rows lies past the last group: it stores nothing, but must not read w / bias of a net that does not exist
+    gw = (size_t)gi * a.g_w; gb = (size_t)gi * a.g_bn;
+  }
   const float* wrow[NB]; bool wok[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
@@ -594,7 +598,11 @@ __global__ __launch_bounds__(256) void pw_gemm_skinny_kernel(PwArgs a) {
     }
   }
   size_t gw = 0, gb = 0;      // grouped frozen nets: the tile's parameter set
-  if (a.g_images) { const int gi = ((m0 - srow0) / rpi) / a.g_images; gw = (size_t)gi * a.g_w; gb = (size_t)gi * a.g_bn; }
+  if (a.g_images) {
+    int gi = ((m0 - srow0) / rpi) / a.g_images;
+    if (a.pyr.n) gi = min(gi, a.pyr.B / a.g_images - 1);      // (padding tiles of a level: see pw_gemm_body)
+    gw = (size_t)gi * a.g_w; gb = (size_t)gi * a.g_bn;
+  }
   const float* wrow[8]; bool wok[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {

@@ -8,7 +8,9 @@ The weight gradient - the grouped launch of pw_wgrad_grouped.hip and the per-lay
 BatchNorm-backward operand forms included - lives in wg_ref.py, which takes its X operand from pw_operand below.  The input gradient - the
 mmd_pwconv_bwd_data* entry points with their BatchNorm-backward operand forms, the slab kernel's <PRO 1> instantiations included - lives in
 bd_ref.py, whose plain launches are pw_fwd below with the sizes swapped.
-OUT OF SCOPE still (pw_fwd is the forward of every one of them): mmd_pwconv_fwd_pyr*, the grouped-nets mode (mmd_set_group), the stem
+The feature-pyramid launches mmd_pwconv_fwd_pyr(_bf16), with the grouped-nets mode (mmd_set_group) over a pyramid, live in pyr_ref.py, which
+calls pw_fwd and route (pyr=True) below.
+OUT OF SCOPE still (pw_fwd is the forward of every one of them): the grouped-nets mode (mmd_set_group) of mmd_pwconv_fwd, the stem
 im2col GEMM (mmd_pw_stem_gemm) and the stem weight gradient (both in mb_ref.py, which calls pw_fwd below), the forward slab family (form 4 of mmd_pwconv_fwd_form, pw_slab.hip: route
 names it where the auto form could take a launch, and no case may land there) and the MMD_STREAM dev kernel.
 
@@ -126,7 +128,7 @@ RW_AFF, RW_SWISH, RW_GATE = 1, 2, 4
 STATS_DEPTH = 128                                    # MMD_STATS_DEPTH (common.h)
 
 
-def _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on):
+def _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on, pyr=False):
     """pw_rows_try (pw_rows.hip:302-361); None: refused"""
     if K < 16 or K > 128 or K & 7:                                                    # :307
         return None
@@ -134,7 +136,7 @@ def _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on):
         return None
     if form != 1 and (M < 32768 or stats or N < 48):                                  # :314
         return None
-    if gate and rpi & 15:                                                             # :316
+    if gate and (pyr or rpi & 15):                                                    # :316 (a pyramid launch with a gate is refused)
         return None
     nkk, tiles, nslabs = K // 8, cdiv(N, 16), cdiv(M, 16)                             # :317-319
     C, best = 1, -1.0
@@ -165,9 +167,9 @@ def _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on):
             "nblk": npanels * bpp, "row_tail": M % 16, "col_tail": N % (C * 16), "slotted": slots_on}
 
 
-def _longk(form, bf16, M, K, N, xf, gate, rpi, slots_on, remap):
+def _longk(form, bf16, M, K, N, xf, gate, rpi, slots_on, remap, pyr=False):
     """pw_longk_try (pw_longk.hip:216-239); None: refused"""
-    if form in (2, 1, 4) or bf16 or remap:                                            # :218
+    if form in (2, 1, 4) or bf16 or remap or pyr:                                     # :218
         return None
     if xf or slots_on:                                                                # :219-220
         return None
@@ -183,10 +185,12 @@ def _longk(form, bf16, M, K, N, xf, gate, rpi, slots_on, remap):
             "slotted": False}
 
 
-def route(form, native, bf16, M, K, N, pro="plain", gate=False, stats=False, ws_slots=0, remap=False, residual=False, rpi=0, split_default=True):
+def route(form, native, bf16, M, K, N, pro="plain", gate=False, stats=False, ws_slots=0, remap=False, residual=False, rpi=0, split_default=True,
+          pyr=False):
     """Which kernel instantiation and geometry a forward call reaches: a COPY of the host decisions of pw_fwd_impl / pw_dispatch
     (pw_gemm.hip), pw_rows_try (pw_rows.hip) and pw_longk_try (pw_longk.hip), with no MMD_* variable set (split_default False: MMD_MFMA_F32).
-    Nothing checks the copy against the host code: keep it in step by hand when the dispatch changes.  `residual` changes no decision."""
+    Nothing checks the copy against the host code: keep it in step by hand when the dispatch changes.  `residual` changes no decision.
+    pyr: a pyramid launch (pyr_ref.py, M = row0[n]) - pw_rows_try then refuses a gate, pw_longk_try and pw_slab_try the launch."""
     aff, act = PRO_KINDS[pro]
     xf = aff is not None or act != 0
     ntm = cdiv(M, 128)
@@ -196,10 +200,10 @@ def route(form, native, bf16, M, K, N, pro="plain", gate=False, stats=False, ws_
     gain = 20 if bf16 else 10                                                         # :1172
     pad64, pad32 = cdiv(N, 64) * 64, cdiv(N, 32) * 32
     variant = 0 if take_skinny else (1 if (N <= 32 or ((pad64 - pad32) * 100 > gain * N and not big < 800)) else (2 if big < 800 else 3))   # :1174-1176
-    if form == 0 and not bf16 and not remap and not slots_on and take_skinny and N > 64 and K >= 256 and xf and N > 224:      # :1197, pw_slab_try
+    if form == 0 and not bf16 and not remap and not pyr and not slots_on and take_skinny and N > 64 and K >= 256 and xf and N > 224:      # :1197, pw_slab_try
         return {"family": "slab", "big_tiles": big}                                   # out of scope: whether it takes the launch is slab_plan's
-    r = None if bf16 else _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on)                                         # :1204
-    r = r or _longk(form, bf16, M, K, N, xf, gate, rpi, slots_on, remap)                                                      # :1206
+    r = None if bf16 else _rows(form, M, K, N, aff, act, gate, rpi, stats, slots_on, pyr)                                    # :1204
+    r = r or _longk(form, bf16, M, K, N, xf, gate, rpi, slots_on, remap, pyr)                                                 # :1206
     if r:
         r["big_tiles"] = big
         return r
