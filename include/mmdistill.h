@@ -264,6 +264,26 @@ int mmd_at_loss_multi(const float* const* a_s, const float* const* a_t, float* c
 // sticky: set to 1 when the batch has a box, never cleared - the caller zeroes it once.
 int mmd_focal_loss(const float* cls, const float* reg, const float* anchors, const float* boxes, const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws, double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale, int to_logit, int* any_boxes, hipStream_t stream);
 
+// mmd_focal_loss with a selectable box regression criterion (an extension: the reference has smooth-L1 only).  Same launches, arguments,
+// workspaces (need no zeroing), clamped box counts and sticky any_boxes as mmd_focal_loss; assignment, classification loss, dcls and the
+// empty-batch / empty-image rules are unchanged in every mode.  box_mode: 0 = smooth-L1, identical to mmd_focal_loss (box_weight must
+// be 1); 1 = GIoU (Rezatofighi et al. 2019); 2 = DIoU, 3 = CIoU (Zheng et al. 2020).  Another mode, a box_weight that is not finite or
+// not > 0, or box_weight != 1 with mode 0 -> MMD_EINVAL, nothing is launched.
+// Modes 1-3, per positive anchor (y1, x1, y2, x2) with size ah, aw and centre acy, acx, in fp32:
+//   prediction (BBoxTransform's decode, src/YetAnotherEfficientDet.py:26-45): pcy = r0*ah + acy, pcx = r1*aw + acx,
+//     ph = exp(min(r2, M))*ah, pw = exp(min(r3, M))*aw, M = log(1000/16); the gradient w.r.t. r2 / r3 is 0 where the clamp is active;
+//   target: the raw box's centre (gcx, gcy), gw = max(x2 - x1, 1), gh = max(y2 - y1, 1) (the clamp of the smooth-L1 targets);
+//   on the corner forms of both: I = product of the two intersection extents clamped at 0, U = pw*ph + gw*gh - I, IoU = I / (U + 1e-7),
+//     cw, ch = extents of the smallest enclosing box;
+//   GIoU: L = 1 - IoU + (cw*ch - U) / (cw*ch + 1e-7)
+//   DIoU: L = 1 - IoU + ((pcx - gcx)^2 + (pcy - gcy)^2) / (cw^2 + ch^2 + 1e-7)
+//   CIoU: DIoU's L + alpha*v, v = (4/pi^2) * (atan(gw/gh) - atan(pw/ph))^2, alpha = v / (1 - IoU + v + 1e-7), a constant in the gradient.
+// Image b contributes box_weight * sum_pos L / npos[b] (0 without boxes or without positive anchors); loss_out[0] is the mean over the
+// B images.  dreg = grad_scale * d loss_out[0] / d reg, analytic through the decode (exp, the min / max selections, atan), stored for
+// every element: zeros for negative, ignored and out-of-range anchors.  A batch without boxes: zero losses and gradients, any_boxes
+// untouched.
+int mmd_focal_loss_box(const float* cls, const float* reg, const float* anchors, const float* boxes, const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws, double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale, int to_logit, int* any_boxes, int box_mode, float box_weight, hipStream_t stream);
+
 // torch.optim.Adam step on a flat segment (src/optimization/train_methods.py:825-833, traditional.py:190).
 int mmd_adam_step(float* p, const float* g, float* m, float* v, float* state, const float* hyper, const int* active, float grad_scale, long long n, hipStream_t stream);
 

@@ -450,12 +450,73 @@ __global__ __launch_bounds__(256) void focal_assign_kernel(const float* __restri
 // float4s of the block's contiguous run of 256 x NC class probabilities (coalesced loads and stores; the per-anchor form touched 64
 // cache lines per wave instruction: 59 us for 2 x 31 MB on the critical path between forward and backward).  A thread's focal terms are
 // summed in fp32, the reduction across threads runs in fp64.
+// MODE: the regression criterion of pass 1.  0 = smooth-L1 on (dy, dx, dh, dw) (upstream's; what mmd_focal_loss launches); 1 GIoU, 2 DIoU,
+// 3 CIoU between the decoded prediction and the assigned box (box_iou_terms), weighted by box_w.  Everything else is common to the modes.
+
+// One positive anchor's IoU-family loss and its gradient w.r.t. the four regression outputs (fp32).  Prediction: BBoxTransform's decode of
+// r on the anchor (centre acx/acy, size aw/ah), exp's argument clamped at log(1000/16) with a zero gradient where the clamp is active;
+// target: centre gcx/gcy, size gw/gh (already clamped to a pixel).  The gradient goes through the corner selections (min / max: the
+// selected operand), the clamp of the intersection's extents at 0, exp and atan; CIoU's alpha is a constant.  g4 = d L / d r (unscaled).
+template <int MODE>
+__device__ __forceinline__ float box_iou_terms(const float* __restrict__ r, float ah, float aw, float acy, float acx, float gcy, float gcx,
+                                               float gh, float gw, float* g4) {
+  const float eps = 1e-7f;
+  const float M = 4.1351666f;                       // log(1000 / 16)
+  const float pcy = r[0] * ah + acy, pcx = r[1] * aw + acx;
+  const float ph = __expf(fminf(r[2], M)) * ah, pw = __expf(fminf(r[3], M)) * aw;
+  const float px1 = pcx - 0.5f * pw, px2 = pcx + 0.5f * pw, py1 = pcy - 0.5f * ph, py2 = pcy + 0.5f * ph;
+  const float gx1 = gcx - 0.5f * gw, gx2 = gcx + 0.5f * gw, gy1 = gcy - 0.5f * gh, gy2 = gcy + 0.5f * gh;
+  const float iwr = fminf(px2, gx2) - fmaxf(px1, gx1), ihr = fminf(py2, gy2) - fmaxf(py1, gy1);
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float I = iw * ih;
+  const float U = pw * ph + gw * gh - I;
+  const float S = U + eps;
+  const float iou = I / S;
+  const float cw = fmaxf(px2, gx2) - fminf(px1, gx1), ch = fmaxf(py2, gy2) - fminf(py1, gy1);
+  // L = 1 - IoU + penalty.  d IoU / d I = (S + I) / S^2, d IoU / d (pw ph) = -I / S^2
+  float L = 1.f - iou;
+  float dI = -(S + I) / (S * S), dAp = I / (S * S);       // d L / d I, d L / d (pw ph)
+  float dcw, dch, dpcx = 0.f, dpcy = 0.f, dpw = 0.f, dph = 0.f;      // d L / d (enclosing extents), direct terms of centre and size
+  if (MODE == 1) {
+    const float C = cw * ch, Ce = C + eps;
+    L += (C - U) / Ce;
+    dI += 1.f / Ce; dAp -= 1.f / Ce;                      // through -U
+    const float dC = S / (Ce * Ce);
+    dcw = dC * ch; dch = dC * cw;
+  } else {
+    const float dx = pcx - gcx, dy = pcy - gcy;
+    const float rho = dx * dx + dy * dy, D = cw * cw + ch * ch + eps;
+    L += rho / D;
+    dpcx = 2.f * dx / D; dpcy = 2.f * dy / D;
+    const float dD = -rho / (D * D);
+    dcw = dD * 2.f * cw; dch = dD * 2.f * ch;
+    if (MODE == 3) {
+      const float k = 0.40528473f;                        // 4 / pi^2
+      const float da = atanf(gw / gh) - atanf(pw / ph);
+      const float v = k * da * da;
+      const float al = v / (1.f - iou + v + eps);
+      L += al * v;
+      const float dat = -2.f * k * da * al / (pw * pw + ph * ph);      // alpha * d v / d atan(pw / ph), over pw^2 + ph^2
+      dpw = dat * ph; dph = -dat * pw;
+    }
+  }
+  const float diw = iwr > 0.f ? dI * ih : 0.f, dih = ihr > 0.f ? dI * iw : 0.f;
+  const float gx2c = (px2 < gx2 ? diw : 0.f) + (px2 > gx2 ? dcw : 0.f), gx1c = -(px1 > gx1 ? diw : 0.f) - (px1 < gx1 ? dcw : 0.f);
+  const float gy2c = (py2 < gy2 ? dih : 0.f) + (py2 > gy2 ? dch : 0.f), gy1c = -(py1 > gy1 ? dih : 0.f) - (py1 < gy1 ? dch : 0.f);
+  dpcx += gx1c + gx2c; dpcy += gy1c + gy2c;
+  dpw += 0.5f * (gx2c - gx1c) + dAp * ph; dph += 0.5f * (gy2c - gy1c) + dAp * pw;
+  g4[0] = dpcy * ah; g4[1] = dpcx * aw;
+  g4[2] = r[2] <= M ? dph * ph : 0.f; g4[3] = r[3] <= M ? dpw * pw : 0.f;
+  return L;
+}
+
+template <int MODE>
 __global__ __launch_bounds__(256) void focal_loss_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
                                                          const float* __restrict__ anchors, const float* __restrict__ boxes,
                                                          const int* __restrict__ nbox, const int* __restrict__ assign,
                                                          const int* __restrict__ npos, int maxg, int A, int NC, int B,
                                                          double* acc, float* __restrict__ dcls, float* __restrict__ dreg,
-                                                         float gscale, int to_logit) {
+                                                         float gscale, int to_logit, float box_w) {
   __shared__ double sd[8];
   __shared__ short s_as[256], s_lab[256];       // per anchor: -2 negative / -1 ignore / 0 positive; label of a positive
   const int b = blockIdx.y, tid = threadIdx.x;
@@ -486,18 +547,27 @@ __global__ __launch_bounds__(256) void focal_loss_kernel(const float* __restrict
           float gw = bx[2] - bx[0], gh = bx[3] - bx[1];
           float gcx = bx[0] + 0.5f * gw, gcy = bx[1] + 0.5f * gh;
           gw = fmaxf(gw, 1.f); gh = fmaxf(gh, 1.f);
-          float t[4] = {(gcy - acy) / ah, (gcx - acx) / aw, __logf(gh / ah), __logf(gw / aw)};
           const float* r = reg + ((size_t)b * A + a) * 4;
-          const float gr = gscale / (float)B / (4.f * (float)np);
+          if (MODE == 0) {
+            float t[4] = {(gcy - acy) / ah, (gcx - acx) / aw, __logf(gh / ah), __logf(gw / aw)};
+            const float gr = gscale / (float)B / (4.f * (float)np);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            float diff = r[k] - t[k];
-            float ad = fabsf(diff);
-            float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-            if (ad <= 1.f / 9.f) { lr += 4.5 * (double)ad * ad; g4[k] = 9.f * ad * sgn * gr; }
-            else { lr += (double)ad - 0.5 / 9.0; g4[k] = sgn * gr; }
+            for (int k = 0; k < 4; ++k) {
+              float diff = r[k] - t[k];
+              float ad = fabsf(diff);
+              float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
+              if (ad <= 1.f / 9.f) { lr += 4.5 * (double)ad * ad; g4[k] = 9.f * ad * sgn * gr; }
+              else { lr += (double)ad - 0.5 / 9.0; g4[k] = sgn * gr; }
+            }
+            lr /= (4.0 * (double)np);
+          } else {      // image b's term: box_w * sum over its positives / npos
+            const float rv[4] = {r[0], r[1], r[2], r[3]};
+            const float L = box_iou_terms<MODE>(rv, ah, aw, acy, acx, gcy, gcx, gh, gw, g4);
+            const float gr = gscale * box_w / (float)B / (float)np;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g4[k] *= gr;
+            lr = (double)L * (double)box_w / (double)np;
           }
-          lr /= (4.0 * (double)np);
         }
       }
       if (dr) { dr[0] = g4[0]; dr[1] = g4[1]; dr[2] = g4[2]; dr[3] = g4[3]; }
@@ -578,17 +648,44 @@ __global__ void focal_zero_kernel(int* npos, double* acc, int B) {
 }
 // cls [B,A,NC] post-sigmoid probabilities, reg [B,A,4], anchors [A,4] (y1,x1,y2,x2).
 // workspace: assign int[B*A], npos int[B] (zeroed here), acc double[2B] (zeroed here).
+// box_mode / box_w: focal_loss_kernel's MODE and weight (0 / 1 = mmd_focal_loss)
+static int focal_loss_launch(const float* cls, const float* reg, const float* anchors, const float* boxes, const int* nbox, int maxg,
+                             int B, int A, int NC, int* assign_ws, int* npos_ws, double* acc_ws, float* loss_out, float* dcls,
+                             float* dreg, float grad_scale, int to_logit, int* any_boxes, int box_mode, float box_w,
+                             hipStream_t stream) {
+  if (!cls || !reg || !anchors || !boxes || !nbox || !assign_ws || !npos_ws || !acc_ws || !loss_out) return MMD_EINVAL;
+  if (B <= 0 || A <= 0 || NC <= 0 || maxg <= 0) return MMD_EINVAL;
+  if (box_mode < 0 || box_mode > 3 || !(box_w > 0.f) || !(box_w <= 3.4028235e38f) /* NaN, inf */ ||(box_mode == 0 && box_w != 1.f)) return MMD_EINVAL;
+  hipLaunchKernelGGL(focal_zero_kernel, dim3(1), dim3(256), 0, stream, npos_ws, acc_ws, B);      // (one launch: both sit on the critical path)
+  dim3 grid(cdiv(A, 256), B);
+  hipLaunchKernelGGL(focal_assign_kernel, grid, dim3(256), 0, stream, anchors, boxes, nbox, maxg, A, assign_ws, npos_ws);
+#define MMD_FOCAL_LAUNCH(MODE)                                                                                                       \
+  hipLaunchKernelGGL(focal_loss_kernel<MODE>, grid, dim3(256), 0, stream, cls, reg, anchors, boxes, nbox, assign_ws, npos_ws, maxg, \
+                     A, NC, B, acc_ws, dcls, dreg, grad_scale, to_logit, box_w)
+  switch (box_mode) {
+    case 0: MMD_FOCAL_LAUNCH(0); break;
+    case 1: MMD_FOCAL_LAUNCH(1); break;
+    case 2: MMD_FOCAL_LAUNCH(2); break;
+    default: MMD_FOCAL_LAUNCH(3); break;
+  }
+#undef MMD_FOCAL_LAUNCH
+  hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(64), 0, stream, acc_ws, nbox, maxg, B, loss_out, any_boxes);
+  return mmd_check_launch();
+}
+
 extern "C" int mmd_focal_loss(const float* cls, const float* reg, const float* anchors, const float* boxes,
                               const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws,
                               double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale,
                               int to_logit, int* any_boxes, hipStream_t stream) {
-  if (!cls || !reg || !anchors || !boxes || !nbox || !assign_ws || !npos_ws || !acc_ws || !loss_out) return MMD_EINVAL;
-  if (B <= 0 || A <= 0 || NC <= 0 || maxg <= 0) return MMD_EINVAL;
-  hipLaunchKernelGGL(focal_zero_kernel, dim3(1), dim3(256), 0, stream, npos_ws, acc_ws, B);      // (one launch: both sit on the critical path)
-  dim3 grid(cdiv(A, 256), B);
-  hipLaunchKernelGGL(focal_assign_kernel, grid, dim3(256), 0, stream, anchors, boxes, nbox, maxg, A, assign_ws, npos_ws);
-  hipLaunchKernelGGL(focal_loss_kernel, grid, dim3(256), 0, stream, cls, reg, anchors, boxes, nbox, assign_ws, npos_ws, maxg,
-                     A, NC, B, acc_ws, dcls, dreg, grad_scale, to_logit);
-  hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(64), 0, stream, acc_ws, nbox, maxg, B, loss_out, any_boxes);
-  return mmd_check_launch();
+  return focal_loss_launch(cls, reg, anchors, boxes, nbox, maxg, B, A, NC, assign_ws, npos_ws, acc_ws, loss_out, dcls, dreg, grad_scale,
+                           to_logit, any_boxes, 0, 1.f, stream);
+}
+
+// mmd_focal_loss with the regression criterion chosen by box_mode (0 smooth-L1, 1 GIoU, 2 DIoU, 3 CIoU) and weighted by box_weight
+extern "C" int mmd_focal_loss_box(const float* cls, const float* reg, const float* anchors, const float* boxes,
+                                  const int* nbox, int maxg, int B, int A, int NC, int* assign_ws, int* npos_ws,
+                                  double* acc_ws, float* loss_out, float* dcls, float* dreg, float grad_scale,
+                                  int to_logit, int* any_boxes, int box_mode, float box_weight, hipStream_t stream) {
+  return focal_loss_launch(cls, reg, anchors, boxes, nbox, maxg, B, A, NC, assign_ws, npos_ws, acc_ws, loss_out, dcls, dreg, grad_scale,
+                           to_logit, any_boxes, box_mode, box_weight, stream);
 }

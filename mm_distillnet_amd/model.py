@@ -27,7 +27,7 @@ from . import _lib
 from .arch import make_spec
 from .engine import Net, Feat
 from .layout import state_layout
-from .step import KD_LOSSES
+from .step import BOX_LOSSES, KD_LOSSES, check_box_loss
 
 call = _lib.call
 
@@ -304,7 +304,7 @@ class AttentionLoss(nn.Module):
 
 class _FocalFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, cls, reg, anchors, boxes, nbox, maxg):
+    def forward(ctx, cls, reg, anchors, boxes, nbox, maxg, box_loss="smooth_l1", box_weight=1.0):
         B, A, NC = cls.shape
         dev = cls.device
         assign = torch.empty(B * A, dtype=torch.int32, device=dev)
@@ -312,18 +312,30 @@ class _FocalFn(torch.autograd.Function):
         acc = torch.empty(2 * B, dtype=torch.float64, device=dev)
         out = torch.zeros(2, device=dev)
         dcls = torch.empty_like(cls); dreg = torch.empty_like(reg)
-        call("mmd_focal_loss", cls.contiguous(), reg.contiguous(), anchors, boxes, nbox, maxg, B, A, NC, assign, npos, acc,
-             out, dcls, dreg, 1.0, 0, None)
+        if box_loss == "smooth_l1":
+            call("mmd_focal_loss", cls.contiguous(), reg.contiguous(), anchors, boxes, nbox, maxg, B, A, NC, assign, npos, acc,
+                 out, dcls, dreg, 1.0, 0, None)
+        else:
+            call("mmd_focal_loss_box", cls.contiguous(), reg.contiguous(), anchors, boxes, nbox, maxg, B, A, NC, assign, npos, acc,
+                 out, dcls, dreg, 1.0, 0, None, BOX_LOSSES[box_loss], float(box_weight))
         ctx.save_for_backward(dcls, dreg)
         return out[0:1].clone(), out[1:2].clone()
 
     @staticmethod
     def backward(ctx, g_reg, g_cls):
         dcls, dreg = ctx.saved_tensors
-        return dcls * g_cls, dreg * g_reg, None, None, None, None
+        return dcls * g_cls, dreg * g_reg, None, None, None, None, None, None
 
 
 class YetAnotherFocalLoss(nn.Module):
+    """src/loss/YetAnotherFocalLoss.py:27-190.  box_loss / box_weight (an extension, StepConfig's keys of the same names): the box
+    regression criterion, upstream's smooth-L1 by default or giou | diou | ciou with a weight."""
+
+    def __init__(self, box_loss="smooth_l1", box_weight=1.0):
+        super().__init__()
+        check_box_loss(box_loss, box_weight)
+        self.box_loss, self.box_weight = box_loss, float(box_weight)
+
     def forward(self, prediction, annotations, **kwargs):
         classifications, regressions, anchors = prediction
         dev = classifications.device
@@ -336,7 +348,8 @@ class YetAnotherFocalLoss(nn.Module):
                 a = np.asarray(a, dtype=np.float32).reshape(-1, 5)
                 boxes[i, :a.shape[0]] = torch.from_numpy(a)
                 nbox[i] = a.shape[0]
-        return _FocalFn.apply(classifications, regressions, anchors[0].contiguous(), boxes.to(dev), nbox.to(dev), maxg)
+        return _FocalFn.apply(classifications, regressions, anchors[0].contiguous(), boxes.to(dev), nbox.to(dev), maxg,
+                              self.box_loss, self.box_weight)
 
 
 # ---------------------------------------------------------------------------------------- factories
@@ -404,11 +417,15 @@ def loss_names_from_config(config, kd_default: str = "None") -> str:
 
 def extract_criterions_from_config(config):
     """(criterion_main, criterion_div, criterion_kd) for the supported criteria (src/utils/utils.py:1556-1668).  AttentionLoss is built
-    with its default p = 2 as upstream: the cfg's `p` / `T` belong to MTALoss."""
+    with its default p = 2 as upstream: the cfg's `p` / `T` belong to MTALoss.  The extension keys `box_loss` / `box_loss_weight` (absent:
+    smooth_l1 / 1) set the main criterion's box regression loss."""
     kd = loss_names_from_config(config)
+    box_loss = config.get('box_loss', 'smooth_l1')
+    box_weight = float(config.get('box_loss_weight', 1.0))
+    check_box_loss(box_loss, box_weight)
     crit = None
     if kd == 'MTALoss':
         crit = MTALoss(T=config['T'], p=config['p'])
     elif kd == 'AttentionLoss':
         crit = AttentionLoss()
-    return YetAnotherFocalLoss(), None, crit
+    return YetAnotherFocalLoss(box_loss=box_loss, box_weight=box_weight), None, crit

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 import numbers
 import os
 
@@ -31,6 +32,17 @@ call = _lib.call
 TEACHER_ORDER = ("rgb", "depth", "thermal")     # ModuleDict insertion order in train.py:123-135
 OPT_MODES = {"Adam": 0, "AdamW": 1, "SGD": 2}
 KD_LOSSES = ("MTALoss", "AttentionLoss", "None")
+BOX_LOSSES = {"smooth_l1": 0, "giou": 1, "diou": 2, "ciou": 3}      # cfg `box_loss` -> box_mode of mmd_focal_loss_box
+
+
+def check_box_loss(name, weight) -> None:
+    """The box regression criterion's two settings, checked on the host (StepConfig, trainer.box_loss_settings, the model.py facade)"""
+    if not isinstance(name, str) or name not in BOX_LOSSES:
+        raise ValueError(f"box_loss {name!r}: one of {' | '.join(BOX_LOSSES)}")
+    if isinstance(weight, bool) or not isinstance(weight, numbers.Real) or not math.isfinite(weight) or not weight > 0:
+        raise ValueError(f"box_weight {weight!r}: a finite weight > 0")
+    if name == "smooth_l1" and weight != 1:
+        raise ValueError(f"box_weight {weight!r} with box_loss smooth_l1: upstream's criterion has no weight (1 only)")
 
 
 @dataclass
@@ -70,8 +82,13 @@ class StepConfig:
                                        # NMS over their concatenation; "wbf": weighted box fusion (csrc/postproc.hip pp_wbf_kernel) at the
                                        # same merge_iou / inclusive_nms - overlapping boxes of one label are averaged, weights = scores
     label_merge_votes: int = 1         # wbf: a fused box needs members from at least this many distinct sources (1 .. number of sources)
+    box_loss: str = "smooth_l1"        # extension key: the box regression criterion.  "smooth_l1": upstream's, on (dy, dx, dh, dw); "giou" |
+                                       # "diou" | "ciou": an IoU-family loss between the decoded prediction and the pseudo-label, computed per
+                                       # positive anchor inside the focal launch (csrc/loss.hip mmd_focal_loss_box)
+    box_weight: float = 1.0            # giou / diou / ciou: weight of the regression loss and its gradient (smooth_l1: 1 only)
 
     def __post_init__(self):
+        check_box_loss(self.box_loss, self.box_weight)
         if self.label_merge not in LABEL_MERGES:
             raise ValueError(f"label_merge {self.label_merge!r}: one of {' | '.join(LABEL_MERGES)}")
         v = self.label_merge_votes
@@ -524,8 +541,13 @@ class DistillEngine:
         assign = self.ws.alloc((B * A,), torch.int32); npos = self.ws.alloc((B,), torch.int32)
         acc = self.ws.alloc((2 * B,), torch.float64); main = self.ws.alloc((2,))
         dcls = st._alloc(B, A, nc); dreg = st._alloc(B, A, 4)
-        call("mmd_focal_loss", cls_s, reg_s, st.anchors(S), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
-             float(cfg.w_main), 1, self.head_active if train else self.ws.alloc((1,), torch.int32))
+        any_boxes = self.head_active if train else self.ws.alloc((1,), torch.int32)
+        if cfg.box_loss == "smooth_l1":
+            call("mmd_focal_loss", cls_s, reg_s, st.anchors(S), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
+                 float(cfg.w_main), 1, any_boxes)
+        else:      # the same launches with an IoU-family criterion in the regression slot
+            call("mmd_focal_loss_box", cls_s, reg_s, st.anchors(S), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
+                 float(cfg.w_main), 1, any_boxes, BOX_LOSSES[cfg.box_loss], float(cfg.box_weight))
         # backward + optimizer
         if train and not _lib.dev_switch("MMD_DEV_NO_BWD"):      # (MMD_DEV_NO_BWD=1: timing experiment - forward + losses only)
             call("mmd_memset_async", st.ps.grad, 0, st.ps.grad.numel() * 4)

@@ -66,6 +66,16 @@ def label_merge_settings(cfg) -> Dict:
     return {"label_merge": name, "label_merge_votes": cfg.getint("label_merge_votes", 1)}
 
 
+def box_loss_settings(cfg) -> Dict:
+    """cfg -> StepConfig keyword arguments of the box regression criterion (extension keys, absent from the reference's cfg files ->
+    upstream's smooth-L1): box_loss (smooth_l1 | giou | diou | ciou) and box_loss_weight (the IoU-family loss' weight, default 1).  Host
+    work only: an unknown name or a bad weight raises here, before any device work (StepConfig repeats the checks for direct users)."""
+    from .step import check_box_loss
+    name, weight = cfg.get("box_loss", "smooth_l1"), cfg.getfloat("box_loss_weight", 1.0)
+    check_box_loss(name, weight)
+    return {"box_loss": name, "box_weight": weight}
+
+
 def ema_validate_setting(cfg) -> bool:
     """cfg ema_validate (default False): validate(), and with it best-checkpoint selection and early stopping, on the averaged weights"""
     on = bool(cfg.getboolean("ema_validate", False))

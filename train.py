@@ -15,6 +15,8 @@ Extension keys `ema_decay` / `ema_warmup` / `ema_validate` (absent -> off): an e
 the device, saved as two more checkpoint keys (`state_dict_ema`, `ema_updates`) and as only_parameters_student_best_ema.<rank>.
 Extension keys `label_merge` (nms | wbf, absent -> nms: upstream's NMS) / `label_merge_votes` (absent -> 1): the teachers' boxes become the
 pseudo-labels by weighted box fusion on the device instead of the NMS.
+Extension keys `box_loss` (smooth_l1 | giou | diou | ciou, absent -> smooth_l1: upstream's criterion) / `box_loss_weight` (absent -> 1): the
+student's boxes are regressed with an IoU-family loss between the decoded prediction and the pseudo-label, inside the focal launch.
 """
 import argparse
 import configparser
@@ -103,7 +105,8 @@ def step_config(cfg) -> StepConfig:
                       augment=bool(cfg.getboolean("audio_augmentation_merge", False)) and method == "traditional_nms_augmented",
                       # extension key (absent from the reference's cfg files -> fp32): "bf16" = 1x1 convs on the bf16 MFMA
                       precision=cfg.get("precision", "fp32"), seed=cfg.getint("seed", 24),
-                      **TR.optimizer_settings(cfg), **TR.ema_settings(cfg), **TR.label_merge_settings(cfg))
+                      **TR.optimizer_settings(cfg), **TR.ema_settings(cfg), **TR.label_merge_settings(cfg),
+                      **TR.box_loss_settings(cfg))
 
 
 def augment_from_config(cfg, raw: bool, rank: int = 0):
