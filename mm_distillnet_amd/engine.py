@@ -17,13 +17,14 @@ import contextlib
 import ctypes
 import os
 import threading
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib
 from .arch import NetSpec, BN_EPS, BN_MOMENTUM, pyramid_sizes
+from .pyramid import Pyramid
 from .store import ParamStore, Arena
 
 NONE, SWISH, SIGMOID = 0, 1, 2
@@ -71,6 +72,11 @@ WG_ROWS = 4096        # rows per item: 4096 x (64x64 tile) measured best (1.33 m
 WG_BLOCKS = 4096
 
 
+class Live(NamedTuple):
+    """A train-mode BatchNorm whose coefficients forward consumers derive on the fly from the batch sums, in the order they take them (`*live`)."""
+    stats: torch.Tensor; gamma: torch.Tensor; beta: torch.Tensor; count: int       # (stats: [2C] double raw sums)
+
+
 @dataclass
 class Feat:
     """rows [B*H*W, C] plus the pending per-channel transform consumers must apply."""
@@ -82,7 +88,7 @@ class Feat:
     scale: Optional[torch.Tensor] = None
     shift: Optional[torch.Tensor] = None
     act: int = NONE
-    bn: Optional[tuple] = None     # train-mode forward: (stats[2C] double, gamma, beta, count) -> coefficients derived on the fly
+    bn: Optional[Live] = None      # train-mode forward: the BatchNorm is still live (scale / shift are filled at the end of the forward)
 
     @property
     def M(self) -> int:
@@ -150,6 +156,59 @@ class LazyDz:
     BatchNorm evaluate dz = BnBwd(g, z) in their operand prologues (mmd_pwconv_bwd_data_bn / _weight_bn)."""
     g: torch.Tensor; z: torch.Tensor; aff: Aff; sums: torch.Tensor
     act: int; mul_b: Optional[torch.Tensor]; rpi: int; bn_name: str; count: int
+
+
+# ---- the tape: what the train forward hands to the backward, one record type per stage (every field has a reader in the backward)
+class StemRec(NamedTuple):
+    """Tape.stem: the NCHW image, the stem output (BatchNorm-0 + swish pending on it) and that BatchNorm's finalized statistics."""
+    x: torch.Tensor; out: Feat; mean: torch.Tensor; invstd: torch.Tensor
+
+
+class BlockRec(NamedTuple):
+    """Tape.blocks[idx]: one MBConv block.  f0 = the depthwise conv's input: the expand conv's output, or `inp` itself (bn0 None) without one."""
+    inp: Feat; out: Feat; f0: Feat; bn0: Optional[Aff]; f1: Feat; bn1: Aff
+    pooled: torch.Tensor; hpre: torch.Tensor; gate: torch.Tensor                # squeeze-excite: pooled mean, hidden pre-activation, gate
+    z2: torch.Tensor; bn2: Aff; rs: Optional[torch.Tensor]                      # project conv's raw output; rs: drop-connect scale per image
+
+
+class DownRec(NamedTuple):
+    """Tape.down[name]: a down-channel conv of the first BiFPN cell; out = BN(z), materialised or (lazy) pending on z."""
+    x: Feat; out: Feat; z: torch.Tensor; bn: Aff
+
+
+class FirstCellRec(NamedTuple):
+    """Tape.first: the p5 -> p6 conv's output and its two max-pooled descendants (the first cell's p6 / p7 inputs)."""
+    c6: Feat; p6_in: Feat; p7_in: Feat
+
+
+class NodeRec(NamedTuple):
+    """Tape.nodes[cell][i]: a BiFPN node: its operands (None: absent), parameter names, depthwise output zd, raw 1x1 output z, BatchNorm."""
+    in0: Feat; in1: Optional[Feat]; up: Optional[Feat]; pl: Optional[Feat]; theta: str; conv: str
+    zd: Feat; z: Optional[torch.Tensor]; bn: Optional[Aff]; out: Feat           # (z, bn: None in an eval forward, whose tape nobody reads)
+
+
+class HeadLayerRec(NamedTuple):
+    """One conv_list layer of a head over the pyramid: input rows x, depthwise output zd, raw 1x1 output z; x_off / off = where the
+    BatchNorms of x's producer (None: the BiFPN) / of z start in the contiguous BatchNorm arrays."""
+    x: torch.Tensor; x_off: Optional[int]; zd: torch.Tensor; z: torch.Tensor; off: int
+
+
+class HeadRec(NamedTuple):
+    """Tape.heads[name]: the layers, the header's input hx (BatchNorms at hx_off) and depthwise output hzd, each level's offset in the output."""
+    layers: List[HeadLayerRec]; hx: torch.Tensor; hx_off: int; hzd: torch.Tensor; yoff: List[int]; lev_stride: int
+
+
+@dataclass
+class Tape:
+    """Everything the backward reads from the train forward.  begin_step() starts a fresh one; an eval forward fills a throw-away one."""
+    stem: Optional[StemRec] = None
+    blocks: Dict[int, BlockRec] = field(default_factory=dict)
+    down: Dict[str, DownRec] = field(default_factory=dict)
+    first: Optional[FirstCellRec] = None
+    nodes: List[List[NodeRec]] = field(default_factory=list)       # one list per BiFPN cell, in forward order
+    heads: Dict[str, HeadRec] = field(default_factory=dict)
+    feats: Optional[List[Feat]] = None                             # the five BiFPN outputs
+    A: int = 0                                                     # anchors per image
 
 
 # MBConv expand convs with a thin input at high resolution (round 4): BatchNorm-0 backward, input gradient and weight gradient in one pass over
@@ -226,7 +285,7 @@ class Net:
                 tiles += ((R + 31) // 32) * ((C + 31) // 32)
             self.wt_desc = torch.tensor(descs, dtype=torch.int64, device=device)
             self.wt_tiles = tiles
-        self.tape: Dict[str, object] = {}
+        self.tape = Tape()
         self._slab_floats: Dict[tuple, int] = {}
         self._wg_read_done = None
         self._anchors: Dict[int, torch.Tensor] = {}
@@ -313,7 +372,7 @@ class Net:
             call("mmd_memset_async", c, 0, c.numel())
         if self.trainable:
             call("mmd_memset_async", self.stats_flat, 0, self.stats_flat.numel() * 8)
-        self.tape = {}
+        self.tape = Tape()
 
     def _bn_stats(self, name: str, train: bool):
         """Raw-sum accumulator [2C] (double) of BN `name` for this step (train) or None (eval)."""
@@ -324,21 +383,21 @@ class Net:
         return self.stats_flat[2 * o:2 * o + 2 * c]
 
     def _bn_aff(self, name: str, train: bool, stats, count: int):
-        """-> (Aff, live).  eval: folded running stats.  train: views that the batched finalize
-        at the end of the forward fills (the backward reads them) + the `live` tuple forward consumers use."""
+        """-> (Aff, Live or None).  eval: folded running stats.  train: views that the batched finalize
+        at the end of the forward fills (the backward reads them) + the Live record forward consumers use."""
         b = self.ps.bn(name)
         if not train:
             return Aff(b["fscale"], b["fshift"], None, None), None
         o, c = b["off"], b["C"]
         self.bn_count_host[o:o + c] = float(count)
         return (Aff(self.t_scale[o:o + c], self.t_shift[o:o + c], self.t_mean[o:o + c], self.t_invstd[o:o + c]),
-                (stats, b["gamma"], b["beta"], int(count)))
+                Live(stats, b["gamma"], b["beta"], int(count)))
 
     @staticmethod
     def _xf(x: Feat):
         """prologue arguments (scale, shift, act, stats, gamma, beta, count) of a forward consumer of x"""
         if x.bn is not None:
-            return (None, None, x.act, x.bn[0], x.bn[1], x.bn[2], x.bn[3])
+            return (None, None, x.act, *x.bn)
         return (x.scale, x.shift, x.act, None, None, None, 0)
 
     STATS_SLOTS = 64
@@ -447,126 +506,144 @@ class Net:
         return self._forward(x, train, drop_scale, raw_logits, None)
 
     def _forward(self, x, train, drop_scale, raw_logits, pack):
-        spec, ps = self.spec, self.ps
-        if pack is not None:
-            B, S = x[0].shape[0] * len(pack), x[0].shape[2]
-        else:
-            B, Cin, S, _ = x.shape
-        tape = self.tape if train else {}
+        tape = self.tape if train else Tape()
         self._counting = train
         if train:
             self._uses, self._bnout, self._linear = {}, {}, set()
-        P = "backbone_net.model"
-        # ---- stem: im2col + GEMM
-        OH = (S + 1) // 2
-        # direct 3x3/s2 stem conv (NCHW image -> NHWC rows); the im2col matrix is only built in the backward, for the
-        # weight gradient, on the wgrad stream
-        st = self._bn_stats(f"{P}._bn0", train)
-        (sc, sh, mu, istd), live = self._bn_aff(f"{P}._bn0", train, st, B * OH * OH)
-        z = self._alloc(B * OH * OH, spec.stem_out)
-        wstem = ps.w(f"{P}._conv_stem.conv.weight")
+        stem = self._forward_stem(x, train, pack, tape)
+        taps = self._forward_blocks(stem, train, drop_scale, tape)
+        feats = self._bifpn(taps, train, tape)
+        cls, reg = self._forward_heads(feats, train, raw_logits, tape)
         if train:
-            call("mmd_stem_conv_fwd", x, wstem, z, B, Cin, S, S, ps.stem_kp, spec.stem_out, None, None, NONE, st,
-                 *self._stats_ws(st, B * OH * OH, spec.stem_out))
-            cur = Feat(z, B, OH, OH, spec.stem_out, sc, sh, SWISH, live)
-            tape["stem"] = (x, cur, mu, istd)
-        elif pack is not None:
+            self._counting = False
+            self._finalize_bn((stem.B, x.shape[2]))
+        return cls, reg, feats
+
+    def _forward_stem(self, x, train: bool, pack, tape: Tape) -> Feat:
+        """Direct 3x3/s2 stem conv (NCHW image -> NHWC rows); the im2col matrix is only built in the backward, for the weight gradient, on
+        the wgrad stream.  x: the image batch; in a pack forward one batch per net."""
+        spec, ps, P = self.spec, self.ps, "backbone_net.model"
+        B, S = (x[0].shape[0] * len(pack), x[0].shape[2]) if pack is not None else (x.shape[0], x.shape[2])
+        OH = (S + 1) // 2
+        z = self._alloc(B * OH * OH, spec.stem_out)
+        if pack is not None:
             # the stems differ (input channels): one launch per net, each writing its images' rows of the shared stem output
             Bg, rows = x[0].shape[0], x[0].shape[0] * OH * OH
             for gi, (net, xg) in enumerate(zip(pack, x)):
                 b0 = net.ps.bn(f"{P}._bn0")
                 call("mmd_stem_conv_fwd", xg, net.ps.w(f"{P}._conv_stem.conv.weight"), z[gi * rows:(gi + 1) * rows], Bg, xg.shape[1], S, S,
                      net.ps.stem_kp, spec.stem_out, b0["fscale"], b0["fshift"], SWISH, None, None, 0)
-            cur = Feat(z, B, OH, OH, spec.stem_out)
-        else:
-            # frozen net: the folded BN + swish ride in the producer's epilogue (once per element) instead of the depthwise
-            # prologue, which would redo them for every halo pixel (1.6x for 3x3, 2.25x for 5x5 tiles)
-            call("mmd_stem_conv_fwd", x, wstem, z, B, Cin, S, S, ps.stem_kp, spec.stem_out, sc, sh, SWISH, None, None, 0)
-            cur = Feat(z, B, OH, OH, spec.stem_out)
-            self._tf("stem", z)
+            return Feat(z, B, OH, OH, spec.stem_out)
+        Cin, wstem = x.shape[1], ps.w(f"{P}._conv_stem.conv.weight")
+        if train:
+            st = self._bn_stats(f"{P}._bn0", True)
+            a, live = self._bn_aff(f"{P}._bn0", True, st, B * OH * OH)
+            call("mmd_stem_conv_fwd", x, wstem, z, B, Cin, S, S, ps.stem_kp, spec.stem_out, None, None, NONE, st,
+                 *self._stats_ws(st, B * OH * OH, spec.stem_out))
+            out = Feat(z, B, OH, OH, spec.stem_out, a.scale, a.shift, SWISH, live)
+            tape.stem = StemRec(x, out, a.mean, a.invstd)
+            return out
+        # frozen net: the folded BN + swish ride in the producer's epilogue (once per element) instead of the depthwise
+        # prologue, which would redo them for every halo pixel (1.6x for 3x3, 2.25x for 5x5 tiles)
+        b0 = ps.bn(f"{P}._bn0")
+        call("mmd_stem_conv_fwd", x, wstem, z, B, Cin, S, S, ps.stem_kp, spec.stem_out, b0["fscale"], b0["fshift"], SWISH, None, None, 0)
+        self._tf("stem", z)
+        return Feat(z, B, OH, OH, spec.stem_out)
+
+    def _forward_blocks(self, cur: Feat, train: bool, drop_scale, tape: Tape) -> List[Feat]:
+        """The MBConv blocks in order -> the tapped block outputs (the BiFPN's inputs)."""
         taps: List[Feat] = []
         skip_i = 0
-        for blk in spec.blocks:
-            q = f"{P}._blocks.{blk.idx}"
+        for blk in self.spec.blocks:
             inp = cur
-            rec = {"inp": inp}
             self._use(inp)                  # the block's own path ...
             if blk.skip:
                 self._use(inp)              # ... and the identity skip
-            fused_front = (not train and blk.expand != 1 and ps.flat.is_cuda
-                           and _lib.LIB.load().mmd_mbconv_expand_dw_supported(inp.C, blk.cmid, blk.kernel, blk.stride) == 1)
-            if fused_front:
-                f0 = None           # frozen net, thin input: expand + depthwise in one kernel below, the expanded tensor stays in LDS
-            elif blk.expand != 1:
-                st0 = self._bn_stats(f"{q}._bn0", train)
-                a0, live0 = self._bn_aff(f"{q}._bn0", train, st0, inp.M)
-                if train:
-                    z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, stats=st0)
-                    f0 = Feat(z0, B, inp.H, inp.W, blk.cmid, a0.scale, a0.shift, SWISH, live0)
-                else:           # frozen net: activate in the producer's epilogue (see the stem)
-                    z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, out_aff=(a0.scale, a0.shift), out_act=SWISH)
-                    f0 = Feat(z0, B, inp.H, inp.W, blk.cmid)
-                rec["f0"], rec["bn0"] = f0, a0
-            else:
-                f0 = inp
-            res = inp.z if blk.skip else None
-            H1, W1 = -(-inp.H // blk.stride), -(-inp.W // blk.stride)
-            M1 = B * H1 * W1
-            # (frozen nets: Q36 fixed-point integer sums - bit-reproducible whatever order the blocks' atomics arrive in, csrc/common.h mmd_pool_add)
-            pooled = self._zalloc((B, blk.cmid)) if train else self._zalloc((B, blk.cmid), torch.int64)
-            hpre = self._alloc(B, blk.se)
-            gate = self._alloc(B, blk.cmid)
-            se_w = (ps.w(f"{q}._se_reduce.conv.weight"), ps.w(f"{q}._se_reduce.conv.bias"),
-                    ps.w(f"{q}._se_expand.conv.weight"), ps.w(f"{q}._se_expand.conv.bias"))
             if train:
-                st1 = self._bn_stats(f"{q}._bn1", True)
-                z1, _, _ = self._dw(f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride, stats=st1)
-                a1, live1 = self._bn_aff(f"{q}._bn1", True, st1, M1)
-                f1 = Feat(z1, B, H1, W1, blk.cmid, a1.scale, a1.shift, SWISH, live1)
-                call("mmd_chan_pool", z1, *self._xf(f1)[:2], *self._xf(f1)[3:], SWISH, None, pooled, 1.0 / (H1 * W1), B,
-                     H1 * W1, blk.cmid)
-                call("mmd_se_fc_fwd", pooled, *se_w, hpre, gate, B, blk.cmid, blk.se)
-                st2 = self._bn_stats(f"{q}._bn2", True)
-                z2 = self._pw(f1, f"{q}._project_conv.conv.weight", blk.cout, stats=st2, gate=gate)
-                a2, live2 = self._bn_aff(f"{q}._bn2", True, st2, M1)
-                y = self._alloc(M1, blk.cout)
-                rs = None
-                if blk.skip and blk.drop_rate and drop_scale is not None:
-                    rs = drop_scale[skip_i]
-                call("mmd_affine_act", z2, None, None, *live2, NONE, rs, H1 * W1, res, y, M1, blk.cout)
-                rec.update(f1=f1, bn1=a1, pooled=pooled, hpre=hpre, gate=gate, z2=z2, bn2=a2, rs=rs)
-                self._bnout[y.data_ptr()] = BnOut(z2, a2.mean, a2.invstd, blk.cout, rs, H1 * W1)
+                rs = drop_scale[skip_i] if blk.skip and blk.drop_rate and drop_scale is not None else None
+                rec = tape.blocks[blk.idx] = self._block_fwd_train(blk, inp, rs)
+                cur = rec.out
             else:
-                # frozen net: BN1+swish and the SE average pool ride in the depthwise epilogue (no separate pool pass)
-                b1 = ps.bn(f"{q}._bn1")
-                if fused_front:
-                    b0 = ps.bn(f"{q}._bn0")
-                    a1v = self._alloc(M1, blk.cmid)
-                    self._c("mmd_mbconv_expand_dw_fwd", inp.z, ps.w(f"{q}._expand_conv.conv.weight"), b0["fscale"], b0["fshift"],
-                         ps.w(f"{q}._depthwise_conv.conv.weight"), b1["fscale"], b1["fshift"], a1v, pooled, B, inp.H, inp.W, inp.C,
-                         blk.cmid, blk.kernel, blk.stride)
-                else:
-                    a1v, _, _ = self._dw(f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride,
-                                         out_aff=(b1["fscale"], b1["fshift"]), out_act=SWISH, pool=pooled)
-                f1 = Feat(a1v, B, H1, W1, blk.cmid)
-                self._c("mmd_se_fc_fwd_q", pooled, *se_w, hpre, gate, B, blk.cmid, blk.se)
-                b2 = ps.bn(f"{q}._bn2")
-                y = self._pw(f1, f"{q}._project_conv.conv.weight", blk.cout, gate=gate,
-                             out_aff=(b2["fscale"], b2["fshift"]), residual=res)
+                cur = self._block_fwd_frozen(blk, inp)
             if blk.skip:
                 skip_i += 1
             if blk.idx == self.mark_block and self.ps.flat.is_cuda:
                 self.mark_event = torch.cuda.current_stream().record_event()      # "this net is past block k" (step.py staggers the teachers on it)
-            cur = Feat(y, B, H1, W1, blk.cout)
-            self._tf(f"blk{blk.idx}", y)
-            rec["out"] = cur
-            if train:
-                tape[f"blk{blk.idx}"] = rec
-            if blk.idx in spec.taps:
+            self._tf(f"blk{blk.idx}", cur.z)
+            if blk.idx in self.spec.taps:
                 taps.append(cur)
-        # ---- BiFPN
-        feats = self._bifpn(taps, train, tape)
-        # ---- heads
+        return taps
+
+    def _se_bufs(self, blk, q: str, B: int, pooled_dtype):
+        """What the two regimes of a block share -> (pooled, hpre, gate, squeeze-excite FC parameters).  Each calls it BEHIND its expand conv,
+        where these allocations have always stood: the arenas hand out addresses in call order."""
+        ps = self.ps
+        pooled = self._zalloc((B, blk.cmid), pooled_dtype)
+        hpre = self._alloc(B, blk.se)
+        gate = self._alloc(B, blk.cmid)
+        return pooled, hpre, gate, (ps.w(f"{q}._se_reduce.conv.weight"), ps.w(f"{q}._se_reduce.conv.bias"),
+                                    ps.w(f"{q}._se_expand.conv.weight"), ps.w(f"{q}._se_expand.conv.bias"))
+
+    def _block_fwd_train(self, blk, inp: Feat, rs: Optional[torch.Tensor]) -> BlockRec:
+        """One MBConv block in train mode: every conv writes its raw output + BatchNorm sums, its consumer applies the live BatchNorm + swish;
+        only the block output is materialised (BatchNorm-2 [* rs per image] + skip in one mmd_affine_act)."""
+        ps, q, B = self.ps, f"backbone_net.model._blocks.{blk.idx}", inp.B
+        f0, a0 = inp, None
+        if blk.expand != 1:
+            st0 = self._bn_stats(f"{q}._bn0", True)
+            a0, live0 = self._bn_aff(f"{q}._bn0", True, st0, inp.M)
+            z0 = self._pw(inp, f"{q}._expand_conv.conv.weight", blk.cmid, stats=st0)
+            f0 = Feat(z0, B, inp.H, inp.W, blk.cmid, a0.scale, a0.shift, SWISH, live0)
+        pooled, hpre, gate, se_w = self._se_bufs(blk, q, B, torch.float32)
+        st1 = self._bn_stats(f"{q}._bn1", True)
+        z1, H1, W1 = self._dw(f0, f"{q}._depthwise_conv.conv.weight", blk.kernel, blk.stride, stats=st1)
+        M1 = B * H1 * W1
+        a1, live1 = self._bn_aff(f"{q}._bn1", True, st1, M1)
+        f1 = Feat(z1, B, H1, W1, blk.cmid, a1.scale, a1.shift, SWISH, live1)
+        call("mmd_chan_pool", z1, None, None, *live1, SWISH, None, pooled, 1.0 / (H1 * W1), B, H1 * W1, blk.cmid)
+        call("mmd_se_fc_fwd", pooled, *se_w, hpre, gate, B, blk.cmid, blk.se)
+        st2 = self._bn_stats(f"{q}._bn2", True)
+        z2 = self._pw(f1, f"{q}._project_conv.conv.weight", blk.cout, stats=st2, gate=gate)
+        a2, live2 = self._bn_aff(f"{q}._bn2", True, st2, M1)
+        y = self._alloc(M1, blk.cout)
+        call("mmd_affine_act", z2, None, None, *live2, NONE, rs, H1 * W1, inp.z if blk.skip else None, y, M1, blk.cout)
+        self._bnout[y.data_ptr()] = BnOut(z2, a2.mean, a2.invstd, blk.cout, rs, H1 * W1)
+        return BlockRec(inp=inp, out=Feat(y, B, H1, W1, blk.cout), f0=f0, bn0=a0, f1=f1, bn1=a1, pooled=pooled, hpre=hpre, gate=gate,
+                        z2=z2, bn2=a2, rs=rs)
+
+    def _block_fwd_frozen(self, blk, inp: Feat) -> Feat:
+        """One MBConv block of a frozen net (alone or in a pack): the folded BatchNorms + swish ride in the producers' epilogues (see the
+        stem), BN1 + swish and the squeeze-excite average pool in the depthwise epilogue (no separate pool pass)."""
+        ps, q, B = self.ps, f"backbone_net.model._blocks.{blk.idx}", inp.B
+
+        def bn(i):                  # folded (scale, shift) of the block's BatchNorm i
+            b = ps.bn(f"{q}._bn{i}")
+            return b["fscale"], b["fshift"]
+
+        wexp, wdw = f"{q}._expand_conv.conv.weight", f"{q}._depthwise_conv.conv.weight"
+        H1, W1 = -(-inp.H // blk.stride), -(-inp.W // blk.stride)
+        # thin input: expand + depthwise in one kernel below, the expanded tensor stays in LDS
+        fused_front = (blk.expand != 1 and ps.flat.is_cuda
+                       and _lib.LIB.load().mmd_mbconv_expand_dw_supported(inp.C, blk.cmid, blk.kernel, blk.stride) == 1)
+        f0 = inp
+        if blk.expand != 1 and not fused_front:
+            f0 = Feat(self._pw(inp, wexp, blk.cmid, out_aff=bn(0), out_act=SWISH), B, inp.H, inp.W, blk.cmid)
+        # (pooled: Q36 fixed-point integer sums - bit-reproducible whatever order the blocks' atomics arrive in, csrc/common.h mmd_pool_add)
+        pooled, hpre, gate, se_w = self._se_bufs(blk, q, B, torch.int64)
+        if fused_front:
+            a1v = self._alloc(B * H1 * W1, blk.cmid)
+            self._c("mmd_mbconv_expand_dw_fwd", inp.z, ps.w(wexp), *bn(0), ps.w(wdw), *bn(1), a1v, pooled, B, inp.H, inp.W, inp.C,
+                    blk.cmid, blk.kernel, blk.stride)
+        else:
+            a1v, _, _ = self._dw(f0, wdw, blk.kernel, blk.stride, out_aff=bn(1), out_act=SWISH, pool=pooled)
+        self._c("mmd_se_fc_fwd_q", pooled, *se_w, hpre, gate, B, blk.cmid, blk.se)
+        y = self._pw(Feat(a1v, B, H1, W1, blk.cmid), f"{q}._project_conv.conv.weight", blk.cout, gate=gate, out_aff=bn(2),
+                     residual=inp.z if blk.skip else None)
+        return Feat(y, B, H1, W1, blk.cout)
+
+    def _forward_heads(self, feats: List[Feat], train: bool, raw_logits: bool, tape: Tape):
+        """Regressor, then classifier, over the pyramid row buffer the last BiFPN cell wrote -> (cls [B,A,NC], reg [B,A,4])."""
+        spec, B = self.spec, feats[0].B
         for f in feats:
             self._use(f)                    # one contribution: heads' input gradients (+ the MTA loss' feature gradient) in one launch
         A = sum(f.H * f.W for f in feats) * spec.num_anchors
@@ -574,79 +651,60 @@ class Net:
         cls = self._alloc(B, A, spec.num_classes)
         self._head("regressor", feats, 4, reg, A, NONE, train, tape)
         self._head("classifier", feats, spec.num_classes, cls, A, NONE if raw_logits else SIGMOID, train, tape)
-        if train:
-            tape["feats"] = feats
-            tape["A"] = A
-            tape["cls"] = cls
-            self._counting = False
-            # every BN layer finalized in one launch: running stats + (scale, shift, mean, invstd) for the backward
-            key = (B, S)
-            if self._bn_count_key != key:
-                self.bn_count.copy_(self.bn_count_host)
-                self._bn_count_key = key
-            call("mmd_bn_finalize_all", self.stats_flat, self.bn_count, self.bn_layer_off, self.bn_layer_c,
-                 ps.flat[ps.gamma_off:ps.gamma_off + ps.bn_total], ps.flat[ps.beta_off:ps.beta_off + ps.bn_total],
-                 ps.rmean, ps.rvar, float(self.bn_momentum), BN_EPS, self.t_scale, self.t_shift, self.t_mean,
-                 self.t_invstd, ps.bn_total, ps.nbt, ps.nbt.numel())      # (+ num_batches_tracked += 1 for every BN, in the same launch)
-        return cls, reg, feats
+        tape.feats, tape.A = feats, A
+        return cls, reg
 
-    def _sep_bn(self, name: str, x: Feat, train: bool, rec: dict, bn_name: Optional[str] = None, y=None, zd=None) -> Feat:
-        """SeparableConvBlock(norm=True, activation=False) on a materialised input -> materialised output.
-        zd: depthwise output already produced by the fused fusion+depthwise kernel."""
+    def _finalize_bn(self, key: tuple):
+        """Every BN layer finalized in one launch: running stats + (scale, shift, mean, invstd) for the backward.  key = (B, S): the
+        per-layer row counts the forward noted in bn_count_host are uploaded when it changes."""
         ps = self.ps
-        W = x.C
-        if zd is None:
-            zd, _, _ = self._dw(x, f"{name}.depthwise_conv.conv.weight", 3, 1)
-        zdf = Feat(zd, x.B, x.H, x.W, W)
-        bn_name = bn_name or f"{name}.bn"
+        if self._bn_count_key != key:
+            self.bn_count.copy_(self.bn_count_host)
+            self._bn_count_key = key
+        call("mmd_bn_finalize_all", self.stats_flat, self.bn_count, self.bn_layer_off, self.bn_layer_c,
+             ps.flat[ps.gamma_off:ps.gamma_off + ps.bn_total], ps.flat[ps.beta_off:ps.beta_off + ps.bn_total],
+             ps.rmean, ps.rvar, float(self.bn_momentum), BN_EPS, self.t_scale, self.t_shift, self.t_mean,
+             self.t_invstd, ps.bn_total, ps.nbt, ps.nbt.numel())      # (+ num_batches_tracked += 1 for every BN, in the same launch)
+
+    def _sep_bn(self, name: str, zdf: Feat, train: bool, y=None):
+        """The 1x1 conv + BatchNorm of a SeparableConvBlock(norm=True, activation=False) on its depthwise output zdf
+        -> (materialised output, raw conv output z, Aff); z and Aff are None in eval, where the folded BatchNorm rides in the conv's epilogue."""
+        ps, W, M = self.ps, zdf.C, zdf.M
         bias = ps.w(f"{name}.pointwise_conv.conv.bias")
-        if train:
-            st = self._bn_stats(bn_name, True)
-            z = self._pw(zdf, f"{name}.pointwise_conv.conv.weight", W, bias=bias, stats=st)
-            a, live = self._bn_aff(bn_name, True, st, x.M)
-            if y is None:
-                y = self._alloc(x.M, W)
-            call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, x.M, W)
-            rec.update(zd=zdf, z=z, bn=a)
-            self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
-        else:
-            b = ps.bn(bn_name)
+        if not train:
+            b = ps.bn(f"{name}.bn")
             y = self._pw(zdf, f"{name}.pointwise_conv.conv.weight", W, bias=bias, out_aff=(b["fscale"], b["fshift"]), y=y)
-        return Feat(y, x.B, x.H, x.W, W)
+            return Feat(y, zdf.B, zdf.H, zdf.W, W), None, None
+        st = self._bn_stats(f"{name}.bn", True)
+        z = self._pw(zdf, f"{name}.pointwise_conv.conv.weight", W, bias=bias, stats=st)
+        a, live = self._bn_aff(f"{name}.bn", True, st, M)
+        if y is None:
+            y = self._alloc(M, W)
+        call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, M, W)
+        self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
+        return Feat(y, zdf.B, zdf.H, zdf.W, W), z, a
 
-    def _down_channel(self, name: str, x: Feat, train: bool, tape: dict, lazy: bool = False) -> Feat:
-        ps = self.ps
-        W = self.spec.fpn_w
+    def _down_channel(self, name: str, x: Feat, train: bool, tape: Tape, lazy: bool = False) -> Feat:
+        ps, W = self.ps, self.spec.fpn_w
         bias = ps.w(f"{name}.0.conv.bias")
-        rec = {"x": x}
-        if train and lazy:
-            # lazy output: the raw conv output + its BatchNorm as a pending transform the consuming node kernels apply (no affine launch)
-            st = self._bn_stats(f"{name}.1", True)
-            z = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, stats=st)
-            a, live = self._bn_aff(f"{name}.1", True, st, x.M)
-            rec.update(z=z, bn=a)
-            tape[name] = rec
-            self._use(x)
-            self._bnout[z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
-            out = Feat(z, x.B, x.H, x.W, W, a.scale, a.shift, NONE, live)
-            rec["out"] = out
-            return out
-        if train:
-            st = self._bn_stats(f"{name}.1", True)
-            z = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, stats=st)
-            a, live = self._bn_aff(f"{name}.1", True, st, x.M)
-            y = self._alloc(x.M, W)
-            call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, x.M, W)
-            rec.update(z=z, bn=a)
-            tape[name] = rec
-            self._use(x)
-            self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
-        else:
+        if not train:
             b = ps.bn(f"{name}.1")
-            y = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, out_aff=(b["fscale"], b["fshift"]))
-        out = Feat(y, x.B, x.H, x.W, W)
-        self._tf(name, y)
-        rec["out"] = out
+            out = Feat(self._pw(x, f"{name}.0.conv.weight", W, bias=bias, out_aff=(b["fscale"], b["fshift"])), x.B, x.H, x.W, W)
+        else:
+            st = self._bn_stats(f"{name}.1", True)
+            z = self._pw(x, f"{name}.0.conv.weight", W, bias=bias, stats=st)
+            a, live = self._bn_aff(f"{name}.1", True, st, x.M)
+            if lazy:
+                # lazy output: the raw conv output + its BatchNorm as a pending transform the consuming node kernels apply (no affine launch)
+                out = Feat(z, x.B, x.H, x.W, W, a.scale, a.shift, NONE, live)
+            else:
+                y = self._alloc(x.M, W)
+                call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, x.M, W)
+                out = Feat(y, x.B, x.H, x.W, W)
+            self._use(x)
+            self._bnout[out.z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
+            tape.down[name] = DownRec(x, out, z, a)
+        self._tf(name, out.z)       # (does nothing to a lazy output: lazy forwards run without the test hooks, see _bifpn)
         return out
 
     def _pool(self, x: Feat) -> Feat:
@@ -657,83 +715,81 @@ class Net:
         return Feat(y, x.B, OH, OW, x.C)
 
     def _node(self, cell: str, conv: str, theta: str, in0: Feat, in1: Optional[Feat], up: Optional[Feat],
-              pl: Optional[Feat], train: bool, tape: dict, y=None) -> Feat:
-        out = self._node_impl(cell, conv, theta, in0, in1, up, pl, train, tape, y)
-        self._tf(f"{cell}.{conv}", out.z)
-        return out
-
-    def _node_impl(self, cell: str, conv: str, theta: str, in0: Feat, in1: Optional[Feat], up: Optional[Feat],
-                   pl: Optional[Feat], train: bool, tape: dict, y=None) -> Feat:
-        th = self.ps.w(f"{cell}.{theta}")
+              pl: Optional[Feat], train: bool, tape: Tape, y=None) -> Feat:
+        """One BiFPN node: fast-attention fusion of its operands (in0, same-resolution in1, upsampled `up`, max-pooled `pl`), depthwise 3x3,
+        1x1 conv, BatchNorm.  y: the rows to write a materialised output to (the last cell's pyramid row buffer)."""
+        name, th, ops = f"{cell}.{conv}", self.ps.w(f"{cell}.{theta}"), (in0, in1, up, pl)
         if not train and self.FUSE_NODE and self._node_fusable(in0):
-            # frozen net: fusion + depthwise + 1x1 conv + folded BN in one launch, the depthwise output never leaves the CU
-            name = f"{cell}.{conv}"
-            b = self.ps.bn(f"{name}.bn")
-            if y is None:
-                y = self._alloc(in0.M, in0.C)
-            self._c("mmd_bifpn_node_fwd_fused", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                 self.ps.w(f"{name}.depthwise_conv.conv.weight"), self.ps.w(f"{name}.pointwise_conv.conv.weight"),
-                 self.ps.w(f"{name}.pointwise_conv.conv.bias"), b["fscale"], b["fshift"], y, in0.B, in0.H, in0.W, in0.C)
-            return Feat(y, in0.B, in0.H, in0.W, in0.C)
-        # (also in the bf16 modes: the node's 1x1 conv then runs exact fp32 products in the forward - closer to the fp32 reference than the
-        # mode's operand-rounding rule asks for; its two gradient GEMMs follow the mode)
-        if train and self._node_fusable(in0):
-            # trainable net: fusion + depthwise + 1x1 conv + BatchNorm sums in one launch (raw z out, depthwise output kept for the backward)
-            name, W = f"{cell}.{conv}", in0.C
-            bn_name = f"{name}.bn"
-            st = self._bn_stats(bn_name, True)
-            z, zd = self._alloc(in0.M, W), self._alloc(in0.M, W)
-            ops = (in0, in1, up, pl)
-            lz = [o is not None and o.bn is not None for o in ops]          # operands whose BatchNorm is still pending (lazy producers)
-            args = (in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                    self.ps.w(f"{name}.depthwise_conv.conv.weight"), self.ps.w(f"{name}.pointwise_conv.conv.weight"),
-                    self.ps.w(f"{name}.pointwise_conv.conv.bias"), z, zd, st, in0.B, in0.H, in0.W, W)
-            if any(lz):
-                assert self._lazy and all(o.act == NONE for o, l in zip(ops, lz) if l)
-                vp = ctypes.c_void_p
-                pick = lambda k: (vp * 4)(*[(o.bn[k].data_ptr() if l else None) for o, l in zip(ops, lz)])
-                cnt = (ctypes.c_longlong * 4)(*[(int(o.bn[3]) if l else 0) for o, l in zip(ops, lz)])
-                call("mmd_bifpn_node_fwd_fused_train_lz", *args, pick(0), pick(1), pick(2), cnt)
+            out = self._node_fused_frozen(name, th, ops, y)
+        else:
+            # (the whole-node train kernel also in the bf16 modes: the node's 1x1 conv then runs exact fp32 products in the forward - closer to
+            # the fp32 reference than the mode's operand-rounding rule asks for; its two gradient GEMMs follow the mode)
+            if train and self._node_fusable(in0):
+                zd, z, a, out = self._node_fused_train(name, th, ops, y)
             else:
-                call("mmd_bifpn_node_fwd_fused_train", *args)
-            a, live = self._bn_aff(bn_name, True, st, in0.M)
+                zd, z, a, out = self._node_two_launch(name, th, ops, train, y)
             for operand in ops:
                 if operand is not None:
                     self._use(operand)
-            if pl is not None:
+            if pl is not None and train:
                 self._linear.add(pl.z.data_ptr())
-            zdf = Feat(zd, in0.B, in0.H, in0.W, W)
-            if self._lazy and y is None:
-                # lazy output (every cell but the last, whose outputs the heads and the MTA loss read): no affine launch
-                out = Feat(z, in0.B, in0.H, in0.W, W, a.scale, a.shift, NONE, live)
-                self._bnout[z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
-            else:
-                if y is None:
-                    y = self._alloc(in0.M, W)
-                call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, in0.M, W)
-                out = Feat(y, in0.B, in0.H, in0.W, W)
-                self._bnout[y.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
-            tape.setdefault(cell + ".nodes", []).append({"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "conv": conv,
-                                                         "zd": zdf, "z": z, "bn": a, "out": out})
-            return out
-        # the fused activation is not materialised: the node's backward launch recomputes it, also for the depthwise weight gradient
-        zd = self._alloc(in0.M, in0.C)
-        self._c("mmd_bifpn_node_dw_fwd", in0.z, in1.z if in1 else None, up.z if up else None, pl.z if pl else None, th,
-                self.ps.w(f"{cell}.{conv}.depthwise_conv.conv.weight"), None, zd, in0.B, in0.H, in0.W, in0.C)
-        ff = Feat(zd, in0.B, in0.H, in0.W, in0.C)      # (stands for the fused input of _sep_bn, which only reads its geometry: zd is given)
-        for operand in (in0, in1, up, pl):
-            if operand is not None:
-                self._use(operand)
-        if pl is not None and train:
-            self._linear.add(pl.z.data_ptr())
-        rec = {"in0": in0, "in1": in1, "up": up, "pl": pl, "theta": theta, "conv": conv}
-        out = self._sep_bn(f"{cell}.{conv}", ff, train, rec, y=y, zd=zd)
-        rec["out"] = out
-        if train:
-            tape.setdefault(cell + ".nodes", []).append(rec)
+            tape.nodes[-1].append(NodeRec(in0, in1, up, pl, theta, conv, zd, z, a, out))
+        self._tf(name, out.z)
         return out
 
-    def _bifpn(self, taps: List[Feat], train: bool, tape: dict) -> List[Feat]:
+    def _node_fused_frozen(self, name: str, th, ops, y) -> Feat:
+        """frozen net: fusion + depthwise + 1x1 conv + folded BN in one launch, the depthwise output never leaves the CU"""
+        ps, in0 = self.ps, ops[0]
+        b = ps.bn(f"{name}.bn")
+        if y is None:
+            y = self._alloc(in0.M, in0.C)
+        self._c("mmd_bifpn_node_fwd_fused", *[o.z if o is not None else None for o in ops], th,
+                ps.w(f"{name}.depthwise_conv.conv.weight"), ps.w(f"{name}.pointwise_conv.conv.weight"),
+                ps.w(f"{name}.pointwise_conv.conv.bias"), b["fscale"], b["fshift"], y, in0.B, in0.H, in0.W, in0.C)
+        return Feat(y, in0.B, in0.H, in0.W, in0.C)
+
+    def _node_fused_train(self, name: str, th, ops, y):
+        """trainable net: fusion + depthwise + 1x1 conv + BatchNorm sums in one launch (raw z out, depthwise output kept for the backward)
+        -> (depthwise output, z, Aff, node output)"""
+        ps, in0 = self.ps, ops[0]
+        W = in0.C
+        st = self._bn_stats(f"{name}.bn", True)
+        z, zd = self._alloc(in0.M, W), self._alloc(in0.M, W)
+        args = (*[o.z if o is not None else None for o in ops], th,
+                ps.w(f"{name}.depthwise_conv.conv.weight"), ps.w(f"{name}.pointwise_conv.conv.weight"),
+                ps.w(f"{name}.pointwise_conv.conv.bias"), z, zd, st, in0.B, in0.H, in0.W, W)
+        lives = [o.bn if o is not None else None for o in ops]          # operands whose BatchNorm is still pending (lazy producers)
+        if any(lv is not None for lv in lives):
+            assert self._lazy and all(o.act == NONE for o, lv in zip(ops, lives) if lv is not None)
+            stats, gamma, beta, count = zip(*[lv if lv is not None else Live(None, None, None, 0) for lv in lives])
+            ptrs = lambda col: (ctypes.c_void_p * 4)(*[None if t is None else t.data_ptr() for t in col])
+            call("mmd_bifpn_node_fwd_fused_train_lz", *args, ptrs(stats), ptrs(gamma), ptrs(beta), (ctypes.c_longlong * 4)(*count))
+        else:
+            call("mmd_bifpn_node_fwd_fused_train", *args)
+        a, live = self._bn_aff(f"{name}.bn", True, st, in0.M)
+        if self._lazy and y is None:
+            # lazy output (every cell but the last, whose outputs the heads and the MTA loss read): no affine launch
+            out = Feat(z, in0.B, in0.H, in0.W, W, a.scale, a.shift, NONE, live)
+        else:
+            if y is None:
+                y = self._alloc(in0.M, W)
+            call("mmd_affine_act", z, None, None, *live, NONE, None, 0, None, y, in0.M, W)
+            out = Feat(y, in0.B, in0.H, in0.W, W)
+        self._bnout[out.z.data_ptr()] = BnOut(z, a.mean, a.invstd, W, None, 0)
+        return Feat(zd, in0.B, in0.H, in0.W, W), z, a, out
+
+    def _node_two_launch(self, name: str, th, ops, train: bool, y):
+        """fusion + depthwise in one launch, then the 1x1 conv (train: + BatchNorm sums, and an affine launch) -> as _node_fused_train.
+        The fused activation is not materialised: the node's backward launch recomputes it, also for the depthwise weight gradient"""
+        in0 = ops[0]
+        zd = self._alloc(in0.M, in0.C)
+        self._c("mmd_bifpn_node_dw_fwd", *[o.z if o is not None else None for o in ops], th,
+                self.ps.w(f"{name}.depthwise_conv.conv.weight"), None, zd, in0.B, in0.H, in0.W, in0.C)
+        zdf = Feat(zd, in0.B, in0.H, in0.W, in0.C)
+        out, z, a = self._sep_bn(name, zdf, train, y=y)
+        return zdf, z, a, out
+
+    def _bifpn(self, taps: List[Feat], train: bool, tape: Tape) -> List[Feat]:
         feats: List[Feat] = list(taps)
         # "lazy" BiFPN operands of the trainable net (round 4): a node's / down-channel conv's train-mode BatchNorm is applied by the CONSUMING
         # node kernels while they load the operand (forward: from the live batch sums; backward: finalized coefficients) instead of by an
@@ -744,6 +800,7 @@ class Net:
         lz = self._lazy
         for c in range(self.spec.fpn_cells):
             cell = f"bifpn.{c}"
+            tape.nodes.append([])
             if c == 0:
                 p3, p4, p5 = feats
                 c6 = self._down_channel(f"{cell}.p5_to_p6", p5, train, tape)         # (max-pooled by its own launch: materialised)
@@ -752,16 +809,14 @@ class Net:
                 p3_in = self._down_channel(f"{cell}.p3_down_channel", p3, train, tape, lazy=lz)
                 p4_in = self._down_channel(f"{cell}.p4_down_channel", p4, train, tape, lazy=lz)
                 p5_in = self._down_channel(f"{cell}.p5_down_channel", p5, train, tape, lazy=lz)
-                if train:
-                    tape[cell + ".first"] = {"c6": c6, "p6_in": p6_in, "p7_in": p7_in}
+                tape.first = FirstCellRec(c6, p6_in, p7_in)
             else:
                 p3_in, p4_in, p5_in, p6_in, p7_in = feats
             last = c == self.spec.fpn_cells - 1
             if last:    # final outputs land in ONE pyramid row buffer so the shared-weight heads run all levels per launch
-                sizes = [(p3_in.H, p3_in.W), (p4_in.H, p4_in.W), (p5_in.H, p5_in.W), (p6_in.H, p6_in.W), (p7_in.H, p7_in.W)]
-                pyr = self._make_pyr(p3_in.B, sizes)
+                pyr = Pyramid(p3_in.B, [(f.H, f.W) for f in (p3_in, p4_in, p5_in, p6_in, p7_in)])
                 fcat = self._alloc_pyr(pyr, p3_in.C, train)
-                ov = [fcat[pyr["row0"][l]:pyr["row0"][l] + pyr["rows"][l]] for l in range(5)]
+                ov = pyr.levels(fcat)
                 self._pyr, self._fcat = pyr, fcat
             else:
                 ov = [None] * 5
@@ -779,118 +834,94 @@ class Net:
             feats = [p3_out, p4_out, p5_out, p6_out, p7_out]
         return feats
 
-    def _make_pyr(self, B: int, sizes):
-        rows = [B * h * w for h, w in sizes]
-        row0 = [0]
-        for r in rows:
-            row0.append(row0[-1] + (r + 127) // 128 * 128)
-        flat = [len(sizes), B]
-        for h, w in sizes:
-            flat += [h, w]
-        return {"desc": (ctypes.c_int * len(flat))(*flat), "row0": row0, "rows": rows, "sizes": sizes, "B": B,
-                "total": row0[-1], "padded": row0[-1] != sum(rows)}
-
-    def _alloc_pyr(self, pyr, C: int, zero_pad: bool = True) -> torch.Tensor:
+    def _alloc_pyr(self, pyr: Pyramid, C: int, zero_pad: bool = True) -> torch.Tensor:
         """zero_pad=False: a frozen net's tensor - nothing multiplies its padding rows into a sum (no weight gradients, no batch statistics), whatever
         they hold stays in the padding rows of its consumers' outputs (D4 / 768^2, whose 6^2 level is padded: 40 fill launches less on the pack's chain)."""
-        t = self._alloc(pyr["total"], C)
-        if pyr["padded"] and zero_pad:          # padding rows are multiplied in the weight-gradient GEMMs: they must be zeros, not stale bits
-            for l in range(len(pyr["rows"])):       # (only the pad rows: a whole-buffer memset per pyramid tensor cost 1.8 ms/step at 768)
-                lo, hi = pyr["row0"][l] + pyr["rows"][l], pyr["row0"][l + 1]
+        t = self._alloc(pyr.total, C)
+        if pyr.padded and zero_pad:             # padding rows are multiplied in the weight-gradient GEMMs: they must be zeros, not stale bits
+            for l in range(len(pyr.rows)):          # (only the pad rows: a whole-buffer memset per pyramid tensor cost 1.8 ms/step at 768)
+                lo, hi = pyr.row0[l] + pyr.rows[l], pyr.row0[l + 1]
                 if hi > lo:
                     call("mmd_memset_async", t[lo:hi], 0, (hi - lo) * C * 4)
         return t
 
+    def _head_nsplit(self) -> int:
+        """How many leading pyramid levels the heads' pyramid launches cover: all 5 outside a pack forward.
+        Pack forward (grouped frozen nets): the pyramid GEMM's 128-row tiles must not straddle two nets' rows, i.e. every level needs
+        images_per_group * H * W % 128 == 0.  D4 / 768^2 at B = 8 misses that on the 6 x 6 level only (288 rows per net): the launches
+        then cover the leading levels and each trailing level runs as a plain launch of its own - few rows, so the GEMM lands on the
+        32-row skinny kernel, whose tiles divide 288 (csrc/pw_gemm.hip pw_dispatch checks the tile height of the kernel it takes)."""
+        if self._grp is None:
+            return 5
+        good = [(self._grp[1] * h * w) % 128 == 0 for h, w in self._pyr.sizes]
+        nsplit = good.index(False) if False in good else 5
+        if any(good[nsplit:]) or nsplit == 0:
+            raise RuntimeError("pack forward: pyramid levels %r at %d images per net do not split into whole-tile and small trailing levels" % (self._pyr.sizes, self._grp[1]))
+        return nsplit
+
+    def _head_dw(self, x, cname: str, y, xf: tuple, nsplit: int, lev_stride: int):
+        """Depthwise 3x3 of a head layer over pyramid rows x -> y: the leading nsplit levels in one launch, each trailing level in a plain
+        launch.  xf = (scale, shift, act, stats, gamma, beta): x's pending transform, level l's coefficients l * lev_stride channels in."""
+        pyr, C, w = self._pyr, x.shape[1], self.ps.w(f"{cname}.depthwise_conv.conv.weight")
+        self._c("mmd_dwconv3_pyr", x, w, y, pyr.head_desc(nsplit), C, 0, *xf, lev_stride, None, None, None, NONE, None, None, None, None)
+        sc, sh, act = xf[:3]
+        for l in range(nsplit, 5):
+            (h, wd), lo = pyr.sizes[l], l * lev_stride
+            self._c("mmd_dwconv_fwd", pyr.level(x, l), w, pyr.level(y, l), pyr.B, h, wd, C, 3, 1, sc[lo:] if sc is not None else None,
+                    sh[lo:] if sh is not None else None, act, None, None, None, 0, None, None, NONE, None, None, None, 0)
+
+    def _head_pw(self, x, cname: str, y, N: int, out_act: int, stats, lev_stride: int, nsplit: int, ybs: int = 0, yoff=None):
+        """1x1 conv + bias of a head layer over pyramid rows x, split like _head_dw.  yoff None: y is a pyramid row buffer (stats: the
+        per-level BatchNorm sums, lev_stride channels apart); else the header: level l's rows go to y[image, yoff[l]:], images ybs apart."""
+        pyr, C = self._pyr, x.shape[1]
+        w, bias = self.ps.w(f"{cname}.pointwise_conv.conv.weight"), self.ps.w(f"{cname}.pointwise_conv.conv.bias")
+        self._c("mmd_pwconv_fwd_pyr" + self._sfx, x, w, y, pyr.head_desc(nsplit), C, N, bias, out_act, stats, lev_stride, ybs,
+                None if yoff is None else (ctypes.c_longlong * 5)(*yoff))
+        for l in range(nsplit, 5):
+            h, wd = pyr.sizes[l]
+            self._c("mmd_pwconv_fwd" + self._sfx, pyr.level(x, l), w, pyr.level(y, l) if yoff is None else y, pyr.rows[l], C, N,
+                    None, None, NONE, None, None, None, 0, None, h * wd, bias, None, None, out_act,
+                    None, None, ybs, 0 if yoff is None else yoff[l], None, 0)
+
     def _head(self, hname: str, feats: List[Feat], per_anchor: int, out: torch.Tensor, A: int, out_act: int,
-              train: bool, tape: dict):
+              train: bool, tape: Tape):
         """Regressor / Classifier over all 5 pyramid levels per launch (conv weights shared across levels, BN per level:
         bn_list.<lvl>.<i> sit head_layers*C channels apart in the contiguous BN arrays)."""
         ps, spec, pyr = self.ps, self.spec, self._pyr
         C, nl = feats[0].C, spec.head_layers
-        nout = spec.num_anchors * per_anchor
         lev_stride = nl * C
         off0 = ps.bn_off[f"{hname}.bn_list.0.0"]
         for lvl in range(5):
             for i in range(nl):
                 assert ps.bn_off[f"{hname}.bn_list.{lvl}.{i}"] == off0 + lvl * lev_stride + i * C
-        desc = pyr["desc"]
-        # Pack forward (grouped frozen nets): the pyramid GEMM's 128-row tiles must not straddle two nets' rows, i.e. every level needs
-        # images_per_group * H * W % 128 == 0.  D4 / 768^2 at B = 8 misses that on the 6 x 6 level only (288 rows per net): the launches
-        # then cover the leading levels and each trailing level runs as a plain launch of its own - few rows, so the GEMM lands on the
-        # 32-row skinny kernel, whose tiles divide 288 (csrc/pw_gemm.hip pw_dispatch checks the tile height of the kernel it takes).
-        nsplit = 5
-        if self._grp is not None:
-            good = [(self._grp[1] * h * w) % 128 == 0 for h, w in pyr["sizes"]]
-            nsplit = good.index(False) if False in good else 5
-            if any(good[nsplit:]) or nsplit == 0:
-                raise RuntimeError("pack forward: pyramid levels %r at %d images per net do not split into whole-tile and small trailing levels" % (pyr["sizes"], self._grp[1]))
-            if nsplit < 5:
-                key = ("desc", nsplit)
-                if key not in pyr:
-                    flat = [nsplit, pyr["B"]]
-                    for h, w in pyr["sizes"][:nsplit]:
-                        flat += [h, w]
-                    pyr[key] = (ctypes.c_int * len(flat))(*flat)
-                desc = pyr[key]
-        tail = list(range(nsplit, 5))
-
-        def lv(t, l):                      # level l's rows of a pyramid row buffer
-            return t[pyr["row0"][l]:pyr["row0"][l] + pyr["rows"][l]]
-
-        def dw_tail(x, wkey, y, xf):       # the trailing levels of a depthwise pyramid launch, one plain launch each
-            sc, sh, act = xf[0], xf[1], xf[2]
-            for l in tail:
-                h, w = pyr["sizes"][l]
-                lo = l * lev_stride
-                self._c("mmd_dwconv_fwd", lv(x, l), ps.w(wkey), lv(y, l), pyr["B"], h, w, C, 3, 1, sc[lo:] if sc is not None else None,
-                        sh[lo:] if sh is not None else None, act, None, None, None, 0, None, None, NONE, None, None, None, 0)
-
+        nsplit = self._head_nsplit()
         cur, cur_xf = self._fcat, (None, None, NONE, None, None, None)     # (scale, shift, act, stats, gamma, beta)
         layers = []
         for i in range(nl):
             cname = f"{hname}.conv_list.{i}"
             o = off0 + i * C
             zd = self._alloc_pyr(pyr, C, train)
-            self._c("mmd_dwconv3_pyr", cur, ps.w(f"{cname}.depthwise_conv.conv.weight"), zd, desc, C, 0, *cur_xf, lev_stride,
-                 None, None, None, NONE, None, None, None, None)
-            dw_tail(cur, f"{cname}.depthwise_conv.conv.weight", zd, cur_xf)
+            self._head_dw(cur, cname, zd, cur_xf, nsplit, lev_stride)
             z = self._alloc_pyr(pyr, C, train)
             st = self.stats_flat[2 * o:] if train else None
-            self._c("mmd_pwconv_fwd_pyr" + self._sfx, zd, ps.w(f"{cname}.pointwise_conv.conv.weight"), z, desc, C, C,
-                 ps.w(f"{cname}.pointwise_conv.conv.bias"), NONE, st, lev_stride, 0, None)
-            for l in tail:
-                h, w = pyr["sizes"][l]
-                self._c("mmd_pwconv_fwd" + self._sfx, lv(zd, l), ps.w(f"{cname}.pointwise_conv.conv.weight"), lv(z, l), pyr["rows"][l], C, C,
-                        None, None, NONE, None, None, None, 0, None, h * w, ps.w(f"{cname}.pointwise_conv.conv.bias"), None, None, NONE,
-                        None, None, 0, 0, None, 0)
+            self._head_pw(zd, cname, z, C, NONE, st, lev_stride, nsplit)
             if train:
                 for lvl in range(5):
                     ol = o + lvl * lev_stride
-                    self.bn_count_host[ol:ol + C] = float(pyr["rows"][lvl])
+                    self.bn_count_host[ol:ol + C] = float(pyr.rows[lvl])
                 nxt_xf = (None, None, SWISH, st, ps.flat[ps.gamma_off + o:], ps.flat[ps.beta_off + o:])
             else:
                 nxt_xf = (ps.fold_scale[o:], ps.fold_shift[o:], SWISH, None, None, None)
-            layers.append({"x": cur, "x_off": None if i == 0 else off0 + (i - 1) * C, "zd": zd, "z": z, "off": o})
+            layers.append(HeadLayerRec(cur, None if i == 0 else off0 + (i - 1) * C, zd, z, o))
             cur, cur_xf = z, nxt_xf
         zd = self._alloc_pyr(pyr, C, train)
-        self._c("mmd_dwconv3_pyr", cur, ps.w(f"{hname}.header.depthwise_conv.conv.weight"), zd, desc, C, 0, *cur_xf, lev_stride,
-             None, None, None, NONE, None, None, None, None)
-        dw_tail(cur, f"{hname}.header.depthwise_conv.conv.weight", zd, cur_xf)
+        self._head_dw(cur, f"{hname}.header", zd, cur_xf, nsplit, lev_stride)
         aoff, yoff = 0, []
-        for (h, w) in pyr["sizes"]:
+        for (h, w) in pyr.sizes:
             yoff.append(aoff * per_anchor)
             aoff += h * w * spec.num_anchors
-        yoff_c = (ctypes.c_longlong * 5)(*yoff)
-        self._c("mmd_pwconv_fwd_pyr" + self._sfx, zd, ps.w(f"{hname}.header.pointwise_conv.conv.weight"), out, desc, C, nout,
-             ps.w(f"{hname}.header.pointwise_conv.conv.bias"), out_act, None, 0, A * per_anchor, yoff_c)
-        for l in tail:
-            h, w = pyr["sizes"][l]
-            self._c("mmd_pwconv_fwd" + self._sfx, lv(zd, l), ps.w(f"{hname}.header.pointwise_conv.conv.weight"), out, pyr["rows"][l], C, nout,
-                    None, None, NONE, None, None, None, 0, None, h * w, ps.w(f"{hname}.header.pointwise_conv.conv.bias"), None, None, out_act,
-                    None, None, A * per_anchor, yoff[l], None, 0)
-        if train:
-            tape[hname] = {"layers": layers, "hx": cur, "hx_off": off0 + (nl - 1) * C, "hzd": zd, "yoff": yoff,
-                           "lev_stride": lev_stride}
+        self._head_pw(zd, f"{hname}.header", out, spec.num_anchors * per_anchor, out_act, None, 0, nsplit, A * per_anchor, yoff)
+        tape.heads[hname] = HeadRec(layers, cur, off0 + (nl - 1) * C, zd, yoff, lev_stride)
 
     # ------------------------------------------------------------------ backward (student)
     def _slot(self, f: Feat) -> GradSlot:
@@ -981,8 +1012,8 @@ class Net:
         """precision "bf16": grouped as well (round 4, mmd_wgrad_grouped_bf16) where the per-layer launches are skeleton-bound - D2 / 512^2 in
         bf16 15.50 -> 14.64 ms/step; at D4 / 768^2 the layers are tall enough that the per-layer launches on the side stream measure the
         same or better (53.0-53.3 vs 53.5-53.8 ms), so tall nets keep them: the rows of the stem output decide."""
-        stem = self.tape.get("stem")
-        return stem is None or stem[1].M <= 600000
+        stem = self.tape.stem
+        return stem is None or stem.out.M <= 600000
 
     def _leaf(self, fn):
         """A leaf of the backward graph other than a 1x1-conv weight gradient (depthwise / squeeze-excite / fusion-weight / bias
@@ -1143,41 +1174,41 @@ class Net:
         call("mmd_dwconv3_pyr", dzd, ps.w(wkey), g, desc, C, 1, None, None, NONE, None, None, None, ls, x, t(self.t_scale), t(self.t_shift),
              NONE if xo is None else SWISH, ps.g(wkey), t(self.t_mean), t(self.t_invstd), sums)
 
-    def _head_bwd(self, hname: str, per_anchor: int, dout: torch.Tensor, tape: dict, pyr: dict, A: int, C: int):
+    def _head_bwd(self, hname: str, per_anchor: int, dout: torch.Tensor, rec: HeadRec, pyr: Pyramid, A: int, C: int):
         """Backward of one head over the whole pyramid; returns the gradient w.r.t. the pyramid feature buffer."""
         spec, ps = self.spec, self.ps
-        rec, nout = tape[hname], spec.num_anchors * per_anchor
-        desc, Mt, ls = pyr["desc"], pyr["total"], rec["lev_stride"]
+        nout = spec.num_anchors * per_anchor
+        desc, Mt, ls = pyr.desc, pyr.total, rec.lev_stride
         dy = self._alloc_pyr(pyr, nout, False)          # (the slice launch writes the padding rows itself; the plain input-gradient GEMMs below write every row)
-        call("mmd_slice_rows_pyr", dout, dy, desc, nout, A * per_anchor, (ctypes.c_longlong * len(rec["yoff"]))(*[int(v) for v in rec["yoff"]]))
+        call("mmd_slice_rows_pyr", dout, dy, desc, nout, A * per_anchor, (ctypes.c_longlong * len(rec.yoff))(*[int(v) for v in rec.yoff]))
         hw_key = f"{hname}.header.pointwise_conv.conv.weight"
         self._leaf(lambda dy=dy, gb=ps.g(f"{hname}.header.pointwise_conv.conv.bias"): call("mmd_colsum", dy, gb, Mt, nout))
-        self._pw_wgrad(dy, rec["hzd"], ps.g(hw_key), Mt, C, nout)
+        self._pw_wgrad(dy, rec.hzd, ps.g(hw_key), Mt, C, nout)
         dzd = self._alloc_pyr(pyr, C, False)
         call("mmd_pwconv_bwd_data" + self._sfx, dy, ps.w_t(hw_key), dzd, Mt, C, nout, 0)
-        xo = rec["hx_off"]
+        xo = rec.hx_off
         # the depthwise weight gradient rides in the (flipped) input-gradient launch: a leaf launch's kernel time is paid in full; so do
         # the sums of the BatchNorm backward that consumes g (x's producer), instead of a reduce pass over (g, z): every layer's `sums`
         # below were filled by the depthwise launch behind it
         bsums = self._zalloc((2 * 5 * ls,), torch.float64)
-        off0 = rec["layers"][0]["off"]
+        off0 = rec.layers[0].off
         g = self._alloc_pyr(pyr, C)
-        self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec["hx"], xo, bsums[2 * (xo - off0):])
+        self._pyr_dw_bwd(dzd, f"{hname}.header.depthwise_conv.conv.weight", g, desc, C, ls, rec.hx, xo, bsums[2 * (xo - off0):])
         for i in reversed(range(spec.head_layers)):
-            L = rec["layers"][i]
+            L = rec.layers[i]
             cname = f"{hname}.conv_list.{i}"
-            o = L["off"]
+            o = L.off
             sums = bsums[2 * (o - off0):]
             dz = self._alloc_pyr(pyr, C)
-            call("mmd_bn_bwd_apply_pyr", g, L["z"], self.t_mean[o:], self.t_invstd[o:], ps.flat[ps.gamma_off + o:], sums, desc, ls, dz,
+            call("mmd_bn_bwd_apply_pyr", g, L.z, self.t_mean[o:], self.t_invstd[o:], ps.flat[ps.gamma_off + o:], sums, desc, ls, dz,
                  ps.grad[ps.gamma_off + o:], ps.grad[ps.beta_off + o:], C, self.t_scale[o:], self.t_shift[o:], SWISH)
             wkey = f"{cname}.pointwise_conv.conv.weight"
-            self._pw_wgrad(dz, L["zd"], ps.g(wkey), Mt, C, C)
+            self._pw_wgrad(dz, L.zd, ps.g(wkey), Mt, C, C)
             dzd = self._alloc_pyr(pyr, C, False)
             call("mmd_pwconv_bwd_data" + self._sfx, dz, ps.w_t(wkey), dzd, Mt, C, C, 0)
-            xo = L["x_off"]
+            xo = L.x_off
             g = self._alloc_pyr(pyr, C)
-            self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L["x"], xo,
+            self._pyr_dw_bwd(dzd, f"{cname}.depthwise_conv.conv.weight", g, desc, C, ls, L.x, xo,
                              None if xo is None else bsums[2 * (xo - off0):])
         return g
 
@@ -1205,8 +1236,7 @@ class Net:
     def _backward_heads(self, dcls_logit, dreg, dfeats, dfeat_pyr):
         """Both heads, every layer over the whole pyramid in one launch; their input gradients (+ dfeats) land in the last BiFPN cell's slots."""
         spec, ps, tape, pyr = self.spec, self.ps, self.tape, self._pyr
-        feats, C = tape["feats"], tape["feats"][0].C
-        lv = lambda t, lvl: t[pyr["row0"][lvl]:pyr["row0"][lvl] + pyr["rows"][lvl]]      # level lvl's rows of a pyramid row buffer
+        feats, C = tape.feats, tape.feats[0].C
         fold_heads = ps.flat.is_cuda and (dfeat_pyr is not None or all(d is None for d in dfeats))
         if not fold_heads:
             for f, d in zip(feats, dfeats):
@@ -1224,7 +1254,7 @@ class Net:
             if use_side:
                 self._side.wait_event(fork)
             with torch.cuda.stream(self._side if use_side else main_stream):
-                gparts.append(self._head_bwd(hname, per_anchor, dout, tape, pyr, tape["A"], C))
+                gparts.append(self._head_bwd(hname, per_anchor, dout, tape.heads[hname], pyr, tape.A, C))
         if main_stream is not None:
             main_stream.wait_stream(self._side)
         gsum = gparts[0]
@@ -1233,29 +1263,29 @@ class Net:
             quads = []
             for lvl, f in enumerate(feats):
                 sl, xs = self._contrib(f, True)
-                sl.t = lv(gsum, lvl)
+                sl.t = pyr.level(gsum, lvl)
                 quads.append(NO_SUMS_QUAD if xs is None else [t.data_ptr() for t in xs.quad])
             arrs = [(ctypes.c_void_p * 5)(*col) for col in zip(*quads)]         # (z, mean, invstd, sums), each one pointer per level
-            call("mmd_pyr_add_bnsums", gparts[0], gparts[1], dfeat_pyr, gsum, pyr["desc"], C, *arrs)
+            call("mmd_pyr_add_bnsums", gparts[0], gparts[1], dfeat_pyr, gsum, pyr.desc, C, *arrs)
         else:
             call("mmd_scale_acc", gparts[1], gsum, None, 0, 0, 1, gsum.numel())
             for lvl, f in enumerate(feats):
-                self._acc(f, lv(gsum, lvl))
+                self._acc(f, pyr.level(gsum, lvl))
 
     def _backward_bifpn(self):
         """BiFPN cells and nodes in reverse; ONE launch at the end finishes all fusion-weight gradients (the nodes' dot products: wdot_all)."""
         spec, ps, tape = self.spec, self.ps, self.tape
-        n_nodes = sum(len(tape[f"bifpn.{c}.nodes"]) for c in range(spec.fpn_cells))
+        n_nodes = sum(len(nodes) for nodes in tape.nodes)
         wdot_all = self._zalloc((4 * n_nodes,))
         theta_desc = []
         for c in reversed(range(spec.fpn_cells)):
             cell = f"bifpn.{c}"
-            for rec in reversed(tape[cell + ".nodes"]):
-                if self._slot(rec["out"]).t is None:
+            for rec in reversed(tape.nodes[c]):
+                if self._slot(rec.out).t is None:
                     continue          # node output unused downstream (cannot happen in this topology)
                 n = len(theta_desc)
                 self._node_bwd(cell, rec, wdot_all[4 * n:4 * n + 4])
-                theta_desc.append((ps.entries[f"{cell}.{rec['theta']}"].off, ps.w(f"{cell}.{rec['theta']}").numel()))
+                theta_desc.append((ps.entries[f"{cell}.{rec.theta}"].off, ps.w(f"{cell}.{rec.theta}").numel()))
             if c == 0:
                 self._bifpn_inputs_bwd(cell)
         if theta_desc:
@@ -1266,21 +1296,21 @@ class Net:
                 self._theta_desc[key] = torch.tensor(theta_desc, dtype=torch.int64, device=self.device)
             self._leaf(lambda d=self._theta_desc[key], n=len(theta_desc): call("mmd_bifpn_theta_bwd_batched", ps.flat, ps.grad, wdot_all, d, n))
 
-    def _node_bwd(self, cell: str, rec: dict, wdot: torch.Tensor):
+    def _node_bwd(self, cell: str, rec: NodeRec, wdot: torch.Tensor):
         """Backward of one BiFPN node; wdot [4] receives the dot products of its fusion-weight gradient."""
-        ps, out = self.ps, rec["out"]
-        s, name, W = self._slot(out), f"{cell}.{rec['conv']}", out.C
+        ps, out = self.ps, rec.out
+        s, name, W = self._slot(out), f"{cell}.{rec.conv}", out.C
         wkey, dwkey = f"{name}.pointwise_conv.conv.weight", f"{name}.depthwise_conv.conv.weight"
-        L = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.bn", NONE, out.M, W, lazy=True, sums=s.sums if s.have_sums else None)
-        ops = in0, in1, up, pl = rec["in0"], rec["in1"], rec["up"], rec["pl"]
+        L = self._bn_bwd(s.t, rec.z, rec.bn, f"{name}.bn", NONE, out.M, W, lazy=True, sums=s.sums if s.have_sums else None)
+        ops = in0, in1, up, pl = rec.in0, rec.in1, rec.up, rec.pl
         mode_ = (1 if in1 is not None else 0) | (2 if up is not None else 0) | (4 if pl is not None else 0)
         # whole-node backward (round 4): the node's BatchNorm backward + its 1x1 conv's input gradient (exact fp32 MFMA) + the depthwise /
         # fusion backward in ONE launch instead of a GEMM launch in front of it - 40 launches off the backward's serial chain.  bf16
         # modes: up to width 160 (closer to the fp32 reference than the mode's operand-rounding rule asks for, like the whole-node
         # forward; D2 bf16 13.48 -> 13.25 ms/step); D4 (224) 49.9 -> 52.2: there the bf16 GEMM + two-launch form stays
         full = W % 16 == 0 and W <= 224 and mode_ in (2, 5, 4) and (self.precision == "fp32" or W <= 160)
-        dzd = None if full else self._pw_bwd(L, rec["zd"], wkey, W, None, True)
-        th = ps.w(f"{cell}.{rec['theta']}")
+        dzd = None if full else self._pw_bwd(L, rec.zd, wkey, W, None, True)
+        th = ps.w(f"{cell}.{rec.theta}")
         # One gradient contribution per operand, in the order in0, in1, up, pl; all of them leave the one launch below: the
         # same-resolution operands directly, the upsampled one as 2x2 block sums, the pooled one scattered - added to each
         # window's arg-max with atomics, on top of the earlier contributions (or of zeros: a zero-initialised arena buffer when this
@@ -1311,7 +1341,7 @@ class Net:
         plargs = (grad[3][0], *bnsums[3], own)
         if full:
             # the evaluated dz is stored once for the conv's weight-gradient GEMM (grouped flush)
-            bq, zdf = ps.bn(L.bn_name), rec["zd"]
+            bq, zdf = ps.bn(L.bn_name), rec.zd
             dzm = self._alloc(out.M, W)
             call("mmd_bifpn_node_bwd_full", *xargs, wdot, *gargs, *plargs, scs, shs, L.g, L.z, L.aff.scale, L.aff.mean, L.aff.invstd, L.sums,
                  L.count, ps.w_t(wkey), dzm, bq["dgamma"], bq["dbeta"])
@@ -1326,8 +1356,7 @@ class Net:
     def _bifpn_inputs_bwd(self, cell: str):
         """The first cell's inputs: the p6 / p7 max-pool backward, then the six down-channel convs (into the backbone taps' slots)."""
         tape = self.tape
-        first = tape[cell + ".first"]
-        c6, p6_in, p7_in = first["c6"], first["p6_in"], first["p7_in"]
+        c6, p6_in, p7_in = tape.first
         s7, s6 = self._slot(p7_in), self._slot(p6_in)
         if s7.t is not None:
             self._contrib(p6_in, False)
@@ -1341,12 +1370,12 @@ class Net:
             call("mmd_maxpool_same_bwd_acc2", c6.z, s6.t, sc6.t, None, 0, 0, 0, c6.B, c6.H, c6.W, c6.C, *(xs.quad if xs else NO_SUMS_QUAD))
         for nm in ("p5_down_channel_2", "p4_down_channel_2", "p5_down_channel", "p4_down_channel", "p3_down_channel", "p5_to_p6"):
             name = f"{cell}.{nm}"
-            rec = tape[name]
-            out, x = rec["out"], rec["x"]
+            rec = tape.down[name]
+            out, x = rec.out, rec.x
             s = self._slot(out)
             if s.t is None:
                 continue
-            dz = self._bn_bwd(s.t, rec["z"], rec["bn"], f"{name}.1", NONE, out.M, out.C, lazy=True, sums=s.sums if s.have_sums else None)
+            dz = self._bn_bwd(s.t, rec.z, rec.bn, f"{name}.1", NONE, out.M, out.C, lazy=True, sums=s.sums if s.have_sums else None)
             self._pw_bwd(dz, x, f"{name}.0.conv.weight", out.C, None, True, into=x)
 
     def backward_finish(self, stop_before: int):
@@ -1357,7 +1386,7 @@ class Net:
     def _backward_blocks(self, blocks):
         """Backbone blocks in reverse, then the squeeze-excite FC weight gradients of all of them in one launch."""
         for blk in reversed(blocks):
-            self._block_bwd(blk, self.tape[f"blk{blk.idx}"])
+            self._block_bwd(blk, self.tape.blocks[blk.idx])
         if self._se_wg:
             recs, self._se_wg = self._se_wg, []
             key = tuple((r.dpe.data_ptr(), r.dpr.data_ptr(), r.hpre.data_ptr(), r.pooled.data_ptr(), r.g_reduce_w.data_ptr()) for r in recs)
@@ -1369,22 +1398,22 @@ class Net:
             tab, nb = self._se_wg_tabs[key], recs[0].dpe.shape[0]
             self._leaf(lambda tab=tab, n=len(recs), mx=max(r.C * r.S for r in recs), nb=nb: call("mmd_se_fc_wgrad_batched", tab, n, mx, nb))
 
-    def _block_bwd(self, blk, rec: dict):
+    def _block_bwd(self, blk, rec: BlockRec):
         """Backward of one MBConv block: project conv, squeeze-excite, depthwise conv, expand conv."""
         ps, q = self.ps, f"backbone_net.model._blocks.{blk.idx}"
-        inp, f1 = rec["inp"], rec["f1"]
-        s = self._slot(rec["out"])
+        inp, f1 = rec.inp, rec.f1
+        s = self._slot(rec.out)
         if s.t is None:
             return                # blocks after the last tap do not exist; defensive
         dy, M1, HW1 = s.t, f1.M, f1.H * f1.W
-        dz2 = self._bn_bwd(dy, rec["z2"], rec["bn2"], f"{q}._bn2", NONE, M1, blk.cout, rpi=HW1, mul_b=rec["rs"], lazy=True,
+        dz2 = self._bn_bwd(dy, rec.z2, rec.bn2, f"{q}._bn2", NONE, M1, blk.cout, rpi=HW1, mul_b=rec.rs, lazy=True,
                            sums=s.sums if s.have_sums else None)
         # squeeze-excite backward.  One pass over (z1, g1) pools d(gate) AND the partials of the BN-1 backward sums (the SE kernels finish
         # those sums once dpooled is known, so the expanded tensor is not read by a BN reduce pass); that pass rides in the epilogue of
         # the project conv's input-gradient GEMM, which produces g1
-        a1: Aff = rec["bn1"]
+        a1 = rec.bn1
         pool5 = self._zalloc((5, f1.B, blk.cmid))
-        g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec["gate"], pool5=(f1.z, *a1, pool5, f1.B))
+        g1 = self._pw_bwd(dz2, f1, f"{q}._project_conv.conv.weight", blk.cout, None, True, gate=rec.gate, pool5=(f1.z, *a1, pool5, f1.B))
         # the skip branch may ADOPT dy as the gradient slot of the block input, and the block's own input gradient is later
         # accumulated into that buffer in place; with a lazy BatchNorm backward the project conv's weight-gradient GEMM (side
         # stream) still reads dy, so that later accumulation waits for it (the event is long past by then)
@@ -1397,24 +1426,24 @@ class Net:
         # two wide launches for the two FC data gradients (both in one, mmd_se_fc_bwd_fused, is correct, but every block recomputes its
         # image's hidden gradient - S*C MACs, serial per wave: measured 17.0 -> 17.7 ms/step)
         dh = self._zalloc((f1.B, blk.se))
-        call("mmd_se_fc_bwd", pool5[0], rec["gate"], rec["hpre"], rec["pooled"], ps.w(f"{q}._se_reduce.conv.weight"),
+        call("mmd_se_fc_bwd", pool5[0], rec.gate, rec.hpre, rec.pooled, ps.w(f"{q}._se_reduce.conv.weight"),
              ps.w(f"{q}._se_expand.conv.weight"), dpe, dpr, dh, dpooled, 1.0 / HW1, None, None, None, None, f1.B, blk.cmid, blk.se, pool5, sums1)
         # the FC weight gradients of all blocks of the segment in one launch at its end
-        self._se_wg.append(SeWgRec(dpe, dpr, rec["hpre"], rec["pooled"], *segrads, blk.cmid, blk.se))
-        f0: Feat = rec.get("f0", inp)
+        self._se_wg.append(SeWgRec(dpe, dpr, rec.hpre, rec.pooled, *segrads, blk.cmid, blk.se))
+        f0 = rec.f0
         wkey = f"{q}._depthwise_conv.conv.weight"
         # BatchNorm-1 backward evaluated in the prologue of the depthwise input-gradient launch (stride-1 blocks with an expand conv and
         # >= 64 channels: 17 of D2's 23): dz1 is never written; the other blocks keep the apply pass
         bn1_in_dw = blk.expand != 1 and blk.stride == 1 and blk.cmid >= 64
         if not bn1_in_dw:
-            dz1 = self._bn_bwd(g1, f1.z, a1, f"{q}._bn1", SWISH, M1, blk.cmid, rpi=HW1, mul_bc=rec["gate"], add_bc=dpooled, sums=sums1)
+            dz1 = self._bn_bwd(g1, f1.z, a1, f"{q}._bn1", SWISH, M1, blk.cmid, rpi=HW1, mul_bc=rec.gate, add_bc=dpooled, sums=sums1)
         if blk.expand != 1:
-            a0: Aff = rec["bn0"]
+            a0 = rec.bn0
             if bn1_in_dw:
                 b1 = ps.bn(f"{q}._bn1")
                 g0 = self._alloc(f0.M, f0.C)
                 sums0 = self._zalloc((2 * f0.C,), torch.float64)
-                call("mmd_dwconv_bwd_data_bn1", g1, f1.z, ps.w(wkey), g0, f0.B, f0.H, f0.W, f0.C, blk.kernel, *a1, sums1, M1, rec["gate"],
+                call("mmd_dwconv_bwd_data_bn1", g1, f1.z, ps.w(wkey), g0, f0.B, f0.H, f0.W, f0.C, blk.kernel, *a1, sums1, M1, rec.gate,
                      dpooled, b1["dgamma"], b1["dbeta"], f0.z, *a0, sums0, *self._stats_ws(sums0, f0.M, f0.C), ps.g(wkey))
             else:
                 g0, sums0 = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride, bn_aff=a0)
@@ -1427,8 +1456,8 @@ class Net:
         elif blk.idx == 0 and not blk.skip and blk.stride == 1 and self._slot(inp).t is None:
             # block 0 consumes the stem activation directly and is its only consumer: the stem BN's backward sums ride
             # in this input-gradient launch
-            mu, istd = self.tape["stem"][2:]
-            g0, self._stem_sums = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride, bn_aff=Aff(inp.scale, inp.shift, mu, istd))
+            stem = self.tape.stem
+            g0, self._stem_sums = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride, bn_aff=Aff(inp.scale, inp.shift, stem.mean, stem.invstd))
             self._acc(inp, g0)
         else:
             g0 = self._dw_bwd(dz1, f0, wkey, blk.kernel, blk.stride)
@@ -1438,7 +1467,7 @@ class Net:
 
     def _backward_stem(self):
         ps, tape, P, stem_sums = self.ps, self.tape, "backbone_net.model", self._stem_sums
-        ximg, stem, mu, istd = tape["stem"]
+        ximg, stem, mu, istd = tape.stem
         s = self._slot(stem)
         Bi, Cin, Hi, Wi = ximg.shape
         dll = _lib.LIB.load() if ps.flat.is_cuda else None

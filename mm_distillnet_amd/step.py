@@ -358,9 +358,9 @@ class DistillEngine:
         """Spatial attention maps a[b, j] = mean_c f^p of the five BiFPN outputs of `net` in ONE launch: the final cell writes
         them into one pyramid row buffer (engine._bifpn), so the maps are row slices of one vector.  -> (all, [per level])"""
         pyr, fcat = net._pyr, net._fcat
-        a = self.ws.alloc((pyr["total"],))
-        call("mmd_mta_attention", fcat, a, pyr["total"], fcat.shape[1], self._att_p())
-        return a, [a[pyr["row0"][l]:pyr["row0"][l] + pyr["rows"][l]] for l in range(len(pyr["rows"]))]
+        a = self.ws.alloc((pyr.total,))
+        call("mmd_mta_attention", fcat, a, pyr.total, fcat.shape[1], self._att_p())
+        return a, pyr.levels(a)
 
     def labels_from_rows(self, per_teacher: List[List], A: int) -> List[tuple]:
         """Host pseudo-labels -> the device form `step_body(teacher_labels=...)` takes: per teacher a list of B arrays [n,6]
@@ -421,9 +421,9 @@ class DistillEngine:
             _, a_s = self._attention(st)
             # gradient w.r.t. the student's maps, one vector over the pyramid rows (zeroed: MTA teachers accumulate into it
             # with atomics, and the padding rows of a pyramid must read as zero in the backward)
-            da_all = self.ws.alloc((st._pyr["total"],))
+            da_all = self.ws.alloc((st._pyr.total,))
             call("mmd_memset_async", da_all, 0, da_all.numel() * 4)
-            da = [da_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
+            da = st._pyr.levels(da_all)
         nt = len(self.teachers) + (1 if (cfg.kd_mode == "list" and batch.get("aug_rgb") is not None) else 0)
         kd = self.ws.alloc((nt if cfg.kd_mode == "pairwise" else 1, nlv))
         call("mmd_memset_async", kd, 0, kd.numel() * 4)
@@ -531,9 +531,9 @@ class DistillEngine:
         if train:
             d_all, dfe = None, [None] * nlv
             if use_kd:
-                d_all = st._alloc(st._pyr["total"], feats_s[0].C)
-                call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr["total"], feats_s[0].C, self._att_p(), 0)
-                dfe = [d_all[st._pyr["row0"][l]:st._pyr["row0"][l] + st._pyr["rows"][l]] for l in range(nlv)]
+                d_all = st._alloc(st._pyr.total, feats_s[0].C)
+                call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr.total, feats_s[0].C, self._att_p(), 0)
+                dfe = st._pyr.levels(d_all)
         # cross-teacher merge -> annotations
         boxes, nbox, G = self._merge(rows_t, cnt_t, B, aug)
         # focal + smooth-L1 with gradients w.r.t. (pre-sigmoid) classifier logits and regression

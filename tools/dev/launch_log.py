@@ -2,7 +2,8 @@
 
     python tools/dev/launch_log.py CASE OUT.log          (one fresh process per case; `--list` names the cases)
 
-Two commits issue the same launches iff their logs are equal byte for byte (profiles/engine_backward_notes.md).  The recorder replaces
+Two commits issue the same launches iff their logs are equal byte for byte (profiles/engine_backward_notes.md,
+profiles/engine_forward_notes.md).  The recorder replaces
 mm_distillnet_amd._lib.call BEFORE engine / step are imported, forwards to the real call, and logs per call: the ordinal (by first
 appearance) of the current stream, the entry-point name, and per argument
   int / float          its value
@@ -60,9 +61,11 @@ from mm_distillnet_amd.synth import synth_state, synth_inputs          # noqa: E
 DEV = "cuda:0"
 
 
-def train_steps(precision: str, augment: bool, split: bool, steps: int):
-    """Packed teachers + D2 student, 256^2, B = 2: `steps` eager training steps (split: the two-segment backward of the data-parallel step)."""
-    S, B = 256, 2
+def train_steps(precision: str, augment: bool, split: bool, steps: int, B: int = 2):
+    """Three D2 teachers + D2 student, 256^2: `steps` eager training steps (split: the two-segment backward of the data-parallel step).
+    B = 2: one teacher per stream (8 rows per net on the 2^2 level: no pack); B = 8: the teachers as ONE pack forward, whose 2^2 level (32 rows
+    per net, not whole 128-row tiles) the heads run as plain trailing-level launches."""
+    S = 256
     specs = {"rgb": make_spec(2, 3), "depth": make_spec(2, 3), "thermal": make_spec(2, 1)}
     tstates = {k: synth_state(s, seed=i + 1, cls_bias=-1.0) for i, (k, s) in enumerate(specs.items())}
     sspec = make_spec(2, 8)
@@ -94,6 +97,17 @@ def net_fwd_bwd(coef: int, S: int, precision: str = "fp32", probe: bool = False)
     net.backward(dcls, dreg, dfe)
 
 
+def net_eval(coef: int, S: int, precision: str = "fp32", raw_logits: bool = False, fuse_node: bool = True):
+    """One frozen net outside a pack: eval forward at B = 2 (fuse_node False: the two-launch BiFPN node leg, as tests/test_gpu_net.py sets it)."""
+    spec = make_spec(coef, 3)
+    net = Net(spec, DEV, trainable=False, precision=precision)
+    net.load_state(synth_state(spec, seed=13))
+    net.FUSE_NODE = fuse_node
+    x = synth_inputs(2, S, seed=25)["rgb"].to(DEV)
+    net.begin_step()
+    net.forward(x, raw_logits=raw_logits)
+
+
 CASES = {
     "step_fp32": lambda: train_steps("fp32", False, False, 2),
     "step_bf16_aug": lambda: train_steps("bf16", True, False, 2),
@@ -103,6 +117,13 @@ CASES = {
     "d0": lambda: net_fwd_bwd(0, 128),
     "d1": lambda: net_fwd_bwd(1, 128),                           # width 88
     "d2_probe": lambda: net_fwd_bwd(2, 128, probe=True),         # non-lazy at width 112
+    "pack_fp32": lambda: train_steps("fp32", False, False, 1, B=8),     # the pack forward with a trailing level (the cases above do not pack)
+    "pack_bf16": lambda: train_steps("bf16", False, False, 1, B=8),
+    # frozen single-net forwards
+    "eval_d2_fp32": lambda: net_eval(2, 128),
+    "eval_d2_bf16_raw": lambda: net_eval(2, 128, "bf16", raw_logits=True),
+    "eval_d2_two_launch": lambda: net_eval(2, 128, fuse_node=False),
+    "eval_d4": lambda: net_eval(4, 256),                         # width 224: the NODE_FUSE_WIDE_MAXROWS branch of _node_fusable
 }
 
 
