@@ -16,8 +16,8 @@ import math
 import numbers
 import os
 
-from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Any, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -43,6 +43,89 @@ def check_box_loss(name, weight) -> None:
         raise ValueError(f"box_weight {weight!r}: a finite weight > 0")
     if name == "smooth_l1" and weight != 1:
         raise ValueError(f"box_weight {weight!r} with box_loss smooth_l1: upstream's criterion has no weight (1 only)")
+
+
+class TeacherPass(NamedTuple):
+    """One frozen-net forward of a step that runs on its own (outside the pack)."""
+    mod: str                        # the batch entry it reads, or "augmentation" (the KD-list variant's second RGB pass, which reads `x`)
+    net: Net
+    stream_idx: int                 # its side stream: the teacher's position in ModuleDict order (the second RGB pass: the RGB teacher's)
+    label_idx: int                  # its entry of injected teacher_labels = its place among the sources (the second RGB pass: the last)
+    x: Optional[torch.Tensor]       # the second RGB pass' input; None: the teacher's own modality
+
+
+class TeacherOut(NamedTuple):
+    """What one pseudo-label source hands the losses; a step holds one per source, in source order (the teachers in ModuleDict order, then
+    the second RGB pass)."""
+    rows: torch.Tensor              # [B, cap, 6] (x1, y1, x2, y2, score, label)
+    cnt: torch.Tensor               # [B] int32
+    att: Optional[list]             # per pyramid level its attention map; None with kd_loss = None
+
+
+class TeacherRun(NamedTuple):
+    """What every teacher leg of one step reads."""
+    batch: Dict[str, torch.Tensor]
+    audio: torch.Tensor             # the student's input (after the audio merge)
+    B: int
+    A: int
+    aug: bool
+    use_kd: bool
+    labels: Optional[List[tuple]]   # injected teacher_labels, else the teachers decode their own
+    fork_event: Any                 # recorded on `main` before the student forward; None: no side streams, every leg runs on `main`
+    main: Any
+
+
+class EvalRecord(NamedTuple):
+    """The evaluation record between begin_eval and end_eval: up to max_images images, max_rows predictions (of images that have ground
+    truth) and max_gt ground-truth boxes over the whole evaluation.  One int32 buffer `buf` (12 bytes per row, 12 per image, 4 per box):
+    cursor[3] + overflow | tp mask [max_rows] | (score, class) `rows` [max_rows, 2] | (sum dx, sum dy, n) `cd` [max_images, 3] | `gt` class
+    [max_gt]; the other tensor fields are views of it."""
+    buf: torch.Tensor
+    cursor: torch.Tensor
+    overflow: torch.Tensor
+    tp: torch.Tensor
+    rows: torch.Tensor
+    cd: torch.Tensor
+    gt: torch.Tensor
+    max_rows: int
+    max_images: int
+    max_gt: int
+
+    def capacity_message(self) -> str:
+        return ("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
+                % (self.max_images, self.max_rows, self.max_gt))
+
+
+class CapturedStep(NamedTuple):
+    """One captured step variant: its static inputs, the graphs (g_tail None when the backward is not split) and the outputs they write."""
+    static: Dict[str, torch.Tensor]
+    g_main: Any
+    g_tail: Any
+    g_opt: Any
+    out: Dict[str, Any]
+
+
+def smallest_level_rows(S: int, B: int) -> int:
+    """rows per net on the smallest pyramid level (S/128 squared pixels per image)"""
+    return B * (S // 128) ** 2
+
+
+def pack_eligible(S: int, B: int, G: int, aug: bool, node_whole: bool, pack: bool) -> bool:
+    """Do the G frozen teachers of a step at S^2, batch B, run as ONE pack forward?  pack: the engine holds a pack (DistillEngine.pack);
+    node_whole: every BiFPN node of the smallest level runs on the whole-node kernel (DistillEngine._node_whole).
+
+    The pack runs every layer of all the frozen teachers as ONE launch over G x B images with per-group weights, on one side stream.  It needs
+    whole 128-row tiles per group on every pyramid level (the smallest, S/128 squared, decides) and no per-teacher feature surgery (the
+    augmented variant averages images 0 / 1 of each teacher's maps).
+    The smallest level needs whole 32-row tiles per net only - the heads run a level that misses the 128-row tiles as plain launches on the
+    skinny kernel, engine.Net._head - so D4 / 768^2 at B = 8, 288 rows per net on its 6 x 6 level, packs too.
+    The 32-row relaxation holds only where EVERY per-net launch on that level is covered - the heads split it off themselves, the BiFPN nodes
+    only on the whole-node kernel, which has no row-tile constraint; a width without one (88 / 288 / 384: D1, D5 - D7), the wide form past
+    its row cap or a net with the `FUSE_NODE` test hook off send that level's nodes through mmd_pwconv_fwd, whose 64- / 128-row kernels
+    refuse a tile that straddles two nets: those geometries keep the whole-128-row-tile rule, i.e. run one net per stream as before."""
+    rows_small = smallest_level_rows(S, B)
+    return bool(pack and G > 1 and not aug and S % 128 == 0 and
+                (rows_small % 128 == 0 or (rows_small % 32 == 0 and node_whole)))
 
 
 @dataclass
@@ -125,10 +208,10 @@ class DistillEngine:
         slot = max(s.stem_out * ((s.in_channels * 9 + 3) // 4 * 4) for s in teacher_specs.values())
         self.teachers: Dict[str, Net] = {m: Net(teacher_specs[m], device, trainable=False, precision=cfg.precision, stem_slot=slot)
                                          for m in TEACHER_ORDER if m in teacher_specs}
-        # Round 4, teacher pack: the frozen teachers share one body architecture, so each layer of all of them runs as ONE launch over
+        # Teacher pack: the frozen teachers share one body architecture, so each layer of all of them runs as ONE launch over
         # 3 x B images with per-group weights instead of three launches on three streams (fewer, fatter launches beside the student's
         # chain: tools/dev/diag_phases.py proxy - student forward + a frozen net at batch 3B 7.28 ms against 8.41 with three nets on three
-        # streams).  MMD_NO_PACK=1: one net per stream, the round-3 schedule
+        # streams).  MMD_NO_PACK=1: one net per stream
         tl = list(self.teachers.values())
         self.pack = (len(tl) > 1 and not os.environ.get("MMD_NO_PACK") and str(device).startswith("cuda")
                      and pack_nets(tl))
@@ -159,13 +242,12 @@ class DistillEngine:
         self.label_map = torch.tensor(lm, dtype=torch.int32, device=device)
         self.valid_mask = valid_class_mask(cfg.valid_prediction_ids)
         self.cap = int(cfg.cand_cap)     # 0: set to the anchor count at the first step
-        self._eval: Optional[dict] = None  # the evaluation record between begin_eval and end_eval
+        self._eval: Optional[EvalRecord] = None
         self._merge_aux = None             # label_merge = wbf: the last merge's [B, G, 3] (mean score, members, sources) per fused box
-        self.graph = None
-        self._graphs: Dict[str, tuple] = {}       # step variant ("plain" / "aug") -> (static inputs, g_main, g_tail, g_opt, outputs)
-        self.concurrent_teachers = True
+        self._graphs: Dict[str, CapturedStep] = {}       # by step variant ("plain" / "aug")
+        self.on_gpu = torch.cuda.is_available() and str(device).startswith("cuda")
+        self.concurrent_teachers = True    # the teachers on side streams beside the student; a step of an engine off the GPU turns it off
         self.side_streams: List = []
-        self.fork_stream = True if torch.cuda.is_available() and str(device).startswith("cuda") else None
         self.static: Dict[str, torch.Tensor] = {}
         self.out: Dict[str, torch.Tensor] = {}
         self.n_skip = sum(1 for b in student_spec.blocks if b.skip)
@@ -306,8 +388,10 @@ class DistillEngine:
             self.cap = A
         return self.cap
 
-    def _nms_ws(self, B: int, nmax: int):
-        return nms_workspace(self.ws, B, nmax)
+    def _begin_workspace(self, B: int):
+        """Start the step workspace afresh; the NMS kernels' mask words come first in it."""
+        self.ws.reset()
+        self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
 
     def _merge(self, rows_t, cnt_t, B: int, augment: bool):
         """cross-teacher concat + NMS (cfg label_merge = nms, upstream's) or weighted box fusion (wbf) -> (boxes [B,G,5], nbox [B], G).
@@ -326,7 +410,7 @@ class DistillEngine:
         vp = ctypes.c_void_p
         srcs = (vp * nt)(*[t.data_ptr() for t in rows_t]); cnts = (vp * nt)(*[t.data_ptr() for t in cnt_t])
         call("mmd_nms_merge_n", srcs, cnts, nt, float(self.cfg.merge_iou), 1 if self.cfg.inclusive_nms else 0, B, boxes, nbox, G,
-             self.mask_ws, self.overflow, 1 if augment else 0, cap, self._nms_ws(B, nmax))
+             self.mask_ws, self.overflow, 1 if augment else 0, cap, nms_workspace(self.ws, B, nmax))
         return boxes, nbox, G
 
     def merge_labels(self, rows_t: List[torch.Tensor], cnt_t: List[torch.Tensor], augment: bool = False):
@@ -337,12 +421,10 @@ class DistillEngine:
         if not rows_t or len(rows_t) != len(cnt_t):
             raise ValueError("merge_labels: one count array per source")
         B, cap = int(rows_t[0].shape[0]), int(rows_t[0].shape[1])
-        if self.cap <= 0:
-            self.cap = cap
+        self._caps(cap)
         if any(tuple(r.shape) != (B, self.cap, 6) for r in rows_t):
             raise ValueError(f"merge_labels: every source is [B, {self.cap}, 6] (the engine's candidate capacity)")
-        self.ws.reset()
-        self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
+        self._begin_workspace(B)
         boxes, nbox, _ = self._merge(list(rows_t), list(cnt_t), B, bool(augment))
         return boxes, nbox, self._merge_aux
 
@@ -366,7 +448,6 @@ class DistillEngine:
         """Host pseudo-labels -> the device form `step_body(teacher_labels=...)` takes: per teacher a list of B arrays [n,6]
         (x1, y1, x2, y2, score, class: what `logits_to_ground_truth(include_scores=True)` returns,
         src/utils/utils.py:234-324) -> (rows [B, cap, 6] fp32, count [B] int32)."""
-        import numpy as np
         self._caps(A)
         out = []
         for lab in per_teacher:
@@ -391,170 +472,218 @@ class DistillEngine:
         train=False: the losses of `validate()` (src/optimization/train_methods.py:1083-1185): eval-mode student (running
         BatchNorm statistics, no drop-connect), same pseudo-labels and loss terms, no backward."""
         cfg = self.cfg
-        st = self.student
-        S = cfg.image_size
         B = batch["audio"].shape[0]
         # validate() upstream calls model(..., validate=True) with `augment` left at its default False
         # (src/optimization/train_methods.py:1083-1185): the validation losses never see the audio merge / feature averaging / label merge
         aug = bool(cfg.augment and train)
-        self.ws.reset()
-        self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
-        if self.fork_stream is None:
+        use_kd = cfg.kd_loss != "None"          # kd_loss = None: no attention maps, no KD term, no feature gradient (loss_kd = zeros upstream)
+        aug_pass = cfg.kd_mode == "list" and batch.get("aug_rgb") is not None      # the KD-list variant's second RGB pass: one more source
+        self._begin_workspace(B)
+        fork_event = self._fork()
+        audio, cls_s, reg_s, feats_s = self._student_forward(batch, drop_scale, train, aug)
+        A = cls_s.shape[1]
+        self._caps(A)
+        a_s, da_all, kd = self._kd_buffers(use_kd, len(self.teachers) + (1 if aug_pass else 0), len(feats_s))
+        run = TeacherRun(batch, audio, B, A, aug, use_kd, teacher_labels, fork_event, torch.cuda.current_stream())
+        outs = self._run_teachers(run, self._teacher_passes(batch, aug_pass))
+        self._join_teachers(run)
+        if use_kd:
+            self._kd_losses(outs, a_s, da_all, feats_s, kd, B)
+        d_all = self._kd_feature_grad(da_all, feats_s) if train and use_kd else None
+        rows_t, cnt_t = [o.rows for o in outs], [o.cnt for o in outs]
+        boxes, nbox, G = self._merge(rows_t, cnt_t, B, aug)      # cross-teacher merge -> annotations
+        main, dcls, dreg = self._main_loss(cls_s, reg_s, boxes, nbox, G, B, train)
+        if train:
+            self._start_backward(dcls, dreg, d_all, len(feats_s))
+        self.out = {"reg": main[0:1], "cls": main[1:2], "kd": kd, "boxes": boxes, "nbox": nbox, "label_aux": self._merge_aux,
+                    "cls_s": cls_s, "reg_s": reg_s, "feats_s": feats_s, "rows_t": rows_t, "cnt_t": cnt_t}
+        return self.out
+
+    def _fork(self):
+        """-> the event the teachers' side streams start behind, recorded before the student forward is enqueued; None: no side streams
+        (`concurrent_teachers` off, which an engine off the GPU sets here for good)."""
+        if not self.on_gpu:
             self.concurrent_teachers = False
-        fork_event = None
-        if self.concurrent_teachers:
-            # teachers fork from here, before the student forward is enqueued
-            fork_event = torch.cuda.current_stream().record_event()
+        return torch.cuda.current_stream().record_event() if self.concurrent_teachers else None
+
+    def _student_forward(self, batch, drop_scale, train: bool, aug: bool):
+        """-> (audio, cls_s, reg_s, feats_s): the student's input as it ran (after the audio merge) and its outputs."""
+        st = self.student
         st.begin_step()
         audio = batch["audio"]
+        B = audio.shape[0]
         if aug and B >= 2:      # merge_batch_0_1: image 1 <- log10(a0^10 + a1^10), out of place
             merged = st._alloc(*audio.shape)
             call("mmd_audio_merge01", audio, merged, audio[0].numel(), B)
             audio = merged
         st.mark_block, st.mark_event = int(os.environ.get("MMD_PACK_STAGGER", "-1")), None      # (dev: hold the teacher pack until the student passed block k)
         cls_s, reg_s, feats_s = st.forward(audio, train=train, drop_scale=drop_scale if train else None)
-        A = cls_s.shape[1]
-        self._caps(A)
-        nlv = len(feats_s)
-        use_kd = cfg.kd_loss != "None"          # kd_loss = None: no attention maps, no KD term, no feature gradient (loss_kd = zeros upstream)
+        return audio, cls_s, reg_s, feats_s
+
+    def _kd_buffers(self, use_kd: bool, nt: int, nlv: int):
+        """-> (a_s, da_all, kd): the student's attention maps per level, the gradient w.r.t. them (both None without a KD term) and the
+        zeroed KD loss terms of nt sources - allocated before any teacher runs."""
+        st = self.student
+        a_s = da_all = None
         if use_kd:
             _, a_s = self._attention(st)
             # gradient w.r.t. the student's maps, one vector over the pyramid rows (zeroed: MTA teachers accumulate into it
             # with atomics, and the padding rows of a pyramid must read as zero in the backward)
             da_all = self.ws.alloc((st._pyr.total,))
             call("mmd_memset_async", da_all, 0, da_all.numel() * 4)
-            da = st._pyr.levels(da_all)
-        nt = len(self.teachers) + (1 if (cfg.kd_mode == "list" and batch.get("aug_rgb") is not None) else 0)
-        kd = self.ws.alloc((nt if cfg.kd_mode == "pairwise" else 1, nlv))
+        kd = self.ws.alloc((nt if self.cfg.kd_mode == "pairwise" else 1, nlv))
         call("mmd_memset_async", kd, 0, kd.numel() * 4)
-        # the three frozen teachers are independent of each other and of the student forward: issue them on
-        # side streams (parallel branches of the captured graph) so their many small kernels fill the chip together
-        rows_t, cnt_t, att_t = [], [], []
-        main_stream = torch.cuda.current_stream()
-        concurrent = self.concurrent_teachers and torch.cuda.is_available()
-        if concurrent and not self.side_streams:
-            self.side_streams = [torch.cuda.Stream() for _ in self.teachers]
-        passes = [(mod, net, ti, None) for ti, (mod, net) in enumerate(self.teachers.items())]
-        if cfg.kd_mode == "list" and batch.get("aug_rgb") is not None:
+        return a_s, da_all, kd
+
+    # ---- the frozen teachers: independent of each other and of the student forward, so they are issued on side streams (parallel branches
+    # of the captured graph) and their many small kernels fill the chip together
+    def _teacher_passes(self, batch, aug_pass: bool) -> List[TeacherPass]:
+        passes = [TeacherPass(mod, net, ti, ti, None) for ti, (mod, net) in enumerate(self.teachers.items())]
+        if aug_pass:
             # ModelWithNMSKDListLossAugmented.forward(augment=True) (src/optimization/train_methods.py:73-110): the RGB teacher once more,
             # on `label` = RGB frames of the recordings whose audio was mixed into this batch; its pseudo-labels are concatenated after
             # the teachers' and its features join the MTA list.  Same net object, same side stream: the second pass starts after the
             # first one's labels / attention maps have been taken (stream order), so it may reuse the net's arena.
             if "rgb" not in self.teachers:
                 raise ValueError("the augmentation pass runs the RGB teacher")
-            passes.append(("augmentation", self.teachers["rgb"], list(self.teachers).index("rgb"), batch["aug_rgb"]))
-        # Staggered teachers: the frozen nets have the same layer sequence, so three streams started together run in lockstep - three
-        # MFMA-bound GEMMs at once, then three HBM-bound depthwise convs at once.  Teacher i+1 therefore starts once teacher i is past
-        # the high-resolution stages (its second stride-2 block: D2 block 5): 20.3-20.7 -> 19.9-20.1 ms/step in alternating runs
-        # (profiles/r02_notes.md).  MMD_STAGGER=<block> overrides, -1 disables.  Holding teacher 0 behind the student as well measured
-        # slower (20.3-20.5).
+            rgb = list(self.teachers).index("rgb")
+            passes.append(TeacherPass("augmentation", self.teachers["rgb"], rgb, len(self.teachers), batch["aug_rgb"]))
+        return passes
+
+    def _stagger_block(self) -> int:
+        """Staggered teachers: the frozen nets have the same layer sequence, so three streams started together run in lockstep - three
+        MFMA-bound GEMMs at once, then three HBM-bound depthwise convs at once.  Teacher i+1 therefore starts once teacher i is past
+        the high-resolution stages (its second stride-2 block: D2 block 5): 20.3-20.7 -> 19.9-20.1 ms/step in alternating runs
+        (profiles/r02_notes.md).  MMD_STAGGER=<block> overrides, -1 disables.  Holding teacher 0 behind the student as well measured
+        slower (20.3-20.5)."""
         s2 = [b.idx for b in next(iter(self.teachers.values())).spec.blocks if b.stride == 2]
-        stagger = int(os.environ.get("MMD_STAGGER", str(s2[1] if len(s2) > 1 else -1)))
-        prev_net = None
-        # teacher pack (round 4): every layer of all the frozen teachers as ONE launch over G x B images with per-group weights, on one side
-        # stream.  Needs whole 128-row tiles per group on every pyramid level (the smallest, S/128 squared, decides) and no per-teacher
-        # feature surgery (the augmented variant averages images 0 / 1 of each teacher's maps)
+        return int(os.environ.get("MMD_STAGGER", str(s2[1] if len(s2) > 1 else -1)))
+
+    def _node_whole(self, B: int) -> bool:
+        """pack_eligible's `node_whole`: do the BiFPN nodes of the teachers' smallest level run on the whole-node kernel?"""
+        net = next(iter(self.teachers.values()))
+        rows = len(self.teachers) * smallest_level_rows(self.cfg.image_size, B)
+        return bool(net.FUSE_NODE and net.ps.flat.is_cuda and
+                    _lib.LIB.load().mmd_bifpn_node_fused_supported(net.spec.fpn_w) == 1 and
+                    (net.spec.fpn_w <= 160 or rows <= net.NODE_FUSE_WIDE_MAXROWS))
+
+    def _run_teachers(self, run: TeacherRun, passes: List[TeacherPass]) -> List[TeacherOut]:
+        """The pack (where the geometry allows one) and every pass outside it -> one TeacherOut per source, in source order."""
         G = len(self.teachers)
-        # (round 5: the smallest level needs whole 32-row tiles per net only - the heads run a level that misses the 128-row tiles as plain
-        # launches on the skinny kernel, engine.Net._head - so D4 / 768^2 at B = 8, 288 rows per net on its 6 x 6 level, packs too)
-        # (ADVICE r5: the 32-row relaxation holds only where EVERY per-net launch on that level is covered - the heads split it off themselves,
-        # the BiFPN nodes only on the whole-node kernel, which has no row-tile constraint; a width without one (88 / 288 / 384: D1, D5 - D7), the
-        # wide form past its row cap or a net with the `FUSE_NODE` test hook off send that level's nodes through mmd_pwconv_fwd, whose 64- / 128-row kernels refuse
-        # a tile that straddles two nets: those geometries keep the whole-128-row-tile rule, i.e. run one net per stream as before)
-        rows_small = B * (S // 128) ** 2
-        net_f = next(iter(self.teachers.values()))
-        node_whole = bool(net_f.FUSE_NODE and net_f.ps.flat.is_cuda and
-                          _lib.LIB.load().mmd_bifpn_node_fused_supported(net_f.spec.fpn_w) == 1 and
-                          (net_f.spec.fpn_w <= 160 or G * rows_small <= net_f.NODE_FUSE_WIDE_MAXROWS))
-        use_pack = bool(self.pack and G > 1 and not aug and S % 128 == 0 and
-                        (rows_small % 128 == 0 or (rows_small % 32 == 0 and node_whole)))
-        npk = min(G, max(2, int(os.environ.get("MMD_PACK_SPLIT", G))))      # (dev: pack the first npk teachers, the others on their own streams)
-        if use_pack:
-            nets = list(self.teachers.values())[:npk]
-            net0 = nets[0]
-            side = self.side_streams[0] if concurrent else main_stream
-            if concurrent:
-                side.wait_event(fork_event)
-                if st.mark_event is not None:
-                    side.wait_event(st.mark_event)
-            with torch.cuda.stream(side):
-                net0.begin_step()
-                cls_p, reg_p, feats_p = net0.forward([batch[m] for m in list(self.teachers)[:npk]], train=False, pack=nets)
-                if teacher_labels is None:
-                    rows_p, cnt_p = self._pseudo_labels(net0, cls_p, reg_p, npk * B, A, S)
-                if use_kd:
-                    _, a_lv = self._attention(net0)
-            for gi in range(npk):
-                if teacher_labels is not None:
-                    r, c = teacher_labels[gi]
-                else:
-                    r, c = rows_p[gi * B:(gi + 1) * B], cnt_p[gi * B:(gi + 1) * B]
-                rows_t.append(r); cnt_t.append(c)
-                att_t.append([a_lv[l][gi * B * f.H * f.W:(gi + 1) * B * f.H * f.W] for l, f in enumerate(feats_p)] if use_kd else None)
-            passes = [p_ for p_ in passes if p_[3] is not None or p_[2] >= npk]      # (the KD-list variant's extra RGB pass still runs on its own)
-        for pi, (mod, net, si, xin) in enumerate(passes):
-            ti = si if xin is None else G
-            side = self.side_streams[si] if concurrent else main_stream
-            if concurrent and xin is None:
-                side.wait_event(fork_event)
-                if stagger >= 0 and prev_net is not None and prev_net.mark_event is not None:
-                    side.wait_event(prev_net.mark_event)
-                net.mark_block, net.mark_event = stagger, None
-                prev_net = net
-            with torch.cuda.stream(side):
-                net.begin_step()
-                cls_t, reg_t, feats_t = net.forward(xin if xin is not None else (audio if mod == "audio" else batch[mod]), train=False)
-                if aug and B >= 2 and use_kd:      # average_batch_0_1 on the (already consumed by the heads) feature maps
-                    for f in feats_t:
-                        call("mmd_avg_image01", f.z, f.H * f.W * f.C)
-                if teacher_labels is not None:
-                    r, c = teacher_labels[ti]
-                else:
-                    r, c = self._pseudo_labels(net, cls_t, reg_t, B, A, S)
-                at = self._attention(net)[1] if use_kd else None
-            rows_t.append(r); cnt_t.append(c); att_t.append(at)
-        if concurrent:
-            for side in self.side_streams:
-                main_stream.wait_stream(side)
-        # every (level, teacher) KD term of the step in one launch (pairwise: nt x 5 losses; list: 5), then one launch for d attention / d f
-        if use_kd:
-            vp = ctypes.c_void_p
-            p_as = (vp * nlv)(*[t.data_ptr() for t in a_s])
-            p_at = (vp * (nt * nlv))(*[att_t[ti][l].data_ptr() for ti in range(nt) for l in range(nlv)])
-            p_da = (vp * nlv)(*[t.data_ptr() for t in da])
-            hw = (ctypes.c_int * nlv)(*[f.H * f.W for f in feats_s])
-            if cfg.kd_loss == "AttentionLoss":
-                call("mmd_at_loss_multi", p_as, p_at, p_da, hw, nlv, nt, B, kd, float(cfg.w_kd), self.ws.alloc((nt * nlv * B,)))
+        if run.fork_event is not None and not self.side_streams:
+            self.side_streams = [torch.cuda.Stream() for _ in self.teachers]
+        outs: List[TeacherOut] = []
+        if pack_eligible(self.cfg.image_size, run.B, G, run.aug, self._node_whole(run.B), self.pack):
+            npk = min(G, max(2, int(os.environ.get("MMD_PACK_SPLIT", G))))      # (dev: pack the first npk teachers, the others on their own streams)
+            outs += self._run_pack(run, npk)
+            passes = [p for p in passes if p.x is not None or p.stream_idx >= npk]      # (the KD-list variant's extra RGB pass still runs on its own)
+        stagger, prev_net = self._stagger_block(), None
+        for p in passes:
+            outs.append(self._run_teacher(run, p, stagger, prev_net))
+            if p.x is None:
+                prev_net = p.net
+        return outs
+
+    def _side_stream(self, run: TeacherRun, idx: int):
+        return run.main if run.fork_event is None else self.side_streams[idx]
+
+    def _run_pack(self, run: TeacherRun, npk: int) -> List[TeacherOut]:
+        """The first npk teachers as one pack forward on side stream 0, behind the fork (and the student's MMD_PACK_STAGGER block)."""
+        B, st = run.B, self.student
+        nets = list(self.teachers.values())[:npk]
+        net0 = nets[0]
+        side = self._side_stream(run, 0)
+        if run.fork_event is not None:
+            side.wait_event(run.fork_event)
+            if st.mark_event is not None:
+                side.wait_event(st.mark_event)
+        with torch.cuda.stream(side):
+            net0.begin_step()
+            cls_p, reg_p, feats_p = net0.forward([run.batch[m] for m in list(self.teachers)[:npk]], train=False, pack=nets)
+            if run.labels is None:
+                rows_p, cnt_p = self._pseudo_labels(net0, cls_p, reg_p, npk * B, run.A, self.cfg.image_size)
+            if run.use_kd:
+                _, a_lv = self._attention(net0)
+        outs = []
+        for gi in range(npk):
+            rows, cnt = run.labels[gi] if run.labels is not None else (rows_p[gi * B:(gi + 1) * B], cnt_p[gi * B:(gi + 1) * B])
+            att = [a_lv[l][gi * B * f.H * f.W:(gi + 1) * B * f.H * f.W] for l, f in enumerate(feats_p)] if run.use_kd else None
+            outs.append(TeacherOut(rows, cnt, att))
+        return outs
+
+    def _run_teacher(self, run: TeacherRun, p: TeacherPass, stagger: int, prev_net: Optional[Net]) -> TeacherOut:
+        """One net on its side stream: behind the fork and, staggered, behind the previous teacher's `stagger` block."""
+        net, B = p.net, run.B
+        side = self._side_stream(run, p.stream_idx)
+        # (the second RGB pass waits on neither event: it runs on the first RGB pass' stream, behind it in stream order)
+        if run.fork_event is not None and p.x is None:
+            side.wait_event(run.fork_event)
+            if stagger >= 0 and prev_net is not None and prev_net.mark_event is not None:
+                side.wait_event(prev_net.mark_event)
+            net.mark_block, net.mark_event = stagger, None
+        with torch.cuda.stream(side):
+            net.begin_step()
+            cls_t, reg_t, feats_t = net.forward(p.x if p.x is not None else (run.audio if p.mod == "audio" else run.batch[p.mod]), train=False)
+            if run.aug and B >= 2 and run.use_kd:      # average_batch_0_1 on the (already consumed by the heads) feature maps
+                for f in feats_t:
+                    call("mmd_avg_image01", f.z, f.H * f.W * f.C)
+            if run.labels is not None:
+                rows, cnt = run.labels[p.label_idx]
             else:
-                call("mmd_mta_kl_multi", p_as, p_at, p_da, hw, nlv, nt, 0 if cfg.kd_mode == "pairwise" else 1, B, float(cfg.T), kd,
-                     float(cfg.w_kd))
-        if train:
-            d_all, dfe = None, [None] * nlv
-            if use_kd:
-                d_all = st._alloc(st._pyr.total, feats_s[0].C)
-                call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr.total, feats_s[0].C, self._att_p(), 0)
-                dfe = st._pyr.levels(d_all)
-        # cross-teacher merge -> annotations
-        boxes, nbox, G = self._merge(rows_t, cnt_t, B, aug)
-        # focal + smooth-L1 with gradients w.r.t. (pre-sigmoid) classifier logits and regression
-        nc = st.spec.num_classes
+                rows, cnt = self._pseudo_labels(net, cls_t, reg_t, B, run.A, self.cfg.image_size)
+            att = self._attention(net)[1] if run.use_kd else None
+        return TeacherOut(rows, cnt, att)
+
+    def _join_teachers(self, run: TeacherRun):
+        if run.fork_event is not None:
+            for side in self.side_streams:
+                run.main.wait_stream(side)
+
+    def _kd_losses(self, outs: List[TeacherOut], a_s, da_all, feats_s, kd, B: int):
+        """every (level, teacher) KD term of the step in one launch (pairwise: nt x 5 losses; list: 5)"""
+        cfg, nt, nlv = self.cfg, len(outs), len(feats_s)
+        vp = ctypes.c_void_p
+        p_as = (vp * nlv)(*[t.data_ptr() for t in a_s])
+        p_at = (vp * (nt * nlv))(*[o.att[l].data_ptr() for o in outs for l in range(nlv)])
+        p_da = (vp * nlv)(*[t.data_ptr() for t in self.student._pyr.levels(da_all)])
+        hw = (ctypes.c_int * nlv)(*[f.H * f.W for f in feats_s])
+        if cfg.kd_loss == "AttentionLoss":
+            call("mmd_at_loss_multi", p_as, p_at, p_da, hw, nlv, nt, B, kd, float(cfg.w_kd), self.ws.alloc((nt * nlv * B,)))
+        else:
+            call("mmd_mta_kl_multi", p_as, p_at, p_da, hw, nlv, nt, 0 if cfg.kd_mode == "pairwise" else 1, B, float(cfg.T), kd,
+                 float(cfg.w_kd))
+
+    def _kd_feature_grad(self, da_all, feats_s):
+        """one launch for d attention / d f -> the KD gradient w.r.t. the student's BiFPN outputs, one pyramid row buffer"""
+        st = self.student
+        d_all = st._alloc(st._pyr.total, feats_s[0].C)
+        call("mmd_mta_attention_bwd", st._fcat, da_all, d_all, st._pyr.total, feats_s[0].C, self._att_p(), 0)
+        return d_all
+
+    def _main_loss(self, cls_s, reg_s, boxes, nbox, G: int, B: int, train: bool):
+        """focal + box regression loss with gradients w.r.t. (pre-sigmoid) classifier logits and regression -> (main [2] = (reg, cls), dcls, dreg)"""
+        cfg, st = self.cfg, self.student
+        A, nc = cls_s.shape[1], st.spec.num_classes
         assign = self.ws.alloc((B * A,), torch.int32); npos = self.ws.alloc((B,), torch.int32)
         acc = self.ws.alloc((2 * B,), torch.float64); main = self.ws.alloc((2,))
         dcls = st._alloc(B, A, nc); dreg = st._alloc(B, A, 4)
         any_boxes = self.head_active if train else self.ws.alloc((1,), torch.int32)
+        args = (cls_s, reg_s, st.anchors(cfg.image_size), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
+                float(cfg.w_main), 1, any_boxes)
         if cfg.box_loss == "smooth_l1":
-            call("mmd_focal_loss", cls_s, reg_s, st.anchors(S), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
-                 float(cfg.w_main), 1, any_boxes)
+            call("mmd_focal_loss", *args)
         else:      # the same launches with an IoU-family criterion in the regression slot
-            call("mmd_focal_loss_box", cls_s, reg_s, st.anchors(S), boxes, nbox, G, B, A, nc, assign, npos, acc, main, dcls, dreg,
-                 float(cfg.w_main), 1, any_boxes, BOX_LOSSES[cfg.box_loss], float(cfg.box_weight))
-        # backward + optimizer
-        if train and not _lib.dev_switch("MMD_DEV_NO_BWD"):      # (MMD_DEV_NO_BWD=1: timing experiment - forward + losses only)
-            call("mmd_memset_async", st.ps.grad, 0, st.ps.grad.numel() * 4)
-            st.backward(dcls, dreg, dfe, stop_before=self.ar_split, dfeat_pyr=d_all)
-        self.out = {"reg": main[0:1], "cls": main[1:2], "kd": kd, "boxes": boxes, "nbox": nbox, "label_aux": self._merge_aux,
-                    "cls_s": cls_s, "reg_s": reg_s, "feats_s": feats_s, "rows_t": rows_t, "cnt_t": cnt_t}
-        return self.out
+            call("mmd_focal_loss_box", *args, BOX_LOSSES[cfg.box_loss], float(cfg.box_weight))
+        return main, dcls, dreg
+
+    def _start_backward(self, dcls, dreg, d_all, nlv: int):
+        """zero the gradients, then the student's backward up to block `ar_split` (all of it when the backward is not split)"""
+        if _lib.dev_switch("MMD_DEV_NO_BWD"):      # (MMD_DEV_NO_BWD=1: timing experiment - forward + losses only)
+            return
+        st = self.student
+        call("mmd_memset_async", st.ps.grad, 0, st.ps.grad.numel() * 4)
+        dfe = st._pyr.levels(d_all) if d_all is not None else [None] * nlv
+        st.backward(dcls, dreg, dfe, stop_before=self.ar_split, dfeat_pyr=d_all)
 
     def backward_tail(self):
         """Second backward segment (backbone blocks < ar_split + stem); a no-op when the backward is not split."""
@@ -647,13 +776,12 @@ class DistillEngine:
                 gs = 1.0
             ws = self.ws.alloc((1,), torch.float64)
             call("mmd_clip_grad_norm", ps.grad, ps.grad.numel(), float(cfg.grad_clip), ws)
-        r = self.head_ranges
+        args = (ps.flat, ps.grad, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head, self.hyper, self.head_active,
+                *self.head_ranges, float(gs), ps.n_params)
         if self.opt_mode == 0:
-            call("mmd_adam_step_gated", ps.flat, ps.grad, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head,
-                 self.hyper, self.head_active, r[0], r[1], r[2], r[3], r[4], r[5], float(gs), ps.n_params)
+            call("mmd_adam_step_gated", *args)
         else:
-            call("mmd_opt_step_gated", self.opt_mode, ps.flat, ps.grad, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head,
-                 self.hyper, self.head_active, r[0], r[1], r[2], r[3], r[4], r[5], float(gs), ps.n_params)
+            call("mmd_opt_step_gated", self.opt_mode, *args)
         if self.ema_flat is not None:
             # reads ps.flat only, so its order against refresh_wt() does not matter.  Every rank holds the same weights after the
             # all-reduced step, hence the same average: no collective
@@ -683,6 +811,26 @@ class DistillEngine:
     def _variant(batch) -> str:
         return "aug" if (batch is not None and batch.get("aug_rgb") is not None) else "plain"
 
+    def _training_state(self) -> List[torch.Tensor]:
+        """every tensor that a step leaves to the next one (the averaged weights and their update counter too: a warm-up step is not an update)"""
+        ps = self.student.ps
+        state = [ps.flat, ps.rmean, ps.rvar, ps.nbt, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head, self.head_active]
+        if self.ema_flat is not None:
+            state += [self.ema_flat, self.ema_rmean, self.ema_rvar, self.ema_state]
+        return state
+
+    def _warm_up(self, teacher_labels):
+        """two eager steps on the static inputs, on a stream of their own: they size the arenas"""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self.step_body(self.static, self.static["drop_scale"], teacher_labels=teacher_labels)
+                self.backward_tail()
+                self.optimizer_body()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+
     def capture(self, batch: Dict[str, torch.Tensor], teacher_labels: Optional[List[tuple]] = None):
         """Warm up eagerly (sizes the arenas), then capture forward+loss+backward and the optimizer as
         hipGraphs (the backward in two segments when world_size > 1); the gradient all-reduce is launched eagerly between
@@ -699,21 +847,9 @@ class DistillEngine:
         self.static["drop_scale"] = self.make_drop_scale(B)
         torch.cuda.synchronize()
         # snapshot so the warm-up steps do not change the training trajectory
-        ps = self.student.ps
-        # (the averaged weights and their update counter too: a warm-up step is not an update)
-        state = [ps.flat, ps.rmean, ps.rvar, ps.nbt, self.exp_avg, self.exp_avg_sq, self.adam_main, self.adam_head, self.head_active]
-        if self.ema_flat is not None:
-            state += [self.ema_flat, self.ema_rmean, self.ema_rvar, self.ema_state]
+        state = self._training_state()
         snap = [t.clone() for t in state]
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self.step_body(self.static, self.static["drop_scale"], teacher_labels=teacher_labels)
-                self.backward_tail()
-                self.optimizer_body()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        self._warm_up(teacher_labels)
         for arena in arenas:
             arena.frozen = True
         # thread_local: with a process group alive, the RCCL watchdog thread polls its own events; under the default
@@ -735,15 +871,15 @@ class DistillEngine:
             dst.copy_(src)
         self.student.refresh()
         torch.cuda.synchronize()
-        self.graph = True
-        self._graphs[self._variant(batch)] = (self.static, self.g_main, self.g_tail, self.g_opt, out)
+        self._graphs[self._variant(batch)] = CapturedStep(self.static, self.g_main, self.g_tail, self.g_opt, out)
 
     def replay(self, batch: Optional[Dict[str, torch.Tensor]] = None, drop_scale: Optional[torch.Tensor] = None):
         if batch is not None:
             key = self._variant(batch)
             if key not in self._graphs:
                 self.capture(batch)
-            self.static, self.g_main, self.g_tail, self.g_opt, self.out = self._graphs[key]
+            cs = self._graphs[key]
+            self.static, self.g_main, self.g_tail, self.g_opt, self.out = cs.static, cs.g_main, cs.g_tail, cs.g_opt, cs.out
             for k, v in batch.items():
                 if v is not None:
                     self.static[k].copy_(v, non_blocking=True)
@@ -762,21 +898,19 @@ class DistillEngine:
         -> (rows_s [B,cap,6], cnt_s [B], boxes [B,G,5], nbox [B], G, B), all in the step workspace."""
         S = self.cfg.image_size
         B = batch["audio"].shape[0]
-        self.ws.reset()
-        self.mask_ws = self.ws.alloc((B * 1024 * 16,), torch.int64)
+        self._begin_workspace(B)
         st = self.student
         st.refresh()
         st.begin_step()
         cls_s, reg_s, _ = st.forward(batch["audio"], train=False)
         A = cls_s.shape[1]
         rows_s, cnt_s = self._pseudo_labels(st, cls_s, reg_s, B, A, S)
-        rows_t, cnt_t = [], []
+        labels = []
         for mod, net in self.teachers.items():
             net.begin_step()
             cls_t, reg_t, _ = net.forward(batch[mod], train=False)
-            r, c = self._pseudo_labels(net, cls_t, reg_t, B, A, S)
-            rows_t.append(r); cnt_t.append(c)
-        boxes, nbox, G = self._merge(rows_t, cnt_t, B, False)
+            labels.append(self._pseudo_labels(net, cls_t, reg_t, B, A, S))
+        boxes, nbox, G = self._merge([r for r, _ in labels], [c for _, c in labels], B, False)
         return rows_s, cnt_s, boxes, nbox, G, B
 
     @torch.no_grad()
@@ -792,9 +926,7 @@ class DistillEngine:
 
     # ---- evaluation statistics on the device (csrc/evalstats.hip): begin_eval, eval_batch x N, end_eval -> metrics.table_from_stats
     def begin_eval(self, max_images: int, max_rows: int, max_gt: Optional[int] = None):
-        """Allocate and reset the evaluation record: up to max_images images, max_rows predictions (of images that have ground truth) and
-        max_gt ground-truth boxes (default max_rows) over the whole evaluation.  One int32 buffer (12 bytes per row, 12 per image, 4 per box):
-        cursor[3] + overflow | tp mask [max_rows] | (score, class) [max_rows, 2] | (sum dx, sum dy, n) [max_images, 3] | gt class [max_gt]."""
+        """Allocate and reset the evaluation record (EvalRecord has the layout); max_gt defaults to max_rows."""
         max_images, max_rows = int(max_images), int(max_rows)
         max_gt = max_rows if max_gt is None else int(max_gt)
         if min(max_images, max_rows, max_gt) <= 0:
@@ -806,8 +938,8 @@ class DistillEngine:
         rows = buf[o:o + 2 * max_rows].view(torch.float32); o += 2 * max_rows
         cd = buf[o:o + 3 * max_images].view(torch.float32); o += 3 * max_images
         gt = buf[o:o + max_gt].view(torch.float32)
-        self._eval = dict(buf=buf, cursor=buf[0:3], overflow=buf[3:4], tp=tp, rows=rows, cd=cd, gt=gt,
-                          max_rows=max_rows, max_images=max_images, max_gt=max_gt)
+        self._eval = EvalRecord(buf=buf, cursor=buf[0:3], overflow=buf[3:4], tp=tp, rows=rows, cd=cd, gt=gt,
+                                max_rows=max_rows, max_images=max_images, max_gt=max_gt)
 
     @torch.no_grad()
     def eval_batch(self, batch: Dict[str, torch.Tensor]):
@@ -821,8 +953,8 @@ class DistillEngine:
         if n < 0:
             raise RuntimeError(f"mmd_eval_ws_floats({self.cap}, {G}) failed with status {n}")
         ws = self.ws.alloc((B * n,)) if n else None
-        call("mmd_eval_match", rows_s, cnt_s, self.cap, boxes, nbox, G, B, ev["rows"], ev["tp"], ev["max_rows"], ev["cd"],
-             ev["max_images"], ev["gt"], ev["max_gt"], ev["cursor"], ws, ev["overflow"])
+        call("mmd_eval_match", rows_s, cnt_s, self.cap, boxes, nbox, G, B, ev.rows, ev.tp, ev.max_rows, ev.cd,
+             ev.max_images, ev.gt, ev.max_gt, ev.cursor, ws, ev.overflow)
 
     def end_eval(self) -> dict:
         """The record -> plain numpy: score / label float32 [n] and tp int32 [n] (bit k: true positive at IoU 0.5 + 0.05 k) of the
@@ -837,19 +969,18 @@ class DistillEngine:
         if ev is None:
             raise RuntimeError(f"{who} without begin_eval")
         self._eval = None
-        if int(ev["overflow"].item()):
-            raise RuntimeError("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
-                               % (ev["max_images"], ev["max_rows"], ev["max_gt"]))
+        if int(ev.overflow.item()):
+            raise RuntimeError(ev.capacity_message())
         self.check_overflow()
-        nr, ni, ng = (int(v) for v in ev["cursor"].cpu().tolist())
+        nr, ni, ng = (int(v) for v in ev.cursor.cpu().tolist())
         return ev, nr, ni, ng
 
     @staticmethod
     def _record_to_host(ev, nr, ni, ng) -> dict:
-        tp = ev["tp"][:nr].cpu().numpy()
-        rows = ev["rows"][:2 * nr].cpu().numpy().reshape(-1, 2)
-        cd = ev["cd"][:3 * ni].cpu().numpy().reshape(-1, 3)
-        gt = ev["gt"][:ng].cpu().numpy()
+        tp = ev.tp[:nr].cpu().numpy()
+        rows = ev.rows[:2 * nr].cpu().numpy().reshape(-1, 2)
+        cd = ev.cd[:3 * ni].cpu().numpy().reshape(-1, 3)
+        gt = ev.gt[:ng].cpu().numpy()
         return {"score": rows[:, 0].copy(), "label": rows[:, 1].copy(), "tp": tp, "cd": cd, "gt": gt}
 
     def end_eval_table(self, image_size, with_record: bool = False):
@@ -860,7 +991,7 @@ class DistillEngine:
         outside the label range 0 .. 255."""
         from .metrics import table_on_device
         ev, nr, ni, ng = self._close_eval("end_eval_table")
-        table = table_on_device(ev["rows"], ev["tp"], nr, ev["cd"], ni, ev["gt"], ng, image_size)
+        table = table_on_device(ev.rows, ev.tp, nr, ev.cd, ni, ev.gt, ng, image_size)
         return (table, self._record_to_host(ev, nr, ni, ng)) if with_record else table
 
     @torch.no_grad()
@@ -873,9 +1004,8 @@ class DistillEngine:
 
     def check_overflow(self):
         ev = self._eval
-        if ev is not None and int(ev["overflow"].item()):
-            raise RuntimeError("evaluation record capacity exceeded (begin_eval max_images = %d, max_rows = %d, max_gt = %d)"
-                               % (ev["max_images"], ev["max_rows"], ev["max_gt"]))
+        if ev is not None and int(ev.overflow.item()):
+            raise RuntimeError(ev.capacity_message())
         if int(self.overflow.item()):
             raise RuntimeError("pseudo-label capacity exceeded (cfg cand_cap = %d rows / max_boxes = %d per image; 0 = unlimited)"
                                % (self.cfg.cand_cap, self.cfg.max_boxes))

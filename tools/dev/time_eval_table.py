@@ -29,12 +29,12 @@ def fill(eng, n, n_cls, n_img, seed):
     eng.begin_eval(n_img, n, n)
     ev = eng._eval
     rows = np.stack([rng.permutation(n).astype(np.float32) / np.float32(n), rng.integers(0, n_cls, n).astype(np.float32)], axis=1)
-    ev["rows"].copy_(torch.from_numpy(rows.reshape(-1)))
-    ev["tp"].copy_(torch.from_numpy(rng.integers(0, 512, n).astype(np.int32)))
-    ev["cd"].copy_(torch.from_numpy(np.stack([rng.random(n_img) * 300, rng.random(n_img) * 200, rng.integers(1, 9, n_img)], 1)
+    ev.rows.copy_(torch.from_numpy(rows.reshape(-1)))
+    ev.tp.copy_(torch.from_numpy(rng.integers(0, 512, n).astype(np.int32)))
+    ev.cd.copy_(torch.from_numpy(np.stack([rng.random(n_img) * 300, rng.random(n_img) * 200, rng.integers(1, 9, n_img)], 1)
                                     .astype(np.float32).reshape(-1)))
-    ev["gt"].copy_(torch.from_numpy(rng.integers(0, n_cls, n).astype(np.float32)))
-    ev["cursor"].copy_(torch.tensor([n, n_img, n], dtype=torch.int32))
+    ev.gt.copy_(torch.from_numpy(rng.integers(0, n_cls, n).astype(np.float32)))
+    ev.cursor.copy_(torch.tensor([n, n_img, n], dtype=torch.int32))
     torch.cuda.synchronize()
 
 
